@@ -367,6 +367,8 @@ def train_bench(a):
             loss = step()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        if a.dump_outputs:
+            dump_outputs(host_arrays(loss), a.dump_outputs)
         # the same step with the phases bracketed (one extra, untimed in `value`)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
         ev[0].record()
@@ -400,6 +402,45 @@ def train_bench(a):
         out["cpu_baseline"] = {"value": round(1.0 / (tf + tb + ta), 4), "unit": "steps/s", "cores": threads, "kind": "port",
                                "sample": f"1 step of 1 x {N} points: oracle forward {tf:.1f} s + torch.autograd backward {tb:.1f} s + Adam {ta:.2f} s, torch CPU fp32"}
     print(json.dumps(out), flush=True)
+
+
+DUMP_BUDGET_BYTES = 60 * 2 ** 20       # "at most 64 MB": 62.9 MB of data leaves room for the .npy headers
+
+
+def host_arrays(result):
+    """What a caller of the timed path receives from one step, as named float32 / float64 host arrays:
+    the pipeline's / predict_smpl_batch's (meshes, markers, valid, smpl_info) tuple, the model's result dict (--forward-only), a loss tensor (--train)."""
+    def host(v):
+        v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        return v.astype(np.float64 if v.dtype == np.float64 else np.float32)
+
+    if isinstance(result, dict):
+        return {k: host(v) for k, v in sorted(result.items()) if isinstance(v, (torch.Tensor, np.ndarray))}
+    if isinstance(result, tuple):
+        meshes, markers, valid, info = result[:4]
+        out = {"vertices": host(np.stack([m.vertices for m in meshes])), "markers": host(markers), "valid": host(valid)}
+        out.update(zip(("pose", "betas", "global_orient", "transl", "joints"), (host(x) for x in info)))
+        return out
+    return {"output": host(result)}
+
+
+def dump_outputs(arrays, out_dir, budget=DUMP_BUDGET_BYTES):
+    """Write DIR/<name>.npy.  Past `budget` bytes in all, the arrays with a per-point axis (axis 1 of the largest extent) keep a fixed, seeded sample of
+    the points (the same for every run and every build: rng(0)); its indices are written as sample_point_index.npy."""
+    total = sum(v.nbytes for v in arrays.values())
+    if total > budget:
+        n = max(v.shape[1] for v in arrays.values() if v.ndim >= 2)
+        per_point = {k for k, v in arrays.items() if v.ndim >= 2 and v.shape[1] == n}
+        rest = sum(v.nbytes for k, v in arrays.items() if k not in per_point) + 8 * n
+        keep = int(n * (budget - rest) / sum(arrays[k].nbytes for k in per_point))
+        idx = np.sort(np.random.default_rng(0).choice(n, max(1, keep), replace=False))
+        arrays = {k: (np.ascontiguousarray(v[:, idx]) if k in per_point else v) for k, v in arrays.items()}
+        arrays["sample_point_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    print(f"bench.py: wrote {len(arrays)} arrays ({sum(v.nbytes for v in arrays.values()) / 2 ** 20:.1f} MiB) of the last timed step to {out_dir}",
+          file=sys.stderr)
 
 
 def _free_port():
@@ -514,7 +555,11 @@ def main():
     ap.add_argument("--preflight", action="store_true", help="print, WITHOUT touching a GPU, what each of the --gpus N ranks would do: its shard of the "
                     "global batch, the CPU set it would pin itself to, the rendezvous and the RCCL-relevant environment -- so that a failed scaling run "
                     "can be diagnosed from its log")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed in its last step (the "
+                    "arrays its caller receives) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (rank 0); the inputs depend on the arguments only")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     # The GPU phases need ONE host thread; torch's CPU pool (128 threads on the pool's hosts) spinning beside it exhausts the container's CPU quota and freezes
     # the enqueueing thread for up to 100 ms at a time (etch_amd/pipeline.py limit_host_threads; profiles/r06_host_throttling.txt).  The cpu_baseline leg sets
     # its own thread count when it runs, after the timed region.
@@ -588,12 +633,14 @@ def main():
     pts = batches[0]
     timed = [batches[(k + 1) % nbatch] for k in range(a.steps)]
     last = {}
+    final = {}                  # what the caller of the timed path received from its latest step (--dump-outputs)
     sched_report = {"schedule": "none"}
     if dry:
         def step(p=pts):
             time.sleep(0.002)
             last.update(err=p[:, :, 0].mean(1).abs(), valid=torch.ones(B, 86, dtype=torch.bool), x=p[:, :85, 0].contiguous(),
                         status=torch.zeros(B, dtype=torch.int32), frozen=torch.zeros(B, dtype=torch.int64))
+            final["result"] = dict(last)
 
         def run_steps(bs):
             for p in bs:
@@ -612,10 +659,12 @@ def main():
             with torch.no_grad():
                 r, _ = model(p, ["confidence", "direction", "magnitude"], "standard_vector")
             model_results.update(r)
+            final["result"] = r
 
         def full_step(p=pts):
             meshes, markers, valid, info, aux = predict_smpl_batch(args, model, p, "neutral", return_trace=True, **fit_kw)
             tr = aux["err_trace"]
+            final["result"] = (meshes, markers, valid, info)
             last.update(markers=markers, valid=valid, verts=aux["verts"], x=aux["x"], err=tr[:, -1], status=aux["status"],
                         frozen=(tr[:, 1:] == tr[:, :-1]).sum(1))
 
@@ -634,8 +683,8 @@ def main():
                 for p in bs:
                     step(p)
                 return
-            for meshes, markers, valid, info in pipe.run(iter(bs)):
-                pass
+            for res in pipe.run(iter(bs)):
+                final["result"] = res
 
     for _ in range(a.warmup):
         step()
@@ -652,6 +701,8 @@ def main():
     sync()
     P.barrier()
     dt = P.max_over_ranks(time.perf_counter() - t0, device)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(host_arrays(final["result"]), a.dump_outputs)
     if os.environ.get("ETCH_PIPE_TIMING") == "1" and device.type == "cuda":
         print("timed region: allocator segments allocated %d, gc collections per generation %s" % (
             torch.cuda.memory_stats().get("segment.all.allocated", 0) - seg0, [g["collections"] - c for g, c in zip(gc.get_stats(), gc0)]), file=sys.stderr)
@@ -731,7 +782,7 @@ def main():
     sched = ("serial: synchronous steps, one stream" if a.serial else "synchronous steps") if not a.pipeline else \
         (f"stream pipeline, {in_flight} batches in flight: stage 2 of step i overlaps stage 1 of step i+1, the host enqueues two steps ahead"
          if sched_report.get("schedule") != "graph" else
-         f"graph-replay pipeline, {in_flight} batches in flight: every batch's device work (stage 1 with its side streams, glue, marker fit, LBS) is one HIP graph per "
+         f"graph-replay pipeline, {in_flight} batches in flight: every batch's device work (stage 1, glue, marker fit, LBS: one stream) is one HIP graph per "
          "slot, replayed with one host call; stage 2 of step i overlaps stage 1 of step i+1") + \
         (f"; --schedule {a.schedule}" if a.schedule != "eager" else "")
     metric = "scans/s (5k pts, eq-net forward only)" if a.forward_only else "scans/s (5k pts, eq-net + 50-iter SMPL fit)"

@@ -1,5 +1,6 @@
 """ctypes loader of libetch_hip.so.  The product path has NO fallback: if the HIP library is
 missing or a symbol is absent this raises, loudly."""
+import contextlib
 import ctypes
 import os
 import re
@@ -52,22 +53,43 @@ class _Proxy:
         return lambda *a: prof(name, a, fn)
 
 
+def _load(path, how):
+    if not os.path.exists(path):
+        raise EtchHipError(f"{path} is missing: build it with {how} (hipcc, gfx950). etch_amd has no CPU fallback.")
+    cdll = ctypes.CDLL(path)
+    for name in declared_symbols(experiments=hasattr(cdll, "etch_pt_block_k1")):
+        fn = getattr(cdll, name)  # AttributeError if the library does not export a declared symbol
+        fn.restype = ctypes.c_int
+    cdll.etch_smpl_lm_split_workspace_bytes.restype = ctypes.c_long
+    for name in declared_launchers():
+        getattr(cdll, name).restype = None
+    return _Proxy(cdll)
+
+
 def lib():
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise EtchHipError(
-                f"{LIB_PATH} is missing: build it with `python -m etch_amd.build` (hipcc, gfx950). "
-                "etch_amd has no CPU fallback.")
-        cdll = ctypes.CDLL(LIB_PATH)
-        for name in declared_symbols(experiments=hasattr(cdll, "etch_pt_block_k1")):
-            fn = getattr(cdll, name)  # AttributeError if the library does not export a declared symbol
-            fn.restype = ctypes.c_int
-        cdll.etch_smpl_lm_split_workspace_bytes.restype = ctypes.c_long
-        for name in declared_launchers():
-            getattr(cdll, name).restype = None
-        _lib = _Proxy(cdll)
+        _lib = _load(LIB_PATH, "`python -m etch_amd.build`")
     return _lib
+
+
+EXP_LIB_PATH = os.path.join(_HERE, "lib", "libetch_hip_exp.so")
+_exp_lib = None
+
+
+@contextlib.contextmanager
+def experiments_library():
+    """Tests of the opt-in experiment kernels (measured slower than the default path, absent from the product library): every call of etch_amd
+    goes through libetch_hip_exp.so (etch_amd.build.build_experiments(), run by build()) inside the block, through the product library again after it."""
+    global _lib, _exp_lib
+    if _exp_lib is None:
+        _exp_lib = _load(EXP_LIB_PATH, "`etch_amd.build.build_experiments()`")
+    prev = lib()
+    _lib = _exp_lib
+    try:
+        yield _exp_lib
+    finally:
+        _lib = prev
 
 
 def check(status, what):

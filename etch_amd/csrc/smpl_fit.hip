@@ -1297,6 +1297,12 @@ __global__ void __launch_bounds__(256) inner_points_kernel(long n, const float* 
     }
 }
 
+// the split fit's arrival counters (one 256-byte line per scan) cleared before every fit.  A kernel and not hipMemsetAsync: replayed from a
+// captured HIP graph (etch_amd/graph.py), the fit behind a memset node found its counters not cleared and gave every scan up (NaN rows)
+__global__ void __launch_bounds__(256) zero_words_kernel(long n, unsigned* __restrict__ p) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) p[i] = 0u;
+}
+
 // ---------------------------------------------------------------------------------------------- host side
 typedef Body<24, 10, 768> BodySMPL;       // the reference's model (fit_SMPL.py:100)
 typedef Body<55, 20, 512> BodySMPLX;      // SMPL-X-sized: 55 joints, 10 shape + 10 expression coefficients (BASELINE configs[4])
@@ -1329,8 +1335,9 @@ static int launch_lm_fit(int B, int M, const void* const* consts, const float* m
         if (!workspace || (long)B * G > etch_cu_count()) return ETCH_EUNSUPPORTED;
         ctr = reinterpret_cast<unsigned*>(workspace);
         ws = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(workspace) + (size_t)B * 256);
-        e = hipMemsetAsync(workspace, 0, (size_t)B * 256, st);
-        if (e != hipSuccess) return (int)e;
+        const long words = (long)B * 64;
+        hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, words, ctr);
+        ETCH_RETURN_IF_LAUNCH_FAILED();
     }
     hipLaunchKernelGGL(smpl_lm_fit_kernel<BM>, dim3(B * G), dim3(BM::THREADS), lds, st, lm_consts(consts), M, markers, valid, it0, step0, damp0, it1,
                        step1, damp1, x_out, x_stage0, err_trace, phase_ticks, G, ws, reinterpret_cast<unsigned*>(ctr ? ctr : nullptr), g_lm_spin_limit,

@@ -205,7 +205,7 @@ class HotPathPipeline:
 
 class GraphPipeline:
     """The same schedule -- `max_in_flight` batches on the device at once, stage 2 of a batch next to stage 1 of the next -- with the device work of a batch
-    recorded ONCE per slot as a HIP graph (etch_amd.graph.GraphedHotPath: stage 1 with its side streams as branches, labels / inner points, marker fit,
+    recorded ONCE per slot as a HIP graph (etch_amd.graph.GraphedHotPath: stage 1 on one stream, labels / inner points, marker fit,
     final LBS) and replayed with one host call.  Why: the eager pipeline needs ~430 launches = ~7 ms of Python per 33 ms step, and on a host whose cores
     are busy with other tenants those 7 ms become 20 - 60 ms -- the enqueueing thread, not the GPU, then sets the rate (640 - 860 instead of
     900+ scans/s).  A replay costs the host the runtime's own submission of the recorded nodes (C++, ~1 ms) and nothing else.  OPT-IN: on a quiet host

@@ -22,10 +22,13 @@ def dev(a):
                                        (24000, 150, (0.14, 0.31, 0.085))])
 @pytest.mark.parametrize("split", [None, 2, 4, 8])        # None: the dispatch's own choice; G: every scan forced over G workgroups
 def test_fps_vgtk(n, m, sigma, split):
-    from etch_amd import ops
-    if split is not None and n > 8 * 1024 * split:
-        pytest.skip("more than 8 chunks of 1024 points per workgroup: not a split shape")
+    from etch_amd import _lib, ops
     x = np.stack([scan(1000 + b, n, sigma).T for b in range(3)])
+    if split is not None and n > 8 * 1024 * split:
+        # more than 8 chunks of 1024 points per workgroup: not a split shape -- refused as such, nothing sampled
+        with pytest.raises(_lib.EtchHipError, match="unsupported size"):
+            ops.furthest_point_sampling(dev(x), m, split=split)
+        return
     idx = ops.furthest_point_sampling(dev(x), m, split=split)
     got = idx.cpu().numpy()
     assert np.array_equal(got, O.furthest_point_sampling(x, m))
@@ -113,12 +116,15 @@ def test_knn_exact_ties_follow_heap_order():
                                          ([150, 90], 4), ([4999, 130, 2047], 3), ([20000, 20000], 4), ([11000, 300, 20480], 4)])
 @pytest.mark.parametrize("split", [None, 2, 4, 8])
 def test_fps_pointops(segs, stride, split):
-    from etch_amd import ops
-    if split is not None and max(segs) > 8 * 1024 * split:
-        pytest.skip("more than 8 chunks of 1024 points per workgroup: not a split shape")
+    from etch_amd import _lib, ops
     p = np.concatenate([scan(5000 + i, n) for i, n in enumerate(segs)])
     o = np.cumsum(segs).astype(np.int32)
     no = np.cumsum([n // stride for n in segs]).astype(np.int32)
+    if split is not None and max(segs) > 8 * 1024 * split:
+        # more than 8 chunks of 1024 points per workgroup: not a split shape -- refused as such, nothing sampled
+        with pytest.raises(_lib.EtchHipError, match="unsupported size"):
+            ops.furthestsampling(dev(p), dev(o), dev(no), split=split)
+        return
     got = ops.furthestsampling(dev(p), dev(o), dev(no), split=split).cpu().numpy()
     assert np.array_equal(got, O.furthestsampling(p, o, no))
 

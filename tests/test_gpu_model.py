@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from etch_amd.utils.weights import load_seeded, seeded_tensor
+from tests.test_gpu_encoder import experiments  # noqa: F401  (fixture: the experiment kernels' library)
 
 pytestmark = pytest.mark.gpu
 RTOL = 1e-4
@@ -159,13 +160,10 @@ def test_pt_attention_mfma_kernel_matches_split_and_valu(c, ns, n):
 
 
 @pytest.mark.parametrize("c,ns,n,nblocks", [(64, 8, 1003, 1), (128, 8, 517, 2), (128, 16, 1001, 3), (256, 16, 333, 5), (512, 16, 97, 2), (256, 16, 16, 1)])
-def test_fused_block_kernels_match_the_four_kernel_blocks(c, ns, n, nblocks):
+def test_fused_block_kernels_match_the_four_kernel_blocks(c, ns, n, nblocks, experiments):
     """run_blocks (etch_pt_block_k1 / _k2: linear1+bn1+ReLU+q|k|v, then attention+bn2+ReLU+linear3+bn3+residual+ReLU, consecutive blocks
     chained) against the blocks' own four-kernel forward (which the reference golden pins at c = 32): every instantiated (c, nsample),
     runs of 1-5 blocks, point counts that leave partial 16-point tiles, two segments."""
-    from etch_amd import _lib
-    if not _lib.has_experiments():
-        pytest.skip("opt-in experiment kernel: built only with ETCH_BUILD_EXPERIMENTS=1 (measured slower than the default path)")
     from etch_amd import ops
     from etch_amd.models import pointops
     from etch_amd.models import pointtransformer_seg as P

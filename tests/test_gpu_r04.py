@@ -4,7 +4,7 @@ import pytest
 import torch
 
 from etch_amd.utils.weights import load_seeded
-from tests.test_gpu_encoder import _inter_conv_fp64, rel_err
+from tests.test_gpu_encoder import _inter_conv_fp64, experiments, rel_err  # noqa: F401  (experiments: fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -31,15 +31,13 @@ def test_split3_planes_are_exact_and_match_the_host_split():
 @pytest.mark.parametrize("form", [32, 16])
 @pytest.mark.parametrize("cin,cout,nn,p1,p2", [(32, 32, 32, 301, 149), (32, 64, 64, 211, 60), (64, 64, 32, 211, 101), (32, 32, 64, 130, 1),
                                                 (32, 64, 32, 97, 97), (64, 64, 64, 150, 33)])
-def test_inter_conv_planes_matches_the_fp32_kernel_and_fp64(cin, cout, nn, p1, p2, form):
+def test_inter_conv_planes_matches_the_fp32_kernel_and_fp64(cin, cout, nn, p1, p2, form, experiments):
     """etch_inter_so3conv_planes32 / etch_inter_so3conv_planes (32x32x16 / 16x16x32 MFMA form; BOTH contractions on the bf16 matrix cores: fp32 operands split exactly into three bf16 values, six cross
     products each; gathered rows as producer-written planes through LDS-direct loads + transposing LDS reads) against the fp32-MFMA kernel
     (the same sums in another order) and the fp64 formula under the entitled-error rule; bitwise reproducible, schedule-independent;
     padded neighbourhoods (radius smaller than the cloud: cyclic padding) included."""
-    from etch_amd import _lib, ops
+    from etch_amd import ops
     from etch_amd import vgtk_so3conv as V
-    if not _lib.has_experiments():
-        pytest.skip("the round-4 planes kernels are built only with ETCH_BUILD_EXPERIMENTS=1 since round 6 (VERDICT r05 item 9)")
     assert ops.inter_planes_supported(cin, cout, nn)
     g = torch.Generator().manual_seed(cin + nn + p2)
     b = 2
@@ -49,7 +47,9 @@ def test_inter_conv_planes_matches_the_fp32_kernel_and_fp64(cin, cout, nn, p1, p
     conv = load_seeded(V.InterSO3Conv(cin, cout, 1, 2, 0.25, 0.03, nn), 3).cuda()
     rk, W, Wp, bias = conv._derived()
     if form == 32 and cin != 64:
-        pytest.skip("the 32x32x16 form is instantiated for 64 input channels only")
+        # the 32x32x16 form is instantiated for 64 input channels only: this width takes the 16x16x32 form, and no operand of the other is made
+        assert ops.inter_planes_form(cin) == 16 and conv._wq32() is None and conv._wqn() is not None
+        return
     wkw = dict(Wq32=conv._wq32()) if form == 32 else dict(Wqn=conv._wqn())
     assert all(v is not None for v in wkw.values())
     feats = torch.randn(b, p1, 60, cin, generator=g).cuda()

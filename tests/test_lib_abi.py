@@ -53,8 +53,8 @@ REFERENCE_LAUNCHERS = {
 
 def test_reference_launcher_symbols_and_prototypes():
     """The reference's own extern "C" launchers are exported under their names with their exact prototypes (so knnquery_cuda.cpp /
-    sampling_cuda.cpp link against libetch_hip.so unchanged); where /root/reference is present the prototypes are also read from
-    its headers."""
+    sampling_cuda.cpp link against libetch_hip.so unchanged).  The reference headers' prototypes are stored above (REFERENCE_LAUNCHERS,
+    with the header lines they come from)."""
     import re
     B.build()
     names = _lib.declared_launchers()
@@ -66,9 +66,4 @@ def test_reference_launcher_symbols_and_prototypes():
     for name, proto in REFERENCE_LAUNCHERS.items():
         mine = re.search(r"void\s+" + name + r"\s*\([^)]*\)\s*;", hdr).group(0)
         assert _norm(mine) == _norm(proto), (mine, proto)
-    ref = "/root/reference/external/pointops/src"
-    if os.path.isdir(ref):
-        for name, rel in (("knnquery_cuda_launcher", "knnquery/knnquery_cuda_kernel.h"), ("furthestsampling_cuda_launcher", "sampling/sampling_cuda_kernel.h")):
-            theirs = re.search(r"void\s+" + name + r"\s*\([^)]*\)\s*;", open(os.path.join(ref, rel)).read()).group(0)
-            assert _norm(theirs) == _norm(REFERENCE_LAUNCHERS[name])
     assert "etch_knnquery_dev" in _lib.declared_symbols()
