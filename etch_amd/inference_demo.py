@@ -79,7 +79,7 @@ def predict_smpl(args, model, points, gender="neutral"):
     return meshes[0], info
 
 
-def main(argv=None):
+def parse_args(argv=None):
     parser = argparse.ArgumentParser()
     parser.add_argument("--scan_path", type=str, required=True, help="Path to input scan OBJ file")
     parser.add_argument("--gender", type=str, default="neutral", choices=["neutral", "male", "female"])
@@ -94,7 +94,38 @@ def main(argv=None):
     parser.add_argument("--body_model", type=str, default="", help="chumpy-free SMPL .pkl (else the reference's gender paths)")
     parser.add_argument("--synthetic_body", action="store_true", help="use the seeded SMPL-shaped stand-in body model")
     parser.add_argument("--seed", type=int, default=0, help="surface-sampling seed (the reference is unseeded)")
-    args = parser.parse_args(argv)
+    parser.add_argument("--chamfer_refine", type=str, default="none", choices=["none", "both", "partial", "clutter"],
+                        help="after the marker fit, refine the body against the centred scan's vertices (chamfer_refine.py:fit_cham): "
+                             "both directions, scan -> body only (partial scans) or body -> scan only (cluttered scans)")
+    parser.add_argument("--refine_iters", type=int, default=500, help="Adam iterations of --chamfer_refine")
+    return parser.parse_args(argv)
+
+
+def _refine_and_save(args, model, points, centered_mesh, original_center, scan_name):
+    """--chamfer_refine: the marker fit, then fit_cham against the centred scan's vertices (the script's `vertices_scan`).  The OBJ is the
+    refined mesh moved back by the scan centre; the .npz holds the refined parameters, `scale`, and the joints in the centred scan's
+    frame ((joints + trans) * scale, the frame the LM joints of an unrefined run are written in)."""
+    from .models.chamfer_refine import fit_cham, init_from_fit
+    from .models.fit_SMPL import _resolve_body_model
+
+    points_tensor = torch.from_numpy(points).float().unsqueeze(0).to(args.device)
+    meshes, _, _, _, dev = predict_smpl_batch(args, model, points_tensor, args.gender, return_trace=True)
+    bm = _resolve_body_model(args, args.gender)
+    scan = torch.from_numpy(np.asarray(centered_mesh.vertices, np.float32)).unsqueeze(0).to(args.device)
+    verts, prm = fit_cham(bm, scan, init_from_fit(dev), prior=None, bidir=args.chamfer_refine, iterations=args.refine_iters)
+    final = Mesh(verts[0] + original_center, meshes[0].faces)
+    final.export(os.path.join(args.output_folder, f"{scan_name}_pred_smpl.obj"))
+    pose = prm["pose"][0].cpu().numpy()
+    body = pose[3:].reshape(-1, 3)
+    scale = prm["scale"][0].cpu().numpy()
+    trans = prm["trans"][0].cpu().numpy()
+    joints = (prm["joints"][0].cpu().numpy() + trans) * scale
+    np.savez(os.path.join(args.output_folder, f"{scan_name}_output_smpl_info.npz"), body_pose=body[:21], hand_pose=body[21:23],
+             betas=prm["beta"][0].cpu().numpy(), global_orient=pose[:3], transl=trans, scale=scale, joints=joints)
+
+
+def main(argv=None):
+    args = parse_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError("etch_amd needs an AMD GPU (gfx950); there is no CPU path")
     args.cuda = True
@@ -118,10 +149,14 @@ def main(argv=None):
     model = load_model(args)
     centered_mesh, original_center = preprocess_scan(args.scan_path)
     points = sample_points_from_mesh(centered_mesh, args.num_point, args.seed)
+    scan_name = os.path.splitext(os.path.basename(args.scan_path))[0]
+    if args.chamfer_refine != "none":
+        _refine_and_save(args, model, points, centered_mesh, original_center, scan_name)
+        print(f"Predicted SMPL mesh and smpl info saved under {args.output_folder}")
+        return
     pred_smpl_mesh, smpl_info = predict_smpl(args, model, points, args.gender)
     final = pred_smpl_mesh.copy()
     final.vertices = pred_smpl_mesh.vertices + original_center
-    scan_name = os.path.splitext(os.path.basename(args.scan_path))[0]
     final.export(os.path.join(args.output_folder, f"{scan_name}_pred_smpl.obj"))
     np.savez(os.path.join(args.output_folder, f"{scan_name}_output_smpl_info.npz"), body_pose=smpl_info[0][0, :21, :],
              hand_pose=smpl_info[0][0, 21:23, :], betas=smpl_info[1][0], global_orient=smpl_info[2][0], transl=smpl_info[3][0],

@@ -1111,3 +1111,116 @@ def inner_points(points, direction, magnitude, scale):
     _lib.check(_lib.lib().etch_inner_points(_c_long(n), _ptr(points), _ptr(direction), _ptr(magnitude), _c_float(scale), _ptr(out), _stream()),
                "etch_inner_points")
     return out
+
+
+# ------------------------------------------------------------------ chamfer refinement (csrc/chamfer_fit.hip)
+def _lengths(len_t, B, n, device, name):
+    if len_t is None:
+        return None
+    t = torch.as_tensor(len_t, device=device).to(torch.int32).contiguous()
+    if t.shape != (B,):
+        raise _lib.EtchHipError(f"{name} must have shape ({B},), got {tuple(t.shape)}")
+    return t
+
+
+def nn_bidir(x, y, x_lengths=None, y_lengths=None):
+    """Exact nearest neighbours both ways: x (B,N,3), y (B,V,3) fp32 -> idx_xy (B,N) int32, d_xy (B,N), idx_yx (B,V) int32, d_yx (B,V).
+    d = the bit-defined fp32 ((dx*dx)+(dy*dy))+(dz*dz) of the returned pair; exact ties -> the lowest index; padding -> index -1, distance 0."""
+    _need(x, torch.float32, "x"), _need(y, torch.float32, "y")
+    if x.dim() != 3 or y.dim() != 3 or y.shape[0] != x.shape[0] or x.shape[2] != 3 or y.shape[2] != 3:
+        raise _lib.EtchHipError(f"x and y must be (B,N,3) and (B,V,3), got {tuple(x.shape)} and {tuple(y.shape)}")
+    B, N, _ = x.shape
+    V = y.shape[1]
+    xl, yl = _lengths(x_lengths, B, N, x.device, "x_lengths"), _lengths(y_lengths, B, V, x.device, "y_lengths")
+    ws = torch.empty((max(B * (N + V), 1),), dtype=torch.int64, device=x.device)
+    ixy = torch.empty((B, N), dtype=torch.int32, device=x.device)
+    dxy = torch.empty((B, N), dtype=torch.float32, device=x.device)
+    iyx = torch.empty((B, V), dtype=torch.int32, device=x.device)
+    dyx = torch.empty((B, V), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().etch_nn_bidir(B, N, V, _ptr(x), _ptr(y), _optptr(xl), _optptr(yl), _ptr(ws), _ptr(ixy), _ptr(dxy), _ptr(iyx), _ptr(dyx),
+                                        _stream()), "etch_nn_bidir")
+    return ixy, dxy, iyx, dyx
+
+
+def chamfer_grad(x, y, idx_xy, idx_yx, w_xy=None, w_yx=None, x_lengths=None, y_lengths=None, want_x=True, want_y=True):
+    """Gradient of sum_b [w_xy[b] sum_i d_xy + w_yx[b] sum_j d_yx] (neighbours held fixed) -> (gx (B,N,3) or None, gy (B,V,3) or None)."""
+    _need(x, torch.float32, "x"), _need(y, torch.float32, "y")
+    if x.dim() != 3 or y.dim() != 3 or y.shape[0] != x.shape[0] or x.shape[2] != 3 or y.shape[2] != 3:
+        raise _lib.EtchHipError("chamfer_grad: x (B,N,3), y (B,V,3), idx_xy (B,N), idx_yx (B,V)")
+    B, N, _ = x.shape
+    V = y.shape[1]
+    if tuple(idx_xy.shape) != (B, N) or tuple(idx_yx.shape) != (B, V):
+        raise _lib.EtchHipError("chamfer_grad: x (B,N,3), y (B,V,3), idx_xy (B,N), idx_yx (B,V)")
+    for w, n in ((w_xy, "w_xy"), (w_yx, "w_yx")):
+        if w is not None and tuple(w.shape) != (B,):
+            raise _lib.EtchHipError(f"{n} must be ({B},)")
+    xl, yl = _lengths(x_lengths, B, N, x.device, "x_lengths"), _lengths(y_lengths, B, V, x.device, "y_lengths")
+    w_xy = None if w_xy is None else _need(w_xy.to(torch.float32).contiguous(), torch.float32, "w_xy")
+    w_yx = None if w_yx is None else _need(w_yx.to(torch.float32).contiguous(), torch.float32, "w_yx")
+    ws = torch.empty((max(3 * B * (N + V), 1),), dtype=torch.int64, device=x.device)
+    gx = torch.empty_like(x) if want_x else None
+    gy = torch.empty_like(y) if want_y else None
+    _lib.check(_lib.lib().etch_chamfer_grad(B, N, V, _ptr(x), _ptr(y), _optptr(xl), _optptr(yl), _ptr(_need(idx_xy, torch.int32, "idx_xy")),
+                                            _ptr(_need(idx_yx, torch.int32, "idx_yx")), _optptr(w_xy), _optptr(w_yx), _ptr(ws), _optptr(gx),
+                                            _optptr(gy), _stream()), "etch_chamfer_grad")
+    return gx, gy
+
+
+def _check_body(consts, nj, nb, n_extra):
+    """The 8 LBS tables (v_template, shapedirs, posedirs, weights, J0, Jd, parents, extra_vids) must match (nj, nb, n_extra)."""
+    if len(consts) != 8 or tuple(consts[1].shape[1:]) != (3, nb) or tuple(consts[4].shape) != (nj, 3) or consts[7].numel() != n_extra:
+        raise _lib.EtchHipError(f"body tables do not match nj={nj}, nb={nb}, n_extra={n_extra}")
+
+
+def _refine_workspace(B, N, V, nj, nb, n_extra, device):
+    n = ctypes.c_longlong(0)
+    _lib.check(_lib.lib().etch_smpl_chamfer_refine_workspace(B, N, V, int(nj), int(nb), int(n_extra), ctypes.byref(n)),
+               "etch_smpl_chamfer_refine_workspace")
+    return torch.empty((max(int(n.value), 8),), dtype=torch.uint8, device=device)
+
+
+def smpl_lbs_vjp(consts, params, g, nj=24, nb=10, n_extra=21):
+    """params (B, 3 nj + nb + 4) = pose (global orient first) | beta | trans | scale; g (B,V,3) = dL/dverts of
+    verts = (LBS(pose, beta) + trans) * scale  ->  dL/dparams (B, 3 nj + nb + 4)."""
+    _need(params, torch.float32, "params"), _need(g, torch.float32, "g")
+    _check_body(consts, nj, nb, n_extra)
+    if g.dim() != 3 or g.shape[2] != 3 or g.shape[1] != consts[0].shape[0] or tuple(params.shape) != (g.shape[0], 3 * nj + nb + 4):
+        raise _lib.EtchHipError(f"params must be (B, {3 * nj + nb + 4}) and g (B, {consts[0].shape[0]}, 3)")
+    B, V = g.shape[0], g.shape[1]
+    arr = (ctypes.c_void_p * 8)(*[t.data_ptr() for t in consts])
+    ws = _refine_workspace(B, 0, V, nj, nb, n_extra, g.device)
+    grad = torch.empty_like(params)
+    _lib.check(_lib.lib().etch_smpl_lbs_vjp(B, V, int(nj), int(nb), int(n_extra), arr, _ptr(params), _ptr(g), _ptr(ws), _ptr(grad), _stream()),
+               "etch_smpl_lbs_vjp")
+    return grad
+
+
+def smpl_chamfer_refine(consts, scan, params, V, scan_lengths=None, prior=None, bidir=0, iters=500, lr=2e-2, beta1=0.9, beta2=0.999, eps=1e-8,
+                        nj=24, nb=10, n_extra=21, want_trace=False):
+    """fit_cham on the device: params (B, 3 nj + nb + 4) is updated IN PLACE.  prior = None or (means (G,69), precisions (G,69,69),
+    nll_weights (G)) fp32 device tensors.  -> verts (B,V,3), joints (B, nj + n_extra, 3) (without trans / scale), loss of the last forward (B,),
+    loss trace (B, iters) or None."""
+    _need(scan, torch.float32, "scan"), _need(params, torch.float32, "params")
+    _check_body(consts, nj, nb, n_extra)
+    if scan.dim() != 3 or scan.shape[2] != 3 or tuple(params.shape) != (scan.shape[0], 3 * nj + nb + 4) or int(V) != consts[0].shape[0]:
+        raise _lib.EtchHipError(f"scan must be (B,N,3), params (B, {3 * nj + nb + 4}), V = the model's {consts[0].shape[0]} vertices")
+    B, N, _ = scan.shape
+    sl = _lengths(scan_lengths, B, N, scan.device, "scan_lengths")
+    arr = (ctypes.c_void_p * 8)(*[t.data_ptr() for t in consts])
+    G, parr = 0, None
+    if prior is not None:
+        means, prec, w = (_need(t, torch.float32, n) for t, n in zip(prior, ("means", "precisions", "nll_weights")))
+        G = int(w.shape[0])
+        if tuple(w.shape) != (G,) or tuple(means.shape) != (G, 69) or tuple(prec.shape) != (G, 69, 69):
+            raise _lib.EtchHipError("prior: means (G,69), precisions (G,69,69), nll_weights (G,)")
+        parr = (ctypes.c_void_p * 3)(means.data_ptr(), prec.data_ptr(), w.data_ptr())
+    ws = _refine_workspace(B, N, V, nj, nb, n_extra, scan.device)
+    verts = torch.empty((B, V, 3), dtype=torch.float32, device=scan.device)
+    joints = torch.empty((B, nj + n_extra, 3), dtype=torch.float32, device=scan.device)
+    loss = torch.empty((B,), dtype=torch.float32, device=scan.device)
+    tr = torch.empty((B, iters), dtype=torch.float32, device=scan.device) if want_trace else None
+    _lib.check(_lib.lib().etch_smpl_chamfer_refine(B, N, int(V), int(nj), int(nb), int(n_extra), arr, _ptr(scan), _optptr(sl), parr, G, int(bidir),
+                                                   int(iters), _c_float(lr), _c_float(beta1), _c_float(beta2), _c_float(eps), _ptr(params),
+                                                   _ptr(verts), _ptr(joints), _optptr(tr), _ptr(loss), _ptr(ws), _stream()),
+               "etch_smpl_chamfer_refine")
+    return verts, joints, loss, tr

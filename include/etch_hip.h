@@ -640,6 +640,37 @@ int etch_rodrigues(int n, const float* theta, double* R, float* dR, void* stream
  * (V,3,nb), posedirs (9 (nj-1), V*3), lbs_weights (V,nj), J0, Jd, parents, extra_vids (n_extra) i32}.  nj <= 55, nb <= 20. */
 int etch_smpl_lbs(int B, int V, int nj, int nb, int n_extra, const void* const* consts, const float* x, float* verts, float* joints, void* stream);
 
+/* ---- chamfer refinement of the fit against the scan (scripts/experiment_scripts/chamfer_refine.py:fit_cham) --------------------- */
+
+/* Exact brute-force nearest neighbours between X (B,N,3) and Y (B,V,3), both directions in one pass over the pair tiles.
+ * x_len / y_len (B) int32 or NULL: points at or past a scan's length are never chosen and change nothing.  Outputs: idx_xy (B,N) int32 =
+ * the Y index nearest to each X point, d_xy (B,N) its squared distance; idx_yx / d_yx (B,V) the same towards X.  The distance is the
+ * bit-defined fp32 ((dx*dx)+(dy*dy))+(dz*dz) of the returned pair; among exactly equal distances the LOWEST index wins.  Padding rows
+ * get index -1 and distance 0.  workspace: B (N + V) * 8 bytes, contents arbitrary. */
+int etch_nn_bidir(int B, int N, int V, const float* X, const float* Y, const int* x_len, const int* y_len, void* workspace, int* idx_xy, float* d_xy,
+                  int* idx_yx, float* d_yx, void* stream);
+/* Gradient of L = sum_b [w_xy[b] sum_i d_xy(b,i) + w_yx[b] sum_j d_yx(b,j)] with the neighbours of etch_nn_bidir held fixed:
+ * gx (B,N,3), gy (B,V,3) (either may be NULL; padding rows get 0).  w_xy / w_yx (B) or NULL (direction absent).  Deterministic: the
+ * neighbour-side scatter sums fixed-point differences with integer atomics.  workspace: B (N + V) * 24 bytes, contents arbitrary. */
+int etch_chamfer_grad(int B, int N, int V, const float* X, const float* Y, const int* x_len, const int* y_len, const int* idx_xy, const int* idx_yx,
+                      const float* w_xy, const float* w_yx, void* workspace, float* gx, float* gy, void* stream);
+/* Workspace bytes of etch_smpl_chamfer_refine (N scan points) and of etch_smpl_lbs_vjp (N = 0); (nj, nb) in {(24, 10), (55, 20)}. */
+int etch_smpl_chamfer_refine_workspace(int B, int N, int V, int nj, int nb, int n_extra, long long* bytes);
+/* Reverse mode of verts = (LBS(pose, beta) + trans) * scale over the full mesh.  params (B, P = 3 nj + nb + 4) = pose[3 nj] (global
+ * orient first) | beta[nb] | trans[3] | scale; g (B,V,3) = dL/dverts -> grad (B,P) = dL/dparams.  consts as etch_smpl_lbs. */
+int etch_smpl_lbs_vjp(int B, int V, int nj, int nb, int n_extra, const void* const* consts, const float* params, const float* g, void* workspace, float* grad,
+                      void* stream);
+/* fit_cham: `iters` torch.optim.Adam steps (beta1, beta2, eps; no weight decay) on params (B,P, updated in place) of the per-scan loss
+ * data + 1e-8 prior(pose[3:]) + 0.2 mean(beta^2), data = sqrt(S1) + sqrt(S2) (bidir 0), sqrt(S1) (1: scan -> body only) or sqrt(S2)
+ * (-1: body -> scan only), S1 = sum over the scan (B,N,3; scan_len or NULL) of the squared distance to the nearest vertex, S2 = sum over
+ * the vertices of the squared distance to the nearest scan point.  Step i runs at lr for i = 0 and lr (iters - i + 1) / iters after.
+ * prior: NULL (n_gauss 0) or {means (G,69), precisions (G,69,69), nll_weights (G)} of the max-mixture GMM, SMPL (nj 24) only.
+ * Outputs: verts (B,V,3) of the final params, joints (B, nj + n_extra, 3) of the final params without trans and scale, loss_last (B) =
+ * the loss of the last forward, loss_trace (B, iters) or NULL.  Everything is queued on `stream` without a host wait (capturable). */
+int etch_smpl_chamfer_refine(int B, int N, int V, int nj, int nb, int n_extra, const void* const* consts, const float* scan, const int* scan_len,
+                             const void* const* prior, int n_gauss, int bidir, int iters, float lr, float beta1, float beta2, float eps, float* params,
+                             float* verts, float* joints, float* loss_trace, float* loss_last, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
