@@ -1224,3 +1224,102 @@ def smpl_chamfer_refine(consts, scan, params, V, scan_lengths=None, prior=None, 
                                                    _ptr(verts), _ptr(joints), _optptr(tr), _ptr(loss), _ptr(ws), _stream()),
                "etch_smpl_chamfer_refine")
     return verts, joints, loss, tr
+
+
+# ------------------------------------------------------------------ tightness supervision (csrc/raycast.hip)
+def _check_mesh(verts, faces):
+    """verts (V,3) fp64, faces (F,3) int32 on the device with every index in [0, V): the kernels read vertices through the face indices."""
+    _need(verts, torch.float64, "verts"), _need(faces, torch.int32, "faces")
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise _lib.EtchHipError(f"mesh must be verts (V,3) and faces (F,3), got {tuple(verts.shape)} and {tuple(faces.shape)}")
+    if faces.numel():
+        lo, hi = (int(v) for v in torch.aminmax(faces))
+        if lo < 0 or hi >= verts.shape[0]:
+            raise _lib.EtchHipError(f"face indices must lie in [0, {verts.shape[0]}), got [{lo}, {hi}]")
+    return verts.shape[0], faces.shape[0]
+
+
+def _mesh_workspace(fn, n, F, device):
+    b = ctypes.c_longlong(0)
+    _lib.check(fn(int(n), int(F), ctypes.byref(b)), "workspace query")
+    return torch.empty((max(int(b.value), 8),), dtype=torch.uint8, device=device)
+
+
+def ray_first_hit(origins, dirs, verts, faces, excl_face=None, t_max=None):
+    """First hit of rays (R,3) fp64 on a mesh (Moller-Trumbore in fp64, csrc/raycast.hip) -> face (R) int32 (-1 = miss), t (R) fp64 (+inf on a
+    miss), bary (R,3) = (1 - u - v, u, v), loc (R,3) = o + t d.  excl_face (R) int32: a face each ray skips (-1 = none); t_max (R) fp64: a hit
+    needs t < t_max.  The smallest t wins, equal t -> the lowest face."""
+    _need(origins, torch.float64, "origins"), _need(dirs, torch.float64, "dirs")
+    if origins.dim() != 2 or origins.shape[1] != 3 or dirs.shape != origins.shape:
+        raise _lib.EtchHipError(f"origins and dirs must both be (R,3), got {tuple(origins.shape)} and {tuple(dirs.shape)}")
+    R = origins.shape[0]
+    _, F = _check_mesh(verts, faces)
+    if excl_face is not None and (_need(excl_face, torch.int32, "excl_face").shape != (R,)):
+        raise _lib.EtchHipError(f"excl_face must be ({R},)")
+    if t_max is not None and (_need(t_max, torch.float64, "t_max").shape != (R,)):
+        raise _lib.EtchHipError(f"t_max must be ({R},)")
+    dev = origins.device
+    ws = _mesh_workspace(_lib.lib().etch_ray_first_hit_workspace, R, F, dev)
+    face = torch.empty((R,), dtype=torch.int32, device=dev)
+    t = torch.empty((R,), dtype=torch.float64, device=dev)
+    bary = torch.empty((R, 3), dtype=torch.float64, device=dev)
+    loc = torch.empty((R, 3), dtype=torch.float64, device=dev)
+    _lib.check(_lib.lib().etch_ray_first_hit(R, F, _ptr(origins), _ptr(dirs), _ptr(verts), _ptr(faces), _optptr(excl_face), _optptr(t_max), _ptr(ws),
+                                             _ptr(face), _ptr(t), _ptr(bary), _ptr(loc), _stream()), "etch_ray_first_hit")
+    return face, t, bary, loc
+
+
+def closest_point_on_mesh(points, verts, faces):
+    """Closest point on a mesh of points (P,3) fp64 (Ericson 5.1.5 in fp64, csrc/raycast.hip) -> face (P) int32, bary (P,3), closest (P,3),
+    d2 (P) fp64.  The smallest d2 wins, equal d2 -> the lowest face."""
+    _need(points, torch.float64, "points")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise _lib.EtchHipError(f"points must be (P,3), got {tuple(points.shape)}")
+    P = points.shape[0]
+    _, F = _check_mesh(verts, faces)
+    dev = points.device
+    ws = _mesh_workspace(_lib.lib().etch_closest_point_on_mesh_workspace, P, F, dev)
+    face = torch.empty((P,), dtype=torch.int32, device=dev)
+    bary = torch.empty((P, 3), dtype=torch.float64, device=dev)
+    closest = torch.empty((P, 3), dtype=torch.float64, device=dev)
+    d2 = torch.empty((P,), dtype=torch.float64, device=dev)
+    _lib.check(_lib.lib().etch_closest_point_on_mesh(P, F, _ptr(points), _ptr(verts), _ptr(faces), _ptr(ws), _ptr(face), _ptr(bary), _ptr(closest),
+                                                     _ptr(d2), _stream()), "etch_closest_point_on_mesh")
+    return face, bary, closest, d2
+
+
+def vertex_face_csr(faces_np, num_vertices):
+    """Vertex -> (face, corner) incidence in ascending face order: ptr (V+1), idx (3F) with entries 3 f + corner (host numpy, int32)."""
+    import numpy as np
+
+    flat = np.asarray(faces_np, np.int64).ravel()
+    idx = np.argsort(flat, kind="stable").astype(np.int32)
+    ptr = np.zeros(num_vertices + 1, np.int64)
+    np.cumsum(np.bincount(flat, minlength=num_vertices), out=ptr[1:])
+    return ptr.astype(np.int32), idx
+
+
+def vertex_normals(verts, faces):
+    """trimesh's weighted_vertex_normals (corner-angle weights), summed per vertex in ascending face order -> (V,3) fp64."""
+    V, F = _check_mesh(verts, faces)
+    ptr, idx = vertex_face_csr(faces.cpu().numpy(), V)
+    ptr_d = torch.from_numpy(ptr).to(verts.device)
+    idx_d = torch.from_numpy(idx).to(verts.device)
+    ws = torch.empty((max(6 * F, 1),), dtype=torch.float64, device=verts.device)
+    out = torch.empty((V, 3), dtype=torch.float64, device=verts.device)
+    _lib.check(_lib.lib().etch_vertex_normals(V, F, _ptr(verts), _ptr(faces), _ptr(ptr_d), _ptr(idx_d), _ptr(ws), _ptr(out), _stream()),
+               "etch_vertex_normals")
+    return out
+
+
+def remove_close(points, radius):
+    """trimesh 4.x points.remove_close flags: points (C,3) fp64 -> degree (C) int32, removed (C) bool (squared distance <= radius^2 in fp64)."""
+    _need(points, torch.float64, "points")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise _lib.EtchHipError(f"points must be (C,3), got {tuple(points.shape)}")
+    C = points.shape[0]
+    r = float(radius)
+    deg = torch.empty((C,), dtype=torch.int32, device=points.device)
+    rem = torch.empty((C,), dtype=torch.int32, device=points.device)
+    _lib.check(_lib.lib().etch_remove_close(C, _ptr(points), ctypes.c_double(r * r), _ptr(deg), _ptr(rem), _stream()), "etch_remove_close")
+    return deg, rem.bool()

@@ -671,6 +671,29 @@ int etch_smpl_chamfer_refine(int B, int N, int V, int nj, int nb, int n_extra, c
                              const void* const* prior, int n_gauss, int bidir, int iters, float lr, float beta1, float beta2, float eps, float* params,
                              float* verts, float* joints, float* loss_trace, float* loss_last, void* workspace, void* stream);
 
+/* ---- tightness supervision: info points and vector targets (scripts/generate_infopoints.py, GT_dataloader.py:95-122) ------------- */
+
+/* Workspace bytes of etch_ray_first_hit (R rays) / etch_closest_point_on_mesh (P points) against F faces. */
+int etch_ray_first_hit_workspace(int R, int F, long long* bytes);
+/* First hit of R rays (origins, dirs (R,3) fp64) on a mesh (verts (V,3) fp64, faces (F,3) int32, every index in [0, V)): Moller-Trumbore in
+ * fp64 with the operation order of csrc/raycast.hip; a hit needs det != 0, u >= 0, v >= 0, u + v <= 1, 0 < t < t_max.  excl_face (R) int32
+ * or NULL: a face each ray skips (-1 = none); t_max (R) fp64 or NULL (+inf).  Outputs: face (R) int32 (-1 = miss), t (R) (+inf on a miss),
+ * bary (R,3) = (1 - u - v, u, v) (0 on a miss), loc (R,3) = o + t d or NULL.  The smallest t wins, equal t -> the lowest face. */
+int etch_ray_first_hit(int R, int F, const double* origins, const double* dirs, const double* verts, const int* faces, const int* excl_face,
+                       const double* t_max, void* workspace, int* face, double* t, double* bary, double* loc, void* stream);
+int etch_closest_point_on_mesh_workspace(int P, int F, long long* bytes);
+/* Closest point on the mesh of P points (P,3) fp64: Ericson's region test (Real-Time Collision Detection 5.1.5) with the operation order of
+ * csrc/raycast.hip.  Outputs: face (P) int32, bary (P,3), closest (P,3), d2 (P) fp64; the smallest d2 wins, equal d2 -> the lowest face. */
+int etch_closest_point_on_mesh(int P, int F, const double* points, const double* verts, const int* faces, void* workspace, int* face, double* bary,
+                               double* closest, double* d2, void* stream);
+/* trimesh's angle-weighted vertex normals: per vertex the sum of (unit face normal x corner angle) over csr_idx[csr_ptr[i] .. csr_ptr[i+1])
+ * (entries 3 f + corner, in the order given), normalised.  csr_ptr (V+1), csr_idx (3F) int32; workspace F * 48 bytes; normals (V,3) fp64. */
+int etch_vertex_normals(int V, int F, const double* verts, const int* faces, const int* csr_ptr, const int* csr_idx, void* workspace, double* normals,
+                        void* stream);
+/* trimesh 4.x points.remove_close on C points (C,3) fp64: a close pair is i < j with squared distance <= r2; degree (C) int32 = close pairs
+ * containing each point; removed (C) int32 = 1 where the point is dropped (each pair drops its endpoint of higher degree, i on a tie). */
+int etch_remove_close(int C, const double* points, double r2, int* degree, int* removed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
