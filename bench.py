@@ -16,6 +16,10 @@ Workload (BASELINE.json configs[2], the configuration the metric is quoted on): 
 (weak scaling: every rank processes its own 32 scans; no collective on the data path; one RCCL all_gather of the
 per-scan result rows at the end of the job).  Every step gets its own, distinct batch of scans (all resident in HBM before the
 timed region).  `--forward-only` measures BASELINE.json configs[1] (equivariant forward only) instead.  Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, write --dump-outputs, print the line.  `--full` adds
+every other leg: the single-scan latency (one of it in a child process of its own), the synchronous schedule, the well-posed-marker leg, the
+instrumented roofline pass, the stage-2 latency and the CPU baseline with its parity numbers (with --train: the phase split and the CPU step).
 """
 import argparse
 import collections
@@ -324,8 +328,9 @@ def cpu_baseline(n_points, gpu_pts, gpu_results, gpu_fit_aux, args, seed=1, thre
 def train_bench(a):
     """`bench.py --train`: what train.py:77-124 times per iteration -- forward of GT_network_equiv in train() mode (the differentiable path: hand-written
     backward kernels behind torch.autograd, train-mode BatchNorm), the four losses of train.py:81-101, backward, one torch.optim.Adam step (lr 1e-4,
-    train.py:219) -- on synthetic scans at train.py's batch shape (batch_size x num_point, defaults 1 x 5000; --batch / --points override), next to the
-    oracle's CPU autograd step (oracle/train_step.py, ONE step, bounded).  SURVEY 8 f-3.  Prints one JSON line (not the driver's metric)."""
+    train.py:219) -- on synthetic scans at train.py's batch shape (batch_size x num_point, defaults 1 x 5000; --batch / --points override); with --full
+    also one step with its phases bracketed and the oracle's CPU autograd step (oracle/train_step.py, ONE step, bounded).  SURVEY 8 f-3.  Prints one JSON
+    line (not the driver's metric)."""
     import types
     from etch_amd import constants as K
     from etch_amd.models.models_pointcloud import GT_network_equiv
@@ -369,28 +374,32 @@ def train_bench(a):
         dt = time.perf_counter() - t0
         if a.dump_outputs:
             dump_outputs(host_arrays(loss), a.dump_outputs)
-        # the same step with the phases bracketed (one extra, untimed in `value`)
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-        ev[0].record()
-        res, _ = model(pts, items, "standard_vector")
-        l2 = ((1 - torch.nn.functional.cosine_similarity(vec, res["direction"], dim=-1)).mean() + torch.nn.functional.mse_loss(torch.norm(vec, dim=-1, keepdim=True) * 10, res["magnitude"])
-              + torch.nn.functional.mse_loss(res["confidences"], conf) + torch.nn.functional.cross_entropy(res["part_labels"].permute(0, 2, 1).contiguous(), labels))
-        ev[1].record()
-        opt.zero_grad()
-        l2.backward()
-        ev[2].record()
-        opt.step()
-        ev[3].record()
-        torch.cuda.synchronize()
+        if a.full:
+            # the same step with the phases bracketed (one extra, untimed in `value`)
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            ev[0].record()
+            res, _ = model(pts, items, "standard_vector")
+            l2 = ((1 - torch.nn.functional.cosine_similarity(vec, res["direction"], dim=-1)).mean()
+                  + torch.nn.functional.mse_loss(torch.norm(vec, dim=-1, keepdim=True) * 10, res["magnitude"])
+                  + torch.nn.functional.mse_loss(res["confidences"], conf) + torch.nn.functional.cross_entropy(res["part_labels"].permute(0, 2, 1).contiguous(), labels))
+            ev[1].record()
+            opt.zero_grad()
+            l2.backward()
+            ev[2].record()
+            opt.step()
+            ev[3].record()
+            torch.cuda.synchronize()
     ms = dt / a.steps * 1e3
     out = {"metric": "training steps/s (train.py:77-124: forward in train() mode + 4 losses + backward + Adam)", "value": round(a.steps / dt, 3), "unit": "steps/s",
            "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True, "dtype": "f32", "data": "synthetic",
            "config": {"workload": f"train.py batch shape: batch_size {B} x num_point {N}, EPN_layer_num {depth}, seeded random weights, Adam lr 1e-4, all four losses",
                       "path": "etch_amd.autograd / autograd_pt (un-fused differentiable kernels, train-mode BatchNorm on batch statistics)"},
            "scans_per_s": round(B * a.steps / dt, 3), "final_loss": round(float(loss.detach()), 6),
-           "phase_ms": {"forward + losses": round(ev[0].elapsed_time(ev[1]), 2), "backward": round(ev[1].elapsed_time(ev[2]), 2), "adam": round(ev[2].elapsed_time(ev[3]), 2)},
            "peak_hbm_gib": round(torch.cuda.max_memory_allocated(device) / 2 ** 30, 2), "vs_baseline": None}
-    if not a.no_cpu_baseline:
+    if a.full:
+        out["phase_ms"] = {"forward + losses": round(ev[0].elapsed_time(ev[1]), 2), "backward": round(ev[1].elapsed_time(ev[2]), 2),
+                           "adam": round(ev[2].elapsed_time(ev[3]), 2)}
+    if a.full and not a.no_cpu_baseline:
         from oracle import train_step as OT
         threads = a.cpu_threads or min(32, os.cpu_count() or 1)
         torch.set_num_threads(threads)
@@ -533,9 +542,11 @@ def main():
     ap.add_argument("--points", type=int, default=0, help="points per scan (default: the config's)")
     ap.add_argument("--forward-only", action="store_true", help="BASELINE.json configs[1]: a step is the equivariant forward only")
     ap.add_argument("--same-batch", action="store_true", help="feed the same resident batch every step (default: a distinct batch per step)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the stage2_latency / single_scan_latency legs (profiling runs: their launches "
-                    "of other batch sizes would mix into the per-kernel averages of the trace)")
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the headline figure: single-scan latency, synchronous schedule, "
+                    "well-posed markers, roofline pass, stage-2 latency, CPU baseline (default: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the well-posed / stage2_latency / single_scan_latency legs (profiling "
+                    "runs: their launches of other batch sizes would mix into the per-kernel averages of the trace)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="torch CPU threads of the cpu_baseline leg (0: min(32, cores))")
     ap.add_argument("--no-pin", action="store_true", help="do not pin ranks to the cores of their GPU's NUMA node (N > 1 only)")
     ap.add_argument("--sync", action="store_true", help="synchronous steps (stage 2 of a batch finishes before stage 1 of the next starts). Default: the "
@@ -599,7 +610,7 @@ def main():
         except Exception as e:                                  # an unreadable / unexpected topology must not stop the job
             print(f"[bench] rank {rank}: CPU pinning skipped ({type(e).__name__}: {e})", file=sys.stderr)
     latency_child = None
-    if world == 1 and a.config == 2 and not a.forward_only and not a.no_extras and not os.environ.get("ETCH_BENCH_DRY"):
+    if a.full and world == 1 and a.config == 2 and not a.forward_only and not a.no_extras and not os.environ.get("ETCH_BENCH_DRY"):
         # single-scan latency as ONE HIP graph, measured in a child process that owns the GPU alone: started (and finished) BEFORE this
         # process makes its first GPU call, so neither side shares hardware queues with the other
         import subprocess
@@ -719,20 +730,21 @@ def main():
         ht = np.array(pipe.host_times[-a.steps:])
         print("host ms per submit (wait for the oldest ticket / finalize it / enqueue the batch): median %s, max %s; enqueue ms per step: %s"
               % (np.round(np.median(ht, 0), 2), np.round(ht.max(0), 2), " ".join("%.0f" % v for v in ht[:, 2])), file=sys.stderr)
-    # the same K steps without the cross-step overlap (untimed here; reported next to the headline for transparency)
+    # --full: the first (up to 5) of the K steps without the cross-step overlap (untimed in `value`; reported next to the headline for transparency)
     sync()
     ts = time.perf_counter()
-    for k in range(min(a.steps, 5)):
-        step(timed[k])
+    unpipelined = timed[:5] if a.full else []
+    for p in unpipelined:
+        step(p)
     step(pts)           # batch 0 last: it provides the per-scan result rows for the end-of-job gather and parity_scan0
     sync()
-    sync_ms = (time.perf_counter() - ts) / (min(a.steps, 5) + 1) * 1e3
+    sync_ms = (time.perf_counter() - ts) / (len(unpipelined) + 1) * 1e3
 
-    # second, labelled leg: the same K steps with the pipeline's stage 2 consuming WELL-POSED per-scan markers (stage 1 unchanged; get_markers
+    # second, labelled leg (--full): the same K steps with the pipeline's stage 2 consuming WELL-POSED per-scan markers (stage 1 unchanged; get_markers
     # still runs on the network's output): with the bench's seeded random weights the network's own markers leave ~2 of 86 valid and the
     # fit freezes early, so this is the figure a trained network's markers would give
     wp = None
-    if not dry and not a.forward_only and not a.no_extras:
+    if a.full and not dry and not a.forward_only and not a.no_extras:
         mk_wp = well_posed_markers(args, device, B)
         pipe_wp, _ = choose_pipeline(args, model, pts, "neutral", max_in_flight=in_flight, schedule=sched_report["schedule"] if a.pipeline else "eager",
                                      stage1_streams=a.stage1_streams, want_trace=True, markers_override=mk_wp[:3], **fit_kw)
@@ -801,14 +813,30 @@ def main():
                       "collective_backend": (torch.distributed.get_backend() + (" (forced world-size-1 group: ETCH_FORCE_DIST)" if world == 1 else ""))
                       if torch.distributed.is_initialized() else None},
            "gathered_rows": {"columns": row_names, "scans_reported": int(allrows.shape[0]), "finite_scans": int(finite.sum()),
-                             "mean": [float(v) for v in allrows[finite].mean(0)] if bool(finite.any()) else None},
-           "ms_per_step_synchronous": round(sync_ms, 3)}
+                             "mean": [float(v) for v in allrows[finite].mean(0)] if bool(finite.any()) else None}}
+    if a.full:
+        out["ms_per_step_synchronous"] = round(sync_ms, 3)
     if dry:
         out["dry_run"] = True
         print(json.dumps(out), flush=True)
         return
     out["peak_hbm_gib"] = round(torch.cuda.max_memory_allocated(device) / 2 ** 30, 2)
     out["allocator_reserved_gib"] = round(getattr(pipe, "reserved_gib", 0.0), 2)       # free blocks handed to the streams' allocator pools up front (pipeline._reserve_allocator)
+    if N == 5000 and not a.forward_only:
+        # SURVEY 8d: 152.4 GFLOP matmul / conv + 5.2 GFLOP kernel-weight generation per 5 000-point scan -> 1.0 ms at the fp32-MFMA
+        # peak, HBM-side 0.05 ms: ceiling ~ 1 030 scans/s per GPU for the whole path
+        # ceiling_mixed (the lead): the products that run as two fp16 planes (everything but the first conv's VALU work and the kernel-weight generation:
+        # 140.7 + 11.7 of the 152.4 GFLOP since round 5 moved the attention scores / P V too) at the dense fp16 peak / 3 cross terms, the weight generation
+        # (5.2 GFLOP) at the fp32 peak
+        t_mixed = 152.4e9 / (F16_MFMA_PEAK_TFLOPS / 3.0 * 1e12) + 5.2e9 / (FP32_MFMA_PEAK_TFLOPS * 1e12)
+        out["path_roofline"] = {"ceiling_mixed": round(1.0 / t_mixed), "frac_mixed": round(value / world * t_mixed, 4),
+                                "ceiling_scans_per_s_per_gpu_fp32_matrix_peak": 1030, "frac_vs_fp32_matrix_peak": round(value / world / 1030.0, 4),
+                                "note": "frac_mixed (lead) = value / ceiling_mixed: 152.4 GFLOP of products per scan at the dense fp16 matrix peak / 3 cross terms (833 TFLOP/s) "
+                                        "+ 5.2 GFLOP weight generation at the fp32 peak; the second pair prices everything at the fp32 matrix peak, the unit SURVEY 8d's "
+                                        "1 030 scans/s ceiling is written in (the path no longer runs on that pipe)"}
+    if not a.full:                      # the legs below run with --full only
+        print(json.dumps(out), flush=True)
+        return
 
     # roofline of the dominant kernel: one instrumented pass of the same step (HIP events on the launch stream).
     # the instrumented pass runs the step on ONE stream (no heads / index ops on side streams): with kernels of several
@@ -942,19 +970,6 @@ def main():
         out["single_scan_latency"] = single_scan_latency(args, model, device, N)
         if latency_child is not None:
             out["single_scan_latency"]["own_process"] = latency_child
-    if N == 5000 and not a.forward_only:
-        # SURVEY 8d: 152.4 GFLOP matmul / conv + 5.2 GFLOP kernel-weight generation per 5 000-point scan -> 1.0 ms at the fp32-MFMA
-        # peak, HBM-side 0.05 ms: ceiling ~ 1 030 scans/s per GPU for the whole path
-        # ceiling_mixed (the lead): the products that run as two fp16 planes (everything but the first conv's VALU work and the kernel-weight generation:
-        # 140.7 + 11.7 of the 152.4 GFLOP since round 5 moved the attention scores / P V too) at the dense fp16 peak / 3 cross terms, the weight generation
-        # (5.2 GFLOP) at the fp32 peak
-        t_mixed = 152.4e9 / (F16_MFMA_PEAK_TFLOPS / 3.0 * 1e12) + 5.2e9 / (FP32_MFMA_PEAK_TFLOPS * 1e12)
-        out["path_roofline"] = {"ceiling_mixed": round(1.0 / t_mixed), "frac_mixed": round(value / world * t_mixed, 4),
-                                "ceiling_scans_per_s_per_gpu_fp32_matrix_peak": 1030, "frac_vs_fp32_matrix_peak": round(value / world / 1030.0, 4),
-                                "note": "frac_mixed (lead) = value / ceiling_mixed: 152.4 GFLOP of products per scan at the dense fp16 matrix peak / 3 cross terms (833 TFLOP/s) "
-                                        "+ 5.2 GFLOP weight generation at the fp32 peak; the second pair prices everything at the fp32 matrix peak, the unit SURVEY 8d's "
-                                        "1 030 scans/s ceiling is written in (the path no longer runs on that pipe)"}
-
     if world == 1 and not a.no_cpu_baseline:
         def refit(run):          # the GPU fit of batch 0 with a shortened schedule (parity partner of the bounded oracle run)
             _, mk_, va_, _, aux_ = predict_smpl_batch(args, model, pts, "neutral", return_trace=True, steps_stage0=run[0], steps_stage1=run[1])

@@ -247,7 +247,7 @@ def test_bench_gpus2_self_launch_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(ETCH_ALL_RANKS_DEVICE0="1", ETCH_DIST_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2",
-                        "--points", "1024"], env=env, capture_output=True, text=True, timeout=900)
+                        "--points", "1024", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -255,6 +255,32 @@ def test_bench_gpus2_self_launch_on_one_gpu():
     assert out["n_gpus"] == 2 and out["config"]["global_batch"] == 4 and out["config"]["launcher"] == "self"
     assert out["gathered_rows"]["scans_reported"] == 4 and out["roofline"]["kernel"]
     assert "cpu_baseline" not in out                      # rank 0 at N = 1 only
+
+
+def test_bench_plain_run_is_the_headline_only(tmp_path):
+    """`python bench.py` without --full: set-up, warm-up, the timed steps, --dump-outputs and the result line.  None of the legs of --full
+    (single-scan latency, synchronous schedule, well-posed markers, roofline pass, stage-2 latency, CPU baseline) runs or reports."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "ETCH_FORCE_DIST")}
+    dump = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2",
+                        "--points", "1024", "--dump-outputs", str(dump)], env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["n_gpus"] == 1 and out["steps"] == 2 and out["warmup"] == 1 and out["unit"] == "scans/s" and out["higher_is_better"] is True
+    assert out["dtype"].startswith("f32") and out["value"] == pytest.approx(2 / (out["ms_per_step"] * 1e-3), rel=1e-3)
+    assert out["gathered_rows"]["scans_reported"] == 2 and out["gathered_rows"]["finite_scans"] == 2
+    full_only = {"ms_per_step_synchronous", "roofline", "kernel_breakdown_ms", "whole_step_mfma_frac", "stage2_latency", "value_well_posed_fit",
+                 "well_posed_fit", "single_scan_latency", "cpu_baseline", "parity_scan0"}
+    assert not full_only & set(out)
+    names = sorted(f[:-4] for f in os.listdir(dump))
+    assert names == ["betas", "global_orient", "joints", "markers", "pose", "transl", "valid", "vertices"]
+    assert np.load(dump / "vertices.npy").shape[0] == 2
 
 
 def test_evaluate_dataset_on_the_reference_folder_layout(tmp_path):

@@ -77,6 +77,18 @@ def test_bench_self_launch_two_ranks_control_flow():
     assert out["value"] == __import__("pytest").approx(2 * 4 * 3 / (out["ms_per_step"] * 3e-3), rel=1e-3)
 
 
+def test_bench_full_legs_run_with_full_only():
+    """The legs beside the headline run with --full only, and the self-launcher hands --full on to its ranks: the synchronous-schedule
+    figure (the one of them the ETCH_BENCH_DRY stub reaches) is absent from a plain run's line and present with --full."""
+    import json
+    argv = ("--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2", "--points", "64")
+    plain, full = (_bench({"ETCH_BENCH_DRY": "1"}, *argv, *extra) for extra in ((), ("--full",)))
+    assert plain.returncode == 0 and full.returncode == 0, (plain.stderr[-2000:], full.stderr[-2000:])
+    plain, full = (json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0]) for r in (plain, full))
+    assert "ms_per_step_synchronous" not in plain and full["ms_per_step_synchronous"] > 0
+    assert plain["gathered_rows"] == full["gathered_rows"]
+
+
 def test_bench_self_launch_propagates_a_rank_failure():
     """A rank that dies must fail the job (and must not leave its peers waiting in a barrier)."""
     r = _bench({"ETCH_BENCH_DRY": "1", "ETCH_BENCH_DRY_FAIL_RANK": "1"}, "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2",
