@@ -9,8 +9,8 @@
   * `EvalDataset` reads the reference's on-disk layout (README.md:74-90; src/data_utils/GT_dataloader_mixed.py:110-161,259-274):
     scans `<scan_dir>/<id>/<id>.obj`, body models `<smpl_dir>/<id>/{info_<id>.npz, mesh_smpl_<id>.obj}`, per-id `<infopoints_dir>/<id>.npz`
     and the pickled list of activated ids -- the inference-side fields only (points sampled on the scan, gender, ground-truth SMPL
-    vertices / joints); the training targets of that loader (vectors, geodesic confidences, labels: cKDTree / potpourri3d / trimesh
-    proximity queries) and eval.py's visualisation exports are out of scope.
+    vertices / joints).  The training targets of that loader (vectors, geodesic confidences, labels) are built by
+    etch_amd.datasets.GTDataset (DESIGN sections 9 and 10); eval.py's visualisation exports are out of scope.
   * `evaluate_dataset` is eval.py's loop (:76-265): batches, per-sample outputs, v2v_score.txt with its summary block."""
 import os
 

@@ -1323,3 +1323,61 @@ def remove_close(points, radius):
     rem = torch.empty((C,), dtype=torch.int32, device=points.device)
     _lib.check(_lib.lib().etch_remove_close(C, _ptr(points), ctypes.c_double(r * r), _ptr(deg), _ptr(rem), _stream()), "etch_remove_close")
     return deg, rem.bool()
+
+
+# ------------------------------------------------------------------ geodesic labels and confidences (csrc/geodesic.hip)
+def geodesic_heat(verts, topo, sources, t_coef=1.0, intrinsic_delaunay=True, want_dist=True, want_min=True, want_mesh=False, mollify_eps=1e-6,
+                  delaunay_tol=1e-12, max_rounds=4096, heat_tol=1e-9, heat_omega=None, heat_cap=50000, cg_rtol=1e-10, cg_cap=50000):
+    """Heat-method distances: verts (B,V,3) fp64 on the device, topo = the shared edge topology (fv, fe, fs (F,3), ef, ev (E,2) int32
+    device tensors, etch_amd.geodesic.EdgeTopology.device()), sources (S,) int32 -> dict with dist (B,S,V) fp64, dmin (B,V) fp64, label (B,V)
+    int32, iters (B,S,2) int32 (heat sweeps, CG iterations), flips (B,) and, with want_mesh, ev (B,E,2), el (B,E), ecot (B,E,2), area (B,F).
+    heat_omega (None: 1 on the intrinsic Delaunay mesh, 0.7 on the cotan one) damps the heat sweeps.
+    Raises EtchHipError on bad input before any launch, and when a column reaches an iteration cap."""
+    _need(verts, torch.float64, "verts")
+    if heat_omega is None:
+        heat_omega = 1.0 if intrinsic_delaunay else 0.7
+    fv, fe, fs, ef, ev = topo
+    for t, n in zip(topo, ("fv", "fe", "fs", "ef", "ev")):
+        _need(t, torch.int32, n)
+    if verts.dim() != 3 or verts.shape[2] != 3:
+        raise _lib.EtchHipError(f"verts must be (B,V,3), got {tuple(verts.shape)}")
+    B, V, _ = verts.shape
+    F, E = fv.shape[0], ef.shape[0]
+    if fv.shape != (F, 3) or fe.shape != (F, 3) or fs.shape != (F, 3) or ef.shape != (E, 2) or ev.shape != (E, 2) or B < 1 or F < 1:
+        raise _lib.EtchHipError("topology must be fv, fe, fs (F,3) and ef, ev (E,2) with B, F >= 1")
+    if int(fv.min()) < 0 or int(fv.max()) >= V or int(ev.min()) < 0 or int(ev.max()) >= V:
+        raise _lib.EtchHipError(f"vertex indices must lie in [0, {V})")
+    if int(fe.min()) < 0 or int(fe.max()) >= E or int(ef.max()) >= F or int(ef[:, 0].min()) < 0 or int(ef.min()) < -1:
+        raise _lib.EtchHipError("edge / face indices out of range")
+    sources = _need(sources, torch.int32, "sources")
+    S = int(sources.numel())
+    if sources.dim() != 1 or S < 1:
+        raise _lib.EtchHipError("sources must be a non-empty (S,) int32 tensor")
+    if int(sources.min()) < 0 or int(sources.max()) >= V:
+        raise _lib.EtchHipError(f"source indices must lie in [0, {V})")
+    dev = verts.device
+    nb = ctypes.c_longlong(0)
+    _lib.check(_lib.lib().etch_geodesic_workspace(B, V, F, E, S, ctypes.byref(nb)), "etch_geodesic_workspace")
+    ws = torch.empty((max(int(nb.value), 8),), dtype=torch.uint8, device=dev)
+    dist = torch.empty((B, S, V), dtype=torch.float64, device=dev)
+    dmin = torch.empty((B, V), dtype=torch.float64, device=dev) if want_min else None
+    label = torch.empty((B, V), dtype=torch.int32, device=dev) if want_min else None
+    iters = torch.empty((B, S, 2), dtype=torch.int32, device=dev)
+    flips = (ctypes.c_int * B)()
+    mesh = {}
+    if want_mesh:
+        mesh = {"ev": torch.empty((B, E, 2), dtype=torch.int32, device=dev), "el": torch.empty((B, E), dtype=torch.float64, device=dev),
+                "ecot": torch.empty((B, E, 2), dtype=torch.float64, device=dev), "area": torch.empty((B, F), dtype=torch.float64, device=dev)}
+    _lib.check(_lib.lib().etch_geodesic_heat(B, V, F, E, S, _ptr(verts), _ptr(fv), _ptr(fe), _ptr(fs), _ptr(ef), _ptr(ev), _ptr(sources),
+                                             ctypes.c_double(t_coef), int(bool(intrinsic_delaunay)), ctypes.c_double(mollify_eps),
+                                             ctypes.c_double(delaunay_tol), int(max_rounds), ctypes.c_double(heat_tol), ctypes.c_double(heat_omega), int(heat_cap),
+                                             ctypes.c_double(cg_rtol), int(cg_cap), _ptr(ws), _ptr(dist), _optptr(dmin), _optptr(label), _ptr(iters),
+                                             flips, _optptr(mesh.get("ev")), _optptr(mesh.get("el")), _optptr(mesh.get("ecot")),
+                                             _optptr(mesh.get("area")), _stream()), "etch_geodesic_heat")
+    it = iters.cpu()
+    if bool((it < 0).any()):
+        bad = torch.nonzero((it < 0).any(2))[:4].tolist()
+        raise _lib.EtchHipError(f"etch_geodesic_heat: (body, source) {bad} reached an iteration cap (heat {heat_cap}, CG {cg_cap})")
+    out = {"dist": dist if want_dist else None, "dmin": dmin, "label": label, "iters": it, "flips": list(flips)}
+    out.update(mesh)
+    return out

@@ -694,6 +694,24 @@ int etch_vertex_normals(int V, int F, const double* verts, const int* faces, con
  * containing each point; removed (C) int32 = 1 where the point is dropped (each pair drops its endpoint of higher degree, i on a tie). */
 int etch_remove_close(int C, const double* points, double r2, int* degree, int* removed, void* stream);
 
+/* ---- geodesic labels and confidences (GT_dataloader.py:124-145, pp3d.MeshHeatMethodDistanceSolver) -------------- */
+
+/* Workspace bytes of etch_geodesic_heat for B bodies of V vertices, F faces, E edges and S sources. */
+int etch_geodesic_workspace(int B, int V, int F, int E, int S, long long* bytes);
+/* Heat-method distances from S source vertices on B bodies (verts (B,V,3) fp64) sharing one manifold topology stored by edges (fv0, fe0, fs0
+ * (F,3): corners, the edge opposite each corner, the slot of that edge the face holds; ef0 (E,2): faces, -1 = boundary; ev0 (E,2) endpoints),
+ * all int32 and in range.  intrinsic_delaunay != 0: mollify (relative mollify_eps) and flip while cot a + cot b < -delaunay_tol, at most
+ * max_rounds rounds (ETCH_EUNSUPPORTED past them; waits on `stream`).  t = t_coef * (mean input edge length)^2.  Heat: Jacobi sweeps (damped
+ * by heat_omega when it is not 1) until no vertex changes by more than heat_tol of its value (heat_cap sweeps at most); Poisson: Jacobi-PCG until |r| <= cg_rtol |b| (cg_cap at most).
+ * Outputs: dist (B,S,V) fp64 with dist[source] = 0; dmin (B,V) / label (B,V) int32 = min / first argmin over the sources, or both NULL;
+ * iters (B,S,2) int32 = heat sweeps, CG iterations (-1 where the cap was hit); flips (B) HOST int32.  Optional (NULL = not written): out_ev
+ * (B,E,2) int32 and out_el (B,E) fp64 = the final triangulation's edges and lengths, out_ecot (B,E,2) the cotans opposite each edge,
+ * out_area (B,F) face areas.  S = 0 builds the triangulation and operators only. */
+int etch_geodesic_heat(int B, int V, int F, int E, int S, const double* verts, const int* fv0, const int* fe0, const int* fs0, const int* ef0,
+                       const int* ev0, const int* sources, double t_coef, int intrinsic_delaunay, double mollify_eps, double delaunay_tol,
+                       int max_rounds, double heat_tol, double heat_omega, int heat_cap, double cg_rtol, int cg_cap, void* workspace, double* dist, double* dmin,
+                       int* label, int* iters, int* flips, int* out_ev, double* out_el, double* out_ecot, double* out_area, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
