@@ -1381,3 +1381,72 @@ def geodesic_heat(verts, topo, sources, t_coef=1.0, intrinsic_delaunay=True, wan
     out = {"dist": dist if want_dist else None, "dmin": dmin, "label": label, "iters": it, "flips": list(flips)}
     out.update(mesh)
     return out
+
+
+# ------------------------------------------------------------------ the training step (csrc/train_step.hip)
+TRAIN_STATUS_NAN, TRAIN_STATUS_BAD_LABEL = 1, 2       # include/etch_hip.h: ETCH_TRAIN_STATUS_*
+_TRAIN_LOSS_WS = {}
+
+
+def train_losses(direction, magnitude, confidences, part_labels, t_vectors, t_confidences, t_labels, index, weights, scale_magnitude, counter, status=None):
+    """etch_train_losses: the four losses of train.py:81-101 and the gradient of their sum, one launch.  Heads (B,K,3) / (B,K,1) / (B,K,1) / (B,K,M) or
+    None; targets (B,N,3), (B,N,1), (B,N) int64; index (B,K) int64; weights = (direction_w, magnitude_w, confidence_w, part_label_w); counter: one zero
+    int32 (left zero).  Returns (losses (5) = the four weighted losses and their sum, status (>= 1 int32, [0] = the ETCH_TRAIN_STATUS_* bits), gradients
+    in the heads' order, None for an absent head)."""
+    heads = [direction, magnitude, confidences, part_labels]
+    first = next((h for h in heads if h is not None), None)
+    if first is None:
+        raise _lib.EtchHipError("train_losses: at least one head output is needed")
+    B, K = first.shape[0], first.shape[1]
+    for h, last, name in zip(heads, (3, 1, 1, None), ("direction", "magnitude", "confidences", "part_labels")):
+        if h is not None:
+            _need(h, torch.float32, name)
+            if h.dim() != 3 or h.shape[:2] != (B, K) or (last is not None and h.shape[2] != last):
+                raise _lib.EtchHipError(f"{name} must be (B,K,{last or 'M'}) with B, K = {B}, {K}; got {tuple(h.shape)}")
+    if B * K < 1:
+        raise _lib.EtchHipError("train_losses: empty batch")
+    _need(index, torch.int64, "index")
+    if index.shape != (B, K):
+        raise _lib.EtchHipError(f"index must be ({B},{K}), got {tuple(index.shape)}")
+    N = None
+    for t, dtype, tail, name, used in ((t_vectors, torch.float32, (3,), "vectors", direction is not None or magnitude is not None),
+                                       (t_confidences, torch.float32, (1,), "confidences", confidences is not None),
+                                       (t_labels, torch.int64, (), "labels", part_labels is not None)):
+        if not used:
+            continue
+        if t is None:
+            raise _lib.EtchHipError(f"train_losses: the target `{name}` is needed")
+        _need(t, dtype, name)
+        if t.dim() != 2 + len(tail) or t.shape[0] != B or tuple(t.shape[2:]) != tail or (N is not None and t.shape[1] != N):
+            raise _lib.EtchHipError(f"target {name} must be (B,N{',' if tail else ''}{','.join(map(str, tail))}), got {tuple(t.shape)}")
+        N = t.shape[1]
+    if N < 1:
+        raise _lib.EtchHipError("train_losses: empty targets")
+    M = part_labels.shape[2] if part_labels is not None else 0
+    dev = first.device
+    key = (dev.index, _stream().value)
+    ws = _TRAIN_LOSS_WS.get(key)
+    if ws is None:
+        ws = _TRAIN_LOSS_WS[key] = torch.empty((_lib.lib().etch_train_losses_workspace_doubles(),), dtype=torch.float64, device=dev)
+    losses = torch.empty((5,), dtype=torch.float32, device=dev)
+    if status is None:
+        status = torch.zeros((1,), dtype=torch.int32, device=dev)
+    grads = [torch.empty_like(h) if h is not None else None for h in heads]
+    w = [ctypes.c_float(float(x)) for x in weights]
+    used_t = [t_vectors if (direction is not None or magnitude is not None) else None, t_confidences if confidences is not None else None,
+              t_labels if part_labels is not None else None]
+    _lib.check(_lib.lib().etch_train_losses(int(B), int(K), int(N), int(M), *[_optptr(h) for h in heads], *[_optptr(t) for t in used_t], _ptr(index),
+                                            w[0], w[1], w[2], w[3], ctypes.c_float(float(scale_magnitude)), _ptr(ws), _ptr(counter), _ptr(losses),
+                                            _ptr(status), *[_optptr(g) for g in grads], _stream()), "etch_train_losses")
+    return losses, status, grads
+
+
+def guarded_adam_chunk():
+    return int(_lib.lib().etch_guarded_adam_chunk())
+
+
+def guarded_adam_step(T, C, chunk_tensor, first_chunk, numel, pmv, grads, status, steps, chunkflags, lr, betas, eps, counters):
+    """etch_guarded_adam_step over tables built by etch_amd.optim.GuardedAdam (all device tensors; status may be None)."""
+    _lib.check(_lib.lib().etch_guarded_adam_step(int(T), int(C), _ptr(chunk_tensor), _ptr(first_chunk), _ptr(numel), _ptr(pmv), _ptr(grads), _optptr(status),
+                                                 _ptr(steps), _ptr(chunkflags), ctypes.c_double(lr), ctypes.c_double(betas[0]), ctypes.c_double(betas[1]),
+                                                 ctypes.c_double(eps), _ptr(counters), _stream()), "etch_guarded_adam_step")

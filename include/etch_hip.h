@@ -712,6 +712,38 @@ int etch_geodesic_heat(int B, int V, int F, int E, int S, const double* verts, c
                        int max_rounds, double heat_tol, double heat_omega, int heat_cap, double cg_rtol, int cg_cap, void* workspace, double* dist, double* dmin,
                        int* label, int* iters, int* flips, int* out_ev, double* out_el, double* out_ecot, double* out_area, void* stream);
 
+/* ---- the training step (train.py:81-125) -------------------------------------------------------------------------- */
+
+/* Bits of the status word etch_train_losses writes and etch_guarded_adam_step reads. */
+#define ETCH_TRAIN_STATUS_NAN 1          /* the total loss is NaN: the optimizer step that follows changes nothing */
+#define ETCH_TRAIN_STATUS_BAD_LABEL 2    /* a label outside [0, M) or a gather index outside [0, N): that row contributed nothing */
+/* The four losses of train.py:81-101 and the gradient of their sum, one launch.  Head outputs direction (B,K,3), magnitude (B,K,1), confidences
+ * (B,K,1), part_labels (B,K,M) logits -- any may be NULL (absent: loss 0, no gradient; at least one given); targets t_vectors (B,N,3),
+ * t_confidences (B,N,1), t_labels (B,N) int64, read at index (B,K) int64 = selected_indexs[:, :, 0].
+ *   losses[0] = direction_w mean(1 - cos(t_vectors_k, direction)), each norm clamped at 1e-8 (F.cosine_similarity)
+ *   losses[1] = magnitude_w mean((|t_vectors_k| scale_magnitude - magnitude)^2)       losses[2] = confidence_w mean((confidences - t_confidences_k)^2)
+ *   losses[3] = part_label_w mean(logsumexp(row) - row[label])  (row maximum subtracted)    losses[4] = their sum
+ * g_* (shapes of the heads): d losses[4] / d head.  fp32 per element, sums in fp64 in a fixed order: bitwise reproducible.  status[0] = the
+ * ETCH_TRAIN_STATUS_* bits of this call.  workspace: etch_train_losses_workspace_doubles() doubles; counter: one unsigned, zero before the first
+ * call and left zero (as etch_bn_train_forward's). */
+int etch_train_losses_workspace_doubles(void);
+int etch_train_losses(int B, int K, int N, int M, const float* direction, const float* magnitude, const float* confidences, const float* part_labels,
+                      const float* t_vectors, const float* t_confidences, const long long* t_labels, const long long* index, float direction_w,
+                      float magnitude_w, float confidence_w, float part_label_w, float scale_magnitude, double* workspace, unsigned* counter,
+                      float* losses, int* status, float* g_direction, float* g_magnitude, float* g_confidences, float* g_part_labels, void* stream);
+
+/* torch.optim.Adam (weight_decay 0, no amsgrad) over T fp32 tensors with train.py:111-125's guards, 2 launches whatever T is.  The tensors are cut
+ * into C chunks of etch_guarded_adam_chunk() elements (a tensor's last chunk shorter): chunk_tensor (C) = the tensor of each chunk, first_chunk
+ * (T+1) = the first chunk of each tensor, numel (T).  pmv (3,T) = device addresses of parameter, exp_avg, exp_avg_sq; grads (T) = address of each
+ * gradient, 0 = none (the tensor is skipped: no moment update, no step).  A gradient that holds a NaN, or +inf and -inf, is taken as zero
+ * (`param.grad.sum().isnan()`); counters[0] counts such tensors.  steps (T) fp32: the per-tensor step counts, advanced here.  status (may be NULL):
+ * with ETCH_TRAIN_STATUS_NAN set nothing is changed and counters[1] advances; ETCH_TRAIN_STATUS_BAD_LABEL is ORed into counters[2].
+ * chunkflags: C unsigned of scratch.  16-byte accesses where parameter, gradient and moments are 16-byte aligned, scalar otherwise. */
+int etch_guarded_adam_chunk(void);
+int etch_guarded_adam_step(int T, int C, const int* chunk_tensor, const int* first_chunk, const long long* numel, const unsigned long long* pmv,
+                           const unsigned long long* grads, const int* status, float* steps, unsigned* chunkflags, double lr, double beta1,
+                           double beta2, double eps, int* counters, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
