@@ -23,7 +23,10 @@ from .infopoints import tightness_vectors
 class GTDataset:
     gender_dict = {0: "female", 1: "male"}                  # GT_dataloader.py:75
 
-    def __init__(self, args, device=None, laplacian="intrinsic_delaunay", verbose=True):
+    def __init__(self, args, device=None, laplacian="intrinsic_delaunay", verbose=True, reader="python"):
+        if reader not in ("python", "native"):
+            raise ValueError(f"reader must be 'python' or 'native', got {reader!r}")
+        self.reader = reader                                  # "native": etch_amd.mesh_io.read_obj for an item's two meshes, the same arrays
         self.seed = args.seed
         self.scan_dir = args.scan_dir
         self.smpl_dir = args.smpl_dir
@@ -75,6 +78,8 @@ class GTDataset:
 
     def __getitem__(self, index):
         from .inference_demo import load_obj, sample_points_from_mesh
+        if self.reader == "native":
+            from .mesh_io import read_obj as load_obj
         i = self.id_list[index]
         ip_path, scan_path, smpl_path, info_path = self._paths(i)
         assert os.path.isfile(ip_path) and os.path.isfile(scan_path) and os.path.isfile(smpl_path) and os.path.isfile(info_path)

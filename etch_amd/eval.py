@@ -11,24 +11,36 @@
     and the pickled list of activated ids -- the inference-side fields only (points sampled on the scan, gender, ground-truth SMPL
     vertices / joints).  The training targets of that loader (vectors, geodesic confidences, labels) are built by
     etch_amd.datasets.GTDataset (DESIGN sections 9 and 10); eval.py's visualisation exports are out of scope.
-  * `evaluate_dataset` is eval.py's loop (:76-265): batches, per-sample outputs, v2v_score.txt with its summary block."""
+  * `evaluate_dataset` is eval.py's loop (:76-265): batches, per-sample outputs, v2v_score.txt with its summary block.
+  * `python -m etch_amd.eval` is eval.py's command line (:270-315) on top of it.  With ingest="device" (the command's default)
+    the meshes are read by the native OBJ reader on worker threads, one batch ahead of the GPU, sampled on the device per batch and written by
+    the native writer."""
+import argparse
+import json
 import os
+import sys
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
 from . import ops
-from .models.fit_SMPL import fit_smpl
+from .models.fit_SMPL import Mesh, fit_smpl
 
 
 class EvalDataset:
     """Inference-side view of the reference's GTDataset (GT_dataloader_mixed.py:110-161).  Items:
-    {id, hitpts (num_point,3) float32, gender "female" | "male", gt_vertices (V,3), gt_joints (J,3) or None}."""
+    {id, hitpts (num_point,3) float32, gender "female" | "male", gt_vertices (V,3), gt_joints (J,3) or None}.
+    ingest="device": the meshes come from the native reader and an item carries `scan` (the parsed Mesh) in place of `hitpts`; the points are
+    sampled on the device per batch (evaluate_dataset), every scan under the key seed + 15."""
 
     gender_dict = {0: "female", 1: "male"}                # GT_dataloader_mixed.py:133
 
-    def __init__(self, scan_dir, smpl_dir, infopoints_dir, activated_ids_path=None, num_point=5000, seed=0):
+    def __init__(self, scan_dir, smpl_dir, infopoints_dir, activated_ids_path=None, num_point=5000, seed=0, ingest="host"):
         import pickle
+        if ingest not in ("host", "device"):
+            raise ValueError(f"ingest must be 'host' or 'device', got {ingest!r}")
+        self.ingest = ingest
         self.scan_dir, self.smpl_dir, self.infopoints_dir = scan_dir, smpl_dir, infopoints_dir
         activated = None
         if activated_ids_path:
@@ -44,33 +56,75 @@ class EvalDataset:
 
     def __getitem__(self, index):
         from .inference_demo import load_obj, sample_points_from_mesh
+        if self.ingest == "device":
+            from .mesh_io import read_obj as load_obj
         i = self.id_list[index]
         scan = load_obj(os.path.join(self.scan_dir, i, f"{i}.obj"))
         smpl = load_obj(os.path.join(self.smpl_dir, i, f"mesh_smpl_{i}.obj"))
         info = np.load(os.path.join(self.smpl_dir, i, f"info_{i}.npz"))
-        # the reference samples with trimesh.sample.sample_surface(scan, num_point, seed = self.seed + 15) (:201-203); same
-        # distribution (area-weighted faces, uniform barycentric coordinates) from our seeded sampler
-        pts = sample_points_from_mesh(scan, self.num_point, seed=self.seed + 15).astype(np.float32)
-        return {"id": i, "hitpts": pts, "gender": self.gender_dict[int(np.asarray(info["gender"]).item())],
-                "gt_vertices": np.asarray(smpl.vertices, np.float32), "gt_joints": np.asarray(info["joints"], np.float32) if "joints" in info.files else None}
+        item = {"id": i, "gender": self.gender_dict[int(np.asarray(info["gender"]).item())], "gt_vertices": np.asarray(smpl.vertices, np.float32),
+                "gt_joints": np.asarray(info["joints"], np.float32) if "joints" in info.files else None}
+        if self.ingest == "device":
+            item["scan"] = scan                                # sampled on the device with its batch (evaluate_dataset)
+        else:
+            # the reference samples with trimesh.sample.sample_surface(scan, num_point, seed = self.seed + 15) (:201-203); same
+            # distribution (area-weighted faces, uniform barycentric coordinates) from our seeded sampler
+            item["hitpts"] = sample_points_from_mesh(scan, self.num_point, seed=self.seed + 15).astype(np.float32)
+        return item
 
 
-def evaluate_dataset(args, model, dataset, batch_size=8, output_folder=None):
+def _device_batches(dataset, batch_size, prefetch):
+    """Batches of an ingest="device" dataset: the items of a batch are read on worker threads, and with prefetch >= 1 the reads of the next
+    `prefetch` batches are already running while the caller works on the current one."""
+    starts = list(range(0, len(dataset), batch_size))
+    depth = max(int(prefetch), 0)
+    with ThreadPoolExecutor(max_workers=min(16, batch_size)) as pool:
+        submit = lambda s: [pool.submit(dataset.__getitem__, k) for k in range(s, min(s + batch_size, len(dataset)))]
+        queue = [submit(s) for s in starts[:depth]]
+        for n, s in enumerate(starts):
+            if depth == 0:
+                queue.append(submit(s))
+            elif n + depth < len(starts):
+                queue.append(submit(starts[n + depth]))
+            yield [f.result() for f in queue.pop(0)]
+
+
+def _evaluate_dataset_device(args, model, dataset, batch_size, output_folder, prefetch):
+    from .mesh_io import sample_surface, write_obj
+    recs = []
+    for items in _device_batches(dataset, batch_size, prefetch):
+        # every id under one key, as the reference gives each the sampler seed self.seed + 15 (GT_dataloader_mixed.py:201-203)
+        hitpts, _, _ = sample_surface([it["scan"] for it in items], dataset.num_point, [dataset.seed + 15], center=False, device=args.device)
+        gtj = [it["gt_joints"] for it in items]
+        recs += evaluate_batch(args, model, hitpts, [it["gender"] for it in items], ids=[it["id"] for it in items],
+                               gt_vertices=[it["gt_vertices"] for it in items], gt_joints=None if any(j is None for j in gtj) else gtj,
+                               output_folder=output_folder, export=write_obj)
+    return recs
+
+
+def evaluate_dataset(args, model, dataset, batch_size=8, output_folder=None, ingest=None, prefetch=1):
     """eval.py:76-265: the whole dataset in batches through `evaluate_batch`; v2v_score.txt ends with the reference's summary block.
-    Returns (records, average v2v)."""
+    Returns (records, average v2v).  ingest (default: the dataset's): "host" = items sampled by the dataset one at a time in this thread;
+    "device" = native reader on worker threads `prefetch` batches ahead (0: none), device sampler per batch, native writer."""
+    ingest = ingest or getattr(dataset, "ingest", "host")
+    if ingest != getattr(dataset, "ingest", "host"):
+        raise ValueError(f"ingest={ingest!r} needs a dataset built with the same ingest (it has {getattr(dataset, 'ingest', 'host')!r})")
     output_folder = output_folder or args.output_folder
     os.makedirs(output_folder, exist_ok=True)
     score = os.path.join(output_folder, "v2v_score.txt")
     if os.path.exists(score):
         os.remove(score)                                   # eval.py:82-84
-    recs = []
-    for s in range(0, len(dataset), batch_size):
-        items = [dataset[k] for k in range(s, min(s + batch_size, len(dataset)))]
-        hitpts = torch.from_numpy(np.stack([it["hitpts"] for it in items])).to(args.device)
-        gtj = [it["gt_joints"] for it in items]
-        recs += evaluate_batch(args, model, hitpts, [it["gender"] for it in items], ids=[it["id"] for it in items],
-                               gt_vertices=[it["gt_vertices"] for it in items], gt_joints=None if any(j is None for j in gtj) else gtj,
-                               output_folder=output_folder)
+    if ingest == "device":
+        recs = _evaluate_dataset_device(args, model, dataset, batch_size, output_folder, prefetch)
+    else:
+        recs = []
+        for s in range(0, len(dataset), batch_size):
+            items = [dataset[k] for k in range(s, min(s + batch_size, len(dataset)))]
+            hitpts = torch.from_numpy(np.stack([it["hitpts"] for it in items])).to(args.device)
+            gtj = [it["gt_joints"] for it in items]
+            recs += evaluate_batch(args, model, hitpts, [it["gender"] for it in items], ids=[it["id"] for it in items],
+                                   gt_vertices=[it["gt_vertices"] for it in items], gt_joints=None if any(j is None for j in gtj) else gtj,
+                                   output_folder=output_folder)
     total = float(sum(r["v2v"] for r in recs))
     n = len(recs)
     with open(score, "a") as f:                            # eval.py:258-265
@@ -117,9 +171,10 @@ def fit_smpl_by_gender(args, pred_inner_points, pred_part_labels, pred_confidenc
     return meshes, markers, valid, info
 
 
-def evaluate_batch(args, model, hitpts, gender_list, ids=None, gt_vertices=None, gt_joints=None, output_folder=None):
+def evaluate_batch(args, model, hitpts, gender_list, ids=None, gt_vertices=None, gt_joints=None, output_folder=None, export=Mesh.export):
     """One eval.py iteration (eval.py:87-99,181-256) on a batch (B,K,3) already on the device.
-    Returns a list of per-sample dicts {id, v2v, mpjpe, valid_full} (metrics only when ground truth is given)."""
+    Returns a list of per-sample dicts {id, v2v, mpjpe, valid_full} (metrics only when ground truth is given).  export(mesh, path) writes the
+    predicted bodies (default Mesh.export)."""
     B = hitpts.shape[0]
     ids = list(ids) if ids is not None else [str(i) for i in range(B)]
     with torch.no_grad():
@@ -138,7 +193,7 @@ def evaluate_batch(args, model, hitpts, gender_list, ids=None, gt_vertices=None,
         if output_folder is not None:
             d = os.path.join(output_folder, f"{ids[j]}")
             os.makedirs(d, exist_ok=True)
-            meshes[j].export(os.path.join(d, f"forwarded_smpl_mesh_on_pred_{ids[j]}.obj"))
+            export(meshes[j], os.path.join(d, f"forwarded_smpl_mesh_on_pred_{ids[j]}.obj"))
             np.savez(os.path.join(d, f"output_smpl_info_{ids[j]}.npz"), body_pose=info[0][j][:21, :], hand_pose=info[0][j][21:23, :],
                      betas=info[1][j], global_orient=info[2][j], transl=info[3][j], joints=info[4][j])
             if "v2v" in rec:
@@ -146,3 +201,62 @@ def evaluate_batch(args, model, hitpts, gender_list, ids=None, gt_vertices=None,
                     f.write(f"{ids[j]}: {rec['v2v']}{'' if rec['valid_full'] else '  attention, the valid mask is not full'}\n")
         out.append(rec)
     return out
+
+
+def build_parser():
+    """eval.py:270-289's flags with their defaults, then this program's own."""
+    parser = argparse.ArgumentParser(description="ETCH evaluation on one MI355X (etch_amd)")
+    parser.add_argument("--activated_ids_path", type=str, default="datafolder/useful_data_4d-dress/val_ids_sampled_ratio10.pkl", help="pickled list of the ids to evaluate")
+    parser.add_argument("--scale_magnitude", type=int, default=10, help="factor between the magnitude head and metres")
+    parser.add_argument("--markerset_path", default="datafolder/useful_data_4d-dress/superset_smpl.json", type=str)
+    parser.add_argument("--seed", type=int, default=1, metavar="S", help="seed; every scan is sampled under seed + 15")
+    parser.add_argument("--infopoints_dir", type=str, default="datafolder/gt_4D-Dress_data/npz", help="folder of the per-id info-point files <id>.npz")
+    parser.add_argument("--scan_dir", type=str, default="datafolder/4D-DRESS/data_processed/model", help="folder of the scans, <id>/<id>.obj")
+    parser.add_argument("--smpl_dir", type=str, default="datafolder/4D-DRESS/data_processed/smplh", help="folder of the ground-truth bodies, <id>/{mesh_smpl_<id>.obj, info_<id>.npz}")
+    parser.add_argument("--model_path", type=str, default=None, help="state dict of the trained model; without it the seeded initial weights are scored, with a warning")
+    parser.add_argument("--batch_size", type=int, default=3, metavar="N")
+    parser.add_argument("--num_point", type=int, default=5000, metavar="N", help="points sampled on each scan")
+    parser.add_argument("--EPN_input_radius", type=float, default=0.4)
+    parser.add_argument("--EPN_layer_num", type=int, default=2, metavar="N")
+    parser.add_argument("--i", type=str, default=None, help="suffix of the output folder eval_outputs_<i>")
+    # this program's own
+    parser.add_argument("--body_model", type=str, default="", help="chumpy-free SMPL .pkl (else the reference's gender paths)")
+    parser.add_argument("--synthetic_body", action="store_true", help="use the seeded SMPL-shaped stand-in body model")
+    parser.add_argument("--output_root", type=str, default="./all_experiments/experiments")
+    parser.add_argument("--ingest", type=str, default="device", choices=["host", "device"],
+                        help="device: native OBJ reader one batch ahead on worker threads, GPU surface sampler, native writer; host: the Python "
+                             "reader and writer and the numpy sampler, one scan at a time")
+    parser.add_argument("--prefetch", type=int, default=1, help="--ingest device: batches read ahead of the GPU (0: none)")
+    return parser
+
+
+def main(argv=None):
+    """eval.py:270-315.  Returns (records, average v2v)."""
+    from .inference_demo import load_model, resolve_body_model
+    from .train import default_stuff
+
+    args = build_parser().parse_args(argv)
+    if not torch.cuda.is_available():
+        raise RuntimeError("etch_amd.eval needs a GPU: etch_amd has no CPU path")
+    args.cuda = True
+    args.device = torch.device("cuda")
+    default_stuff(args.seed)
+    args.output_folder = os.path.join(args.output_root, f"eval_outputs_{args.i}")
+    os.makedirs(args.output_folder, exist_ok=True)
+    with open(args.markerset_path, "r") as f:
+        args.markerset = json.load(f)
+    resolve_body_model(args)
+    if not args.model_path:
+        print("WARNING: no --model_path: scoring the seeded INITIAL weights, not a trained model (smoke runs only)", file=sys.stderr)
+        args.model_path = ""
+    model = load_model(args)
+    dataset = EvalDataset(args.scan_dir, args.smpl_dir, args.infopoints_dir, args.activated_ids_path, num_point=args.num_point, seed=args.seed,
+                          ingest=args.ingest)
+    print(f"Num of data: {len(dataset)}")
+    recs, avg = evaluate_dataset(args, model, dataset, batch_size=args.batch_size, prefetch=args.prefetch)
+    print(f"average v2v: {avg} over {len(recs)} samples; outputs under {args.output_folder}")
+    return recs, avg
+
+
+if __name__ == "__main__":
+    main()

@@ -98,10 +98,14 @@ def parse_args(argv=None):
                         help="after the marker fit, refine the body against the centred scan's vertices (chamfer_refine.py:fit_cham): "
                              "both directions, scan -> body only (partial scans) or body -> scan only (cluttered scans)")
     parser.add_argument("--refine_iters", type=int, default=500, help="Adam iterations of --chamfer_refine")
+    # absent unless given (the namespace of a run without the flag is what it always was): main() reads it with "host" as the default
+    parser.add_argument("--ingest", type=str, default=argparse.SUPPRESS, choices=["host", "device"],
+                        help="host (default): the Python OBJ reader / writer and the numpy sampler; device: the native reader and writer and "
+                             "the GPU sampler keyed by --seed (etch_amd.mesh_io; same distribution, other points)")
     return parser.parse_args(argv)
 
 
-def _refine_and_save(args, model, points, centered_mesh, original_center, scan_name):
+def _refine_and_save(args, model, points, centered_mesh, original_center, scan_name, export=Mesh.export):
     """--chamfer_refine: the marker fit, then fit_cham against the centred scan's vertices (the script's `vertices_scan`).  The OBJ is the
     refined mesh moved back by the scan centre; the .npz holds the refined parameters, `scale`, and the joints in the centred scan's
     frame ((joints + trans) * scale, the frame the LM joints of an unrefined run are written in)."""
@@ -114,7 +118,7 @@ def _refine_and_save(args, model, points, centered_mesh, original_center, scan_n
     scan = torch.from_numpy(np.asarray(centered_mesh.vertices, np.float32)).unsqueeze(0).to(args.device)
     verts, prm = fit_cham(bm, scan, init_from_fit(dev), prior=None, bidir=args.chamfer_refine, iterations=args.refine_iters)
     final = Mesh(verts[0] + original_center, meshes[0].faces)
-    final.export(os.path.join(args.output_folder, f"{scan_name}_pred_smpl.obj"))
+    export(final, os.path.join(args.output_folder, f"{scan_name}_pred_smpl.obj"))
     pose = prm["pose"][0].cpu().numpy()
     body = pose[3:].reshape(-1, 3)
     scale = prm["scale"][0].cpu().numpy()
@@ -122,6 +126,29 @@ def _refine_and_save(args, model, points, centered_mesh, original_center, scan_n
     joints = (prm["joints"][0].cpu().numpy() + trans) * scale
     np.savez(os.path.join(args.output_folder, f"{scan_name}_output_smpl_info.npz"), body_pose=body[:21], hand_pose=body[21:23],
              betas=prm["beta"][0].cpu().numpy(), global_orient=pose[:3], transl=trans, scale=scale, joints=joints)
+
+
+def resolve_body_model(args):
+    """--synthetic_body / --body_model -> args.body_model (a BodyModel, or None = the reference's gender paths)."""
+    if args.synthetic_body:
+        from .utils.body_model import SyntheticSMPL
+        args.body_model = SyntheticSMPL(7)
+    elif args.body_model:
+        from .utils.body_model import load_smpl_pkl, load_smplx
+        # an SMPL-X model file (SMPLX_*.npz / .pkl) selects the 55-joint, 20-coefficient fit; anything else is read as an SMPL pickle
+        args.body_model = load_smplx(args.body_model) if "smplx" in os.path.basename(args.body_model).lower() else load_smpl_pkl(args.body_model)
+    else:
+        args.body_model = None
+
+
+def _ingest_device(args):
+    """--ingest device: preprocess_scan and sample_points_from_mesh on the native path -> (points (1,N,3) float32 on the device, the centred
+    mesh, the centre)."""
+    from . import mesh_io
+    scan_mesh = mesh_io.read_obj(args.scan_path)
+    points, _, center = mesh_io.sample_surface([scan_mesh], args.num_point, [args.seed], center=True, device=args.device)
+    center = center[0].cpu().numpy()
+    return points, Mesh(scan_mesh.vertices - center, scan_mesh.faces), center
 
 
 def main(argv=None):
@@ -136,28 +163,26 @@ def main(argv=None):
     else:
         from . import constants
         args.markerset = constants.default_markerset()
-    if args.synthetic_body:
-        from .utils.body_model import SyntheticSMPL
-        args.body_model = SyntheticSMPL(7)
-    elif args.body_model:
-        from .utils.body_model import load_smpl_pkl, load_smplx
-        # an SMPL-X model file (SMPLX_*.npz / .pkl) selects the 55-joint, 20-coefficient fit; anything else is read as an SMPL pickle
-        args.body_model = load_smplx(args.body_model) if "smplx" in os.path.basename(args.body_model).lower() else load_smpl_pkl(args.body_model)
-    else:
-        args.body_model = None
+    resolve_body_model(args)
     os.makedirs(args.output_folder, exist_ok=True)
     model = load_model(args)
-    centered_mesh, original_center = preprocess_scan(args.scan_path)
-    points = sample_points_from_mesh(centered_mesh, args.num_point, args.seed)
+    export = Mesh.export
+    if getattr(args, "ingest", "host") == "device":
+        from .mesh_io import write_obj as export
+        points_tensor, centered_mesh, original_center = _ingest_device(args)
+        points = points_tensor[0].cpu().numpy()
+    else:
+        centered_mesh, original_center = preprocess_scan(args.scan_path)
+        points = sample_points_from_mesh(centered_mesh, args.num_point, args.seed)
     scan_name = os.path.splitext(os.path.basename(args.scan_path))[0]
     if args.chamfer_refine != "none":
-        _refine_and_save(args, model, points, centered_mesh, original_center, scan_name)
+        _refine_and_save(args, model, points, centered_mesh, original_center, scan_name, export)
         print(f"Predicted SMPL mesh and smpl info saved under {args.output_folder}")
         return
     pred_smpl_mesh, smpl_info = predict_smpl(args, model, points, args.gender)
     final = pred_smpl_mesh.copy()
     final.vertices = pred_smpl_mesh.vertices + original_center
-    final.export(os.path.join(args.output_folder, f"{scan_name}_pred_smpl.obj"))
+    export(final, os.path.join(args.output_folder, f"{scan_name}_pred_smpl.obj"))
     np.savez(os.path.join(args.output_folder, f"{scan_name}_output_smpl_info.npz"), body_pose=smpl_info[0][0, :21, :],
              hand_pose=smpl_info[0][0, 21:23, :], betas=smpl_info[1][0], global_orient=smpl_info[2][0], transl=smpl_info[3][0],
              joints=smpl_info[4][0])

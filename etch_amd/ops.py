@@ -1450,3 +1450,36 @@ def guarded_adam_step(T, C, chunk_tensor, first_chunk, numel, pmv, grads, status
     _lib.check(_lib.lib().etch_guarded_adam_step(int(T), int(C), _ptr(chunk_tensor), _ptr(first_chunk), _ptr(numel), _ptr(pmv), _ptr(grads), _optptr(status),
                                                  _ptr(steps), _ptr(chunkflags), ctypes.c_double(lr), ctypes.c_double(betas[0]), ctypes.c_double(betas[1]),
                                                  ctypes.c_double(eps), _ptr(counters), _stream()), "etch_guarded_adam_step")
+
+
+# ------------------------------------------------------------------ scan ingestion (csrc/mesh_sample.hip)
+def bbox_center(verts, vert_offsets):
+    """(min + max) / 2 per scan: verts (sum V,3) fp64 concatenated, vert_offsets (B+1) int32 -> (B,3) fp64."""
+    _need(verts, torch.float64, "verts"), _need(vert_offsets, torch.int32, "vert_offsets")
+    B = vert_offsets.numel() - 1
+    center = torch.empty((B, 3), dtype=torch.float64, device=verts.device)
+    _lib.check(_lib.lib().etch_bbox_center(int(B), _ptr(verts), _ptr(vert_offsets), _ptr(center), _stream()), "etch_bbox_center")
+    return center
+
+
+def sample_surface(verts, faces, vert_offsets, face_offsets, keys, num_points, total_faces, max_faces, center=None, want_fp64=False):
+    """etch_sample_surface on a packed ragged batch: verts (sum V,3) fp64, faces (sum F,3) int32 local to their scan and ALREADY VALIDATED,
+    vert_offsets / face_offsets (B+1) int32, keys (B) int64 holding the uint64 bits, center (B,3) fp64 or None; total_faces and max_faces are
+    the host's copies of face_offsets[B] and the largest face count.  -> points (B,N,3) fp32, points64 (B,N,3) fp64 or None, face (B,N) int32,
+    status (B) int32 (ETCH_SAMPLE_STATUS_* bits, still on the device)."""
+    _need(verts, torch.float64, "verts"), _need(faces, torch.int32, "faces"), _need(keys, torch.int64, "keys")
+    _need(vert_offsets, torch.int32, "vert_offsets"), _need(face_offsets, torch.int32, "face_offsets")
+    B, N, dev = keys.numel(), int(num_points), verts.device
+    if vert_offsets.numel() != B + 1 or face_offsets.numel() != B + 1 or faces.shape != (total_faces, 3) or N < 0:
+        raise _lib.EtchHipError("sample_surface: offsets must be (B+1), faces (total_faces,3) and num_points >= 0")
+    if center is not None and _need(center, torch.float64, "center").shape != (B, 3):
+        raise _lib.EtchHipError(f"center must be ({B},3)")
+    ws = _mesh_workspace(_lib.lib().etch_sample_surface_workspace, B, total_faces, dev)
+    p32 = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
+    p64 = torch.empty((B, N, 3), dtype=torch.float64, device=dev) if want_fp64 else None
+    face = torch.empty((B, N), dtype=torch.int32, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().etch_sample_surface(int(B), N, int(total_faces), int(max_faces), _ptr(verts), _ptr(faces), _ptr(vert_offsets), _ptr(face_offsets),
+                                              _ptr(keys), _optptr(center), _ptr(ws), _ptr(p32), _optptr(p64), _ptr(face), _ptr(status), _stream()),
+               "etch_sample_surface")
+    return p32, p64, face, status
