@@ -23,6 +23,7 @@ struct GemmArgs {
     int act;            // 0 none, 1 relu, 2 leaky_relu(0.01)
     const float* res; long ldr; int res_mode;   // 0 none, 1 add before act, 2 add after act
     float* Y; long ldy;
+    double* stat;       // gemm_ws_split_kernel<STATS>: [sample][workgroup][2][O] sums and sums of squares of Y
 };
 
 #define G_BM 64
@@ -44,7 +45,10 @@ __device__ __forceinline__ float4 ld4_guard(const float* row, int k, int K, bool
     return v;
 }
 
-template <bool VECX, bool VECW, int BN, int BM = 64, int WAVES = 4>   // block tile BM rows x BN outputs, WAVES waves (2 along M)
+// STATS (the strided skip conv of etch_linear_stats): blockIdx.z = sample, R = the rows of ONE sample (a tile never straddles two samples), every lane adds
+// the values it stores and their squares in fp64 and the workgroup writes one [2][O] partial per 64-row tile (a.stat: [sample][tile][2][O]), lane groups and
+// waves summed in a fixed order through LDS.  Y is bitwise what the plain kernel writes for the same rows: a row's MFMA chain does not depend on its tile.
+template <bool VECX, bool VECW, int BN, int BM = 64, int WAVES = 4, bool STATS = false>   // block tile BM rows x BN outputs, WAVES waves (2 along M)
 __global__ void __launch_bounds__(WAVES * 64) gemm_nt_kernel(GemmArgs a) {
     constexpr int THREADS = WAVES * 64;
     constexpr int NWN = WAVES / 2;             // waves along the output dimension
@@ -60,6 +64,7 @@ __global__ void __launch_bounds__(WAVES * 64) gemm_nt_kernel(GemmArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r0 = blockIdx.x * BM, o0 = blockIdx.y * BN;
     const int wm = wave / NWN, wn = wave % NWN;
+    const int rbase = STATS ? blockIdx.z * a.R : 0;      // first global row of this sample
     // staging coordinates: thread -> (row = tid/8 [+RPP*h], float4 column = tid%8)
     const int srow = tid >> 3, sc4 = (tid & 7) * 4;
     const float* xrow[XL];
@@ -72,10 +77,11 @@ __global__ void __launch_bounds__(WAVES * 64) gemm_nt_kernel(GemmArgs a) {
         xok[h] = r < a.R;
         long src = 0;
         if (xok[h]) {
-            src = r;
+            const int rg = rbase + r;
+            src = rg;
             if (a.row_idx) {
-                const int q = r / a.grp;
-                src = ((long)(q / a.p_out) * a.p_in + a.row_idx[q]) * a.grp + (r - q * a.grp);
+                const int q = rg / a.grp;
+                src = ((long)(q / a.p_out) * a.p_in + a.row_idx[q]) * a.grp + (rg - q * a.grp);
             }
         }
         xrow[h] = a.X + src * a.ldx;
@@ -128,6 +134,9 @@ __global__ void __launch_bounds__(WAVES * 64) gemm_nt_kernel(GemmArgs a) {
         }
     }
     // epilogue: D[row = fg*4 + reg][col = fr]
+    double st_s[NJ], st_q[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) st_s[j] = st_q[j] = 0.0;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         const int o = o0 + wn * WNS + j * 16 + fr;
@@ -147,8 +156,35 @@ __global__ void __launch_bounds__(WAVES * 64) gemm_nt_kernel(GemmArgs a) {
                 if (a.act == 1) v = fmaxf(v, 0.f);
                 else if (a.act == 2) v = v > 0.f ? v : 0.01f * v;
                 if (a.res_mode == 2) v += a.res[(long)r * a.ldr + o];
-                a.Y[(long)r * a.ldy + o] = v;
+                a.Y[(long)(rbase + r) * a.ldy + o] = v;
+                if constexpr (STATS) { st_s[j] += (double)v; st_q[j] += (double)v * (double)v; }
             }
+    }
+    if constexpr (STATS) {
+        // channel c of the tile = 16 (NJ wn + j) + fr sits in lanes 16 fg + fr of the waves wm NWN + wn: summed wm-major, fg ascending.  The X tile's LDS
+        // (its last readers pass the barrier below) holds [2][waves][64 lanes][NJ] doubles.
+        static_assert(2 * WAVES * 64 * NJ * sizeof(double) <= BM * G_LD * sizeof(float), "the statistics reduction reuses the X tile");
+        double* red = reinterpret_cast<double*>(Xs);
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            red[(wave * 64 + lane) * NJ + j] = st_s[j];
+            red[WAVES * 64 * NJ + (wave * 64 + lane) * NJ + j] = st_q[j];
+        }
+        __syncthreads();
+        if (tid < BN && o0 + tid < a.O) {
+            const int wnc = tid / WNS, j = (tid % WNS) >> 4, f = tid & 15;
+            double ts = 0.0, tq = 0.0;
+            for (int m = 0; m < 2; ++m)
+                for (int g = 0; g < 4; ++g) {
+                    const int e = ((m * NWN + wnc) * 64 + g * 16 + f) * NJ + j;
+                    ts += red[e];
+                    tq += red[WAVES * 64 * NJ + e];
+                }
+            double* dst = a.stat + ((size_t)blockIdx.z * gridDim.x + blockIdx.x) * 2 * a.O + o0 + tid;
+            dst[0] = ts;
+            dst[a.O] = tq;
+        }
     }
 }
 
@@ -339,8 +375,12 @@ __device__ __forceinline__ void g_split8(const float4 v0, const float4 v1, g_bf1
 // features, trained weights): every row of X is staged times the power of two that puts its maximum into [8, 16) (its K / 4 float4s sit in one aligned
 // lane group: DPP maximum, no barrier), every ROW of W (output channel) likewise, once per workgroup; both powers leave in the epilogue's
 // first fmaf (exact).  Opt-in (ETCH_LINEAR_SPLIT=f16): see the dispatch in etch_linear.
-template <int K, int SPW, int RP, bool F16 = false>
+// STATS (the encoder's stride-1 skip convs, etch_linear_stats): grid (workgroups, samples), R = the rows of ONE sample, so a workgroup never straddles two
+// samples; every lane adds the values it stores, and their squares, in fp64 and the workgroup
+// writes one [2][O] partial (lanes and waves summed in a fixed order through LDS): the InstanceNorm statistics of Y without a second pass over it.
+template <int K, int SPW, int RP, bool F16 = false, bool STATS = false>
 __global__ void __launch_bounds__(512) gemm_ws_split_kernel(GemmArgs a, long rows_per_block) {
+    static_assert(!STATS || (SPW == 1 && !F16), "the statistics epilogue covers the one-strip three-plane shapes");
     constexpr int FD_ROWS = 64, SB = K + 8, KT = K / 32, PLANE = FD_ROWS * SB;
     constexpr int NPL = F16 ? 2 : 3;
     constexpr int SG = 8 / RP;                    // strip groups (waves along the output channels)
@@ -352,6 +392,14 @@ __global__ void __launch_bounds__(512) gemm_ws_split_kernel(GemmArgs a, long row
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 15, fg = lane >> 4;
     const int sg = wave % SG, rp = wave / SG;
+    const float* Xb = a.X;
+    float* Yb = a.Y;
+    double st_s[4] = {0.0, 0.0, 0.0, 0.0}, st_q[4] = {0.0, 0.0, 0.0, 0.0};
+    if constexpr (STATS) {
+        const long smp = blockIdx.y;
+        Yb += smp * a.R * a.ldy;
+        Xb += smp * a.R * a.ldx;
+    }
     // this wave's weight fragments: strips SPW sg .. + SPW - 1, rows (output channels) 16 strip + fr, k = 32 t + 8 fg + e
     g_bf16x8 wf[KT][SPW][NPL];
     float4 wk4[SPW];                              // F16: 2^-kw of this lane's four output channels (rows 4 fg .. of the strip)
@@ -417,7 +465,7 @@ __global__ void __launch_bounds__(512) gemm_ws_split_kernel(GemmArgs a, long row
     constexpr int RSTEP = 512 / C4;
     const int row0 = tid / C4, c0 = (tid % C4) * 4;
     auto fetch = [&](long r0) {
-        const float* src = a.X + (r0 + row0) * a.ldx + c0;
+        const float* src = Xb + (r0 + row0) * a.ldx + c0;
 #pragma unroll
         for (int h = 0; h < XL; ++h) {
             xn[h] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -494,7 +542,11 @@ __global__ void __launch_bounds__(512) gemm_ws_split_kernel(GemmArgs a, long row
                 if (a.act == 1) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
                 else if (a.act == 2) { v.x = v.x > 0.f ? v.x : 0.01f * v.x; v.y = v.y > 0.f ? v.y : 0.01f * v.y; v.z = v.z > 0.f ? v.z : 0.01f * v.z; v.w = v.w > 0.f ? v.w : 0.01f * v.w; }
                 if (a.res_mode == 2) { v.x += rs.x; v.y += rs.y; v.z += rs.z; v.w += rs.w; }
-                *reinterpret_cast<float4*>(a.Y + r * a.ldy + o) = v;
+                *reinterpret_cast<float4*>(Yb + r * a.ldy + o) = v;
+                if constexpr (STATS) {
+                    st_s[0] += (double)v.x; st_q[0] += (double)v.x * (double)v.x; st_s[1] += (double)v.y; st_q[1] += (double)v.y * (double)v.y;
+                    st_s[2] += (double)v.z; st_q[2] += (double)v.z * (double)v.z; st_s[3] += (double)v.w; st_q[3] += (double)v.w * (double)v.w;
+                }
             }
         }
     };
@@ -517,6 +569,26 @@ __global__ void __launch_bounds__(512) gemm_ws_split_kernel(GemmArgs a, long row
         for (int i = 1; i < RTW; ++i) row_tile(P, rp * RTW + i, r0, rsc + buf * FD_ROWS);
         if constexpr (!EPI_REGS) fetch(r0 + 2 * FD_ROWS);      // register-bound shape: the prefetch registers are not live across the row tiles
         __syncthreads();
+    }
+    if constexpr (STATS) {
+        // the planes' last readers passed the loop's closing barrier: their LDS (>= 30 KB) holds [8 waves][64 lanes][4] doubles (16 KB), sums first, squares second.
+        // Channel c = 16 sg + 4 fg + j sits in lanes 16 fg + fr (fr = the 16 rows of a row tile) of the RP waves rp SG + sg: summed rp-major, fr ascending.
+        constexpr int O = 16 * SPW * SG;
+        double* red = reinterpret_cast<double*>(lds);
+#pragma unroll
+        for (int which = 0; which < 2; ++which) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) red[(wave * 64 + lane) * 4 + j] = which ? st_q[j] : st_s[j];
+            __syncthreads();
+            if (tid < O) {
+                const int sgc = tid >> 4, fgc = (tid & 15) >> 2, j = tid & 3;
+                double t = 0.0;
+                for (int rpi = 0; rpi < RP; ++rpi)
+                    for (int f = 0; f < 16; ++f) t += red[((rpi * SG + sgc) * 64 + fgc * 16 + f) * 4 + j];
+                a.stat[(((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2 + which) * O + tid] = t;
+            }
+            __syncthreads();
+        }
     }
 }
 
@@ -546,6 +618,66 @@ static int launch_ws_split(const GemmArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(512), lds, st, a, rpb);
     ETCH_RETURN_IF_LAUNCH_FAILED();
     return ETCH_OK;
+}
+
+// Rows of one sample per workgroup of the statistics form: a function of the sample's own row count only -- at most 64 workgroups per sample, whole
+// 64-row tiles, at least GEMM_WS_MIN_TILES of them -- never of the batch size or of the chip (the partition fixes the order of the fp64 sums: a scan's
+// statistics may not depend on its batch neighbours or on the part it runs on).
+static long ws_stats_rows_per_block(long rows) {
+    const long tiles = (rows + 63) / 64;
+    long tpb = (tiles + 63) / 64;
+    if (tpb < GEMM_WS_MIN_TILES) tpb = GEMM_WS_MIN_TILES;
+    return tpb * 64;
+}
+
+template <int K, int SPW, int RP>
+static int launch_ws_stats(const GemmArgs& a, int b, hipStream_t st) {
+    const size_t lds = (size_t)2 * 3 * 64 * (K + 8) * 2 + (size_t)2 * 64 * sizeof(float) + (size_t)8 * SPW * 16 * sizeof(float);
+    static_assert(2 * 3 * 64 * (K + 8) * 2 >= 8 * 64 * 4 * 8, "the statistics reduction reuses the planes' LDS");
+    const long rpb = ws_stats_rows_per_block(a.R);
+    const long nb = (a.R + rpb - 1) / rpb;
+    hipLaunchKernelGGL((gemm_ws_split_kernel<K, SPW, RP, false, true>), dim3((unsigned)nb, (unsigned)b), dim3(512), lds, st, a, rpb);
+    ETCH_RETURN_IF_LAUNCH_FAILED();
+    return ETCH_OK;
+}
+
+extern "C" int etch_instnorm_from_partials_n(int b, int nparts, int C, long total, const double* partial, float* mean, float* rstd, int wide, void* stream);
+
+// strided != 0: the form with a row map, which stays on the fp32 MFMA tile kernel (one part per 64-row tile)
+extern "C" int etch_linear_stats_rows_per_part(int rows, int strided) { return rows <= 0 ? 0 : strided ? G_BM : (int)ws_stats_rows_per_block(rows); }
+
+extern "C" int etch_linear_stats_parts(int rows, int strided) {
+    if (rows <= 0) return 0;
+    const long rpb = etch_linear_stats_rows_per_part(rows, strided);
+    return (int)((rows + rpb - 1) / rpb);
+}
+
+// Y[s][r] = X[rowmap(s, r)] W^T + bias for b samples of `rows` rows each (X, Y contiguous over the samples; with row_idx: rows = p_out * grp and sample
+// s reads source row (s p_in + row_idx[s p_out + r / grp]) grp + r % grp), and mean / rstd [b][O] of Y per (sample, channel): InstanceNorm2d(affine =
+// False, eps 1e-5).  partial: etch_linear_stats_parts(rows) * b * 2 * O doubles.  (K, O) in {(32, 32), (64, 64), (32, 64)}: the encoder's skip convs.
+extern "C" int etch_linear_stats(int b, int rows, int K, int O, const float* X, long ldx, const int* row_idx, int grp, int p_in, int p_out,
+                                 const float* W, long ldw, const float* bias, float* Y, long ldy, double* partial, float* mean, float* rstd, void* stream) {
+    if (b <= 0 || rows <= 0) return ETCH_OK;
+    if (!X || !W || !Y || !partial || !mean || !rstd) return ETCH_EINVAL;
+    if (row_idx && (grp <= 0 || p_out <= 0 || p_in <= 0 || (long)p_out * grp != rows)) return ETCH_EINVAL;
+    if (b > 65535 || (K & 3) || (ldx & 3) || (ldw & 3) || (ldy & 3) || (((uintptr_t)X | (uintptr_t)W | (uintptr_t)Y | (uintptr_t)partial) & 15)) return ETCH_EUNSUPPORTED;
+    if ((long)b * rows > 0x7fffffffL) return ETCH_EUNSUPPORTED;
+    GemmArgs a{rows, K, O, X, ldx, row_idx, grp, p_in, p_out, W, ldw, bias, nullptr, nullptr, 0, nullptr, 0, 0, Y, ldy, partial};
+    hipStream_t st = (hipStream_t)stream;
+    int rc = ETCH_EUNSUPPORTED;
+    if (row_idx) {
+        // a row map: etch_linear takes the fp32 MFMA tile kernel for it, and so does this entry -- Y keeps etch_linear's bits (the three-plane kernel's
+        // product differs from it by fp32 rounding, which the marker fit downstream does not damp)
+        if (K == 32 && O == 64) {
+            hipLaunchKernelGGL((gemm_nt_kernel<true, true, 64, 64, 4, true>), dim3((unsigned)((rows + G_BM - 1) / G_BM), 1, (unsigned)b), dim3(256), 0, st, a);
+            ETCH_RETURN_IF_LAUNCH_FAILED();
+            rc = ETCH_OK;
+        }
+    } else if (K == 32 && O == 32) rc = launch_ws_stats<32, 1, 4>(a, b, st);
+    else if (K == 64 && O == 64) rc = launch_ws_stats<64, 1, 2>(a, b, st);
+    else if (K == 32 && O == 64) rc = launch_ws_stats<32, 1, 2>(a, b, st);
+    if (rc != ETCH_OK) return rc;
+    return etch_instnorm_from_partials_n(b, etch_linear_stats_parts(rows, row_idx != nullptr), O, (long)rows, partial, mean, rstd, 1, stream);
 }
 
 extern "C" int etch_linear(int R, int K, int O, const float* X, long ldx, const int* row_idx, int grp, int p_in, int p_out,

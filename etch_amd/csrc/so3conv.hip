@@ -14,6 +14,8 @@
 //                        (/root/reference/src/models/so3conv.py:36-44,96-99,178-182).
 #include "common.h"
 #include "split_bf16.h"
+#include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -884,7 +886,16 @@ __global__ void instnorm_final_kernel(int rows, int C, float eps, const double* 
 
 // mean / rstd from per-workgroup partial sums written by the fused inter conv: part [b][nparts][2][C] (sum, sum of squares over
 // `count` values each) -> the same statistics as instnorm_partial/final over nparts * count values; fp64 accumulation in a fixed order
-__global__ void __launch_bounds__(1024) instnorm_from_partials_kernel(int nparts, int C, int count, float eps, const double* __restrict__ part,
+// (n = the number of values per (sample, channel); the tail is shared with the wide form below so that both round alike)
+__device__ __forceinline__ void instnorm_finish(double a, double d, double n, float eps, float* __restrict__ mean, float* __restrict__ rstd) {
+    const double m = a / n;
+    double var = d / n - m * m;
+    if (var < 0.0) var = 0.0;
+    *mean = (float)m;
+    *rstd = (float)(1.0 / sqrt(var + (double)eps));
+}
+
+__global__ void __launch_bounds__(1024) instnorm_from_partials_kernel(int nparts, int C, double n, float eps, const double* __restrict__ part,
                                                                       float* __restrict__ mean, float* __restrict__ rstd) {
     __shared__ double red[2][1024];
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -907,12 +918,37 @@ __global__ void __launch_bounds__(1024) instnorm_from_partials_kernel(int nparts
         if (sl == 0) {
             double a = s[j], d = q[j];
             for (int k = 1; k < nsl; ++k) { a += red[0][k * c4 + cq]; d += red[1][k * c4 + cq]; }
-            const double n = (double)nparts * count, m = a / n;
-            double var = d / n - m * m;
-            if (var < 0.0) var = 0.0;
-            mean[(size_t)b * C + cq * 4 + j] = (float)m;
-            rstd[(size_t)b * C + cq * 4 + j] = (float)(1.0 / sqrt(var + (double)eps));
+            instnorm_finish(a, d, n, eps, mean + (size_t)b * C + cq * 4 + j, rstd + (size_t)b * C + cq * 4 + j);
         }
+    }
+}
+
+// The same finalisation across the chip: one workgroup per (channel quad, sample) instead of one per sample.  The one-workgroup form spends its
+// time in the four serial passes of 1024 / (C / 4) LDS reads that 1024 - C / 4 of its threads wait for (31 us on a dependent chain, eight times per
+// step); here a workgroup holds ONE quad, its 1024 / (C / 4) threads are the same slices (k = sl, sl + nsl, ... with the same nsl), and the four
+// channels' final sums run side by side in four threads, each in the same order k = 0 .. nsl - 1: every addition has the same operands, the result
+// is bitwise the one-workgroup form's.  n = the true number of values per (sample, channel) (the producers' last part may be ragged).
+__global__ void __launch_bounds__(256) instnorm_from_partials_wide_kernel(int nparts, int C, double n, float eps, const double* __restrict__ part,
+                                                                           float* __restrict__ mean, float* __restrict__ rstd) {
+    __shared__ double red[2][4][256];
+    const int b = blockIdx.y, cq = blockIdx.x, sl = threadIdx.x, nsl = blockDim.x;
+    double s[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
+    const double* pb = part + (size_t)b * nparts * 2 * C;
+    for (int k = sl; k < nparts; k += nsl) {
+        const double2* u = reinterpret_cast<const double2*>(pb + (size_t)k * 2 * C + cq * 4);
+        const double2* v = reinterpret_cast<const double2*>(pb + (size_t)k * 2 * C + C + cq * 4);
+        const double2 u0 = u[0], u1 = u[1], v0 = v[0], v1 = v[1];
+        s[0] += u0.x; s[1] += u0.y; s[2] += u1.x; s[3] += u1.y;
+        q[0] += v0.x; q[1] += v0.y; q[2] += v1.x; q[3] += v1.y;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { red[0][j][sl] = s[j]; red[1][j][sl] = q[j]; }
+    __syncthreads();
+    if (sl < 4) {
+        const int j = sl;
+        double a = red[0][j][0], d = red[1][j][0];
+        for (int k = 1; k < nsl; ++k) { a += red[0][j][k]; d += red[1][j][k]; }
+        instnorm_finish(a, d, n, eps, mean + (size_t)b * C + cq * 4 + j, rstd + (size_t)b * C + cq * 4 + j);
     }
 }
 
@@ -988,6 +1024,72 @@ __global__ void __launch_bounds__(256) instnorm_act_add_kernel(unsigned per4, in
         one(i + stride, vb, wb);
     }
     if (i < per4) one(i, X1[i], X2 ? X2[i] : z4);
+}
+
+// The final pass of the block whose output feeds the heads: the same `out`, plus the mean over each point's NA anchor rows (mean [b * p][C]), which the
+// heads' 3-NN blend reads -- token_mean_kernel re-read the whole tensor (0.61 GB at 32 x 5 000 points) for it.  A workgroup takes whole points; thread t
+// handles the point's float4 numbers t, t + 256, ... (anchor a0 + k AP of channel quad c4: token_mean_kernel's assignment), adds them in that order,
+// the partial sums cross LDS and are summed k = 0 .. AP - 1 as there: `mean` is bitwise token_mean_kernel's of `out`, `out` bitwise the plain kernel's
+// (the same expressions on the same operands).
+template <int C>
+__global__ void __launch_bounds__(256) instnorm_act_add_mean_kernel(int p, const float* __restrict__ x1, const float* __restrict__ m1,
+                                                                    const float* __restrict__ r1, const float* __restrict__ x2,
+                                                                    const float* __restrict__ m2, const float* __restrict__ r2,
+                                                                    float* __restrict__ out, float* __restrict__ mean) {
+    constexpr int C4 = C / 4, AP = 256 / C4, NIT = (NA + AP - 1) / AP, U = NIT < 4 ? NIT : 4;
+    __shared__ float4 part2[2][256];      // alternating per point: one barrier per point (a buffer's readers are done two barriers before it is written again)
+    const int b = blockIdx.y, tid = threadIdx.x, c4 = tid % C4, a0 = tid / C4;
+    int pb = 0;
+    const size_t base4 = (size_t)b * p * NA * C4;
+    const float4* X1 = reinterpret_cast<const float4*>(x1) + base4;
+    const float4* X2 = x2 ? reinterpret_cast<const float4*>(x2) + base4 : nullptr;
+    float4* O = reinterpret_cast<float4*>(out) + base4;
+    const float4 m = *reinterpret_cast<const float4*>(m1 + (size_t)b * C + c4 * 4);
+    const float4 r = *reinterpret_cast<const float4*>(r1 + (size_t)b * C + c4 * 4);
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 mm = X2 ? *reinterpret_cast<const float4*>(m2 + (size_t)b * C + c4 * 4) : z4;
+    const float4 rr = X2 ? *reinterpret_cast<const float4*>(r2 + (size_t)b * C + c4 * 4) : z4;
+    for (int pt = blockIdx.x; pt < p; pt += gridDim.x) {
+        const unsigned i0 = (unsigned)pt * (NA * C4) + tid;          // < 2^30 (checked by the launcher)
+        float4 acc = z4;
+#pragma unroll
+        for (int g = 0; g < NIT; g += U) {
+            float4 v[U], w[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {                             // every load of the group in flight before the first use
+                const bool ok = g + u < NIT && a0 + (g + u) * AP < NA;
+                v[u] = ok ? X1[i0 + (g + u) * 256] : z4;
+                w[u] = ok && X2 ? X2[i0 + (g + u) * 256] : z4;
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (!(g + u < NIT && a0 + (g + u) * AP < NA)) continue;
+                float o[4] = {(v[u].x - m.x) * r.x, (v[u].y - m.y) * r.y, (v[u].z - m.z) * r.z, (v[u].w - m.w) * r.w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) o[k] = o[k] > 0.f ? o[k] : 0.01f * o[k];
+                if (X2) {
+                    float o2[4] = {(w[u].x - mm.x) * rr.x, (w[u].y - mm.y) * rr.y, (w[u].z - mm.z) * rr.z, (w[u].w - mm.w) * rr.w};
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) o[k] += o2[k] > 0.f ? o2[k] : 0.01f * o2[k];
+                }
+                O[i0 + (g + u) * 256] = make_float4(o[0], o[1], o[2], o[3]);
+                acc.x += o[0]; acc.y += o[1]; acc.z += o[2]; acc.w += o[3];
+            }
+        }
+        float4* part = part2[pb];
+        pb ^= 1;
+        part[tid] = acc;
+        __syncthreads();
+        if (tid < C4) {
+            float4 t = part[tid];
+            for (int k = 1; k < AP; ++k) {
+                const float4 u = part[k * C4 + tid];
+                t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w;
+            }
+            const float ia = 1.0f / (float)NA;
+            reinterpret_cast<float4*>(mean + ((size_t)b * p + pt) * C)[tid] = make_float4(t.x * ia, t.y * ia, t.z * ia, t.w * ia);
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ C ABI
@@ -1156,12 +1258,24 @@ int etch_instnorm_stats(int b, int rows, int C, const float* x, double* workspac
     return ETCH_OK;
 }
 
-int etch_instnorm_from_partials(int b, int nparts, int C, int count, const double* partial, float* mean, float* rstd, void* stream) {
+// total = the number of values per (sample, channel) the partials sum over.  wide != 0: one workgroup per channel quad (C >= 16, b <= 65535;
+// otherwise, and with wide == 0, the one-workgroup form); both give the same bits.
+int etch_instnorm_from_partials_n(int b, int nparts, int C, long total, const double* partial, float* mean, float* rstd, int wide, void* stream) {
     if (b <= 0) return ETCH_OK;
-    if (C < 4 || C > 256 || (C & 3) || (1024 % (C >> 2)) != 0 || nparts <= 0 || count <= 0 || ((uintptr_t)partial & 15)) return ETCH_EUNSUPPORTED;
-    hipLaunchKernelGGL(instnorm_from_partials_kernel, dim3(b), dim3(1024), 0, (hipStream_t)stream, nparts, C, count, 1e-5f, partial, mean, rstd);
+    if (C < 4 || C > 256 || (C & 3) || (1024 % (C >> 2)) != 0 || nparts <= 0 || total <= 0 || ((uintptr_t)partial & 15)) return ETCH_EUNSUPPORTED;
+    if (wide && C >= 16 && b <= 65535)
+        hipLaunchKernelGGL(instnorm_from_partials_wide_kernel, dim3(C >> 2, b), dim3(1024 / (C >> 2)), 0, (hipStream_t)stream, nparts, C, (double)total, 1e-5f,
+                           partial, mean, rstd);
+    else
+        hipLaunchKernelGGL(instnorm_from_partials_kernel, dim3(b), dim3(1024), 0, (hipStream_t)stream, nparts, C, (double)total, 1e-5f, partial, mean, rstd);
     ETCH_RETURN_IF_LAUNCH_FAILED();
     return ETCH_OK;
+}
+
+int etch_instnorm_from_partials(int b, int nparts, int C, int count, const double* partial, float* mean, float* rstd, void* stream) {
+    if (count <= 0) return b <= 0 ? ETCH_OK : ETCH_EUNSUPPORTED;
+    static const bool wide = !(getenv("ETCH_INSTNORM_WIDE") != nullptr && !strcmp(getenv("ETCH_INSTNORM_WIDE"), "0"));     // A/B switch: 0 = one workgroup per sample
+    return etch_instnorm_from_partials_n(b, nparts, C, (long)nparts * count, partial, mean, rstd, wide ? 1 : 0, stream);
 }
 
 int etch_instnorm_stats_workspace_bytes(int b, int C) { return (int)((size_t)IN_CHUNKS * b * 2 * C * sizeof(double)); }
@@ -1208,6 +1322,26 @@ int etch_instnorm_act_add_planes_f16(int b, int rows, int C, const float* x1, co
 int etch_instnorm_act_add_k1_planes_f16(int b, int rows, int C, const float* x1, const float* m1, const float* r1, const float* f, const float* slope,
                                         const float* offset, float* out, void* planes, void* stream) {
     return instnorm_act_add_launch(true, b, rows, C, x1, m1, r1, f, slope, offset, out, planes, stream, true);
+}
+
+// x1 / x2 / out (b, p, 60, C); mean (b * p, C) = the mean of out over each point's 60 anchor rows (what etch_token_mean gives on out).  C in {32, 64, 128, 256};
+// other widths: ETCH_EUNSUPPORTED (the caller runs etch_instnorm_act_add + etch_token_mean).
+int etch_instnorm_act_add_mean(int b, int p, int C, const float* x1, const float* m1, const float* r1, const float* x2, const float* m2, const float* r2,
+                               float* out, float* mean, void* stream) {
+    if (b <= 0 || p <= 0) return ETCH_OK;
+    if (!x1 || !m1 || !r1 || !out || !mean || (x2 && (!m2 || !r2))) return ETCH_EINVAL;
+    if ((long)p * NA * C / 4 >= (1L << 30) || b > 65535) return ETCH_EUNSUPPORTED;      // 32-bit element indices inside a sample
+    if (((uintptr_t)x1 | (uintptr_t)x2 | (uintptr_t)out | (uintptr_t)mean | (uintptr_t)m1 | (uintptr_t)r1 | (uintptr_t)m2 | (uintptr_t)r2) & 15) return ETCH_EUNSUPPORTED;
+    long bx = p;
+    const long cap = (256L * 16 + b - 1) / b;
+    if (bx > cap) bx = cap;
+    const dim3 grid((unsigned)bx, (unsigned)b);
+    hipStream_t st = (hipStream_t)stream;
+#define INAM_CASE(CC) if (C == CC) hipLaunchKernelGGL((instnorm_act_add_mean_kernel<CC>), grid, dim3(256), 0, st, p, x1, m1, r1, x2, m2, r2, out, mean); else
+    INAM_CASE(32) INAM_CASE(64) INAM_CASE(128) INAM_CASE(256) return ETCH_EUNSUPPORTED;
+#undef INAM_CASE
+    ETCH_RETURN_IF_LAUNCH_FAILED();
+    return ETCH_OK;
 }
 
 int etch_instnorm_act_add(int b, int rows, int C, const float* x1, const float* m1, const float* r1, const float* x2,

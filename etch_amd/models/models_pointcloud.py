@@ -433,7 +433,9 @@ class GT_network_equiv(nn.Module):
             # it start ~1 ms earlier); the equivariant tokens themselves are blended inside the first attention layer
             idx3, w3 = ops.prop3nn(hitpts, r.xyz)
             Bc, S, na, C = r.feats_cl.shape
-            cmean = ops.token_mean(r.feats_cl.view(Bc * S, na, C))
+            cmean = getattr(r, "anchor_mean", None)       # written by the encoder's last final pass (etch_instnorm_act_add_mean)
+            if cmean is None:
+                cmean = ops.token_mean(r.feats_cl.view(Bc * S, na, C))
             _, point_inv_feat = ops.prop_interp(cmean.view(Bc, S, 1, C), idx3, w3, order=order)
             point_equiv_cl, interp = None, (r.feats_cl, idx3, w3, order)
         else:

@@ -109,6 +109,10 @@ class SeparableSO3ConvBlock(nn.Module):
 
     fold_k1_skip = os.environ.get("ETCH_SKIP_K1_FOLD", "1") != "0"     # one input channel: the skip conv + its InstanceNorm as a slope / offset of the final pass
 
+    skip_stats_fused = os.environ.get("ETCH_SKIP_STATS_FUSED", "1") != "0"   # the skip conv returns its InstanceNorm statistics (0: conv, then the statistics pass)
+    anchor_mean_fused = os.environ.get("ETCH_ANCHOR_MEAN_FUSED", "1") != "0"  # emit_anchor_mean blocks: the final pass also writes the anchor mean (0: etch_token_mean later)
+    emit_anchor_mean = False      # set by EquivBackbone on the block whose output feeds the heads
+
     def _skip_branch(self, fin, sample_idx, p2):
         b, p1, na, cin = fin.shape
         w = self.skip_conv.weight.detach().view(self.skip_conv.out_channels, cin)
@@ -130,6 +134,14 @@ class SeparableSO3ConvBlock(nn.Module):
             slope = (w64 * rstd).float()
             offset = ((b64 - (w64 * mean + b64)) * rstd).float()
             return ("k1", f, slope, offset)
+        if self.skip_stats_fused and fin.is_cuda and ops.linear_stats_supported(fin, w, self.stride > 1):
+            # the conv's epilogue holds every value it writes: the statistics come with the product (no pass that reads s back); the product itself keeps
+            # the bits of ops.linear (the strided block stays on the fp32 MFMA tile kernel)
+            if self.stride > 1:
+                s, m3, r3 = ops.linear_stats(fin.view(-1, cin), w, bias, b, p2 * na, row_idx=sample_idx.contiguous(), grp=na, p_in=p1, p_out=p2)
+            else:
+                s, m3, r3 = ops.linear_stats(fin.view(-1, cin), w, bias, b, p2 * na)
+            return s.view(b, p2, na, -1), m3, r3
         if self.stride > 1:
             s = ops.linear(fin.view(-1, cin), w, bias=bias, row_idx=sample_idx.contiguous(), grp=na, p_in=p1, p_out=p2, rows=b * p2 * na)
         else:
@@ -172,7 +184,10 @@ class SeparableSO3ConvBlock(nn.Module):
         else:
             torch.cuda.current_stream().wait_event(ev1)
         if isinstance(branch[0], str):                      # ("k1", f, slope, offset): the folded one-channel branch; ("zero",): constant features
-            if branch[0] == "zero":
+            amean = None
+            if branch[0] == "zero" and self._wants_anchor_mean(z.feats_cl):
+                res, amean = ops.instnorm_act_add_mean(z.feats_cl, m2, r2)
+            elif branch[0] == "zero":
                 res = ops.instnorm_act_add(z.feats_cl, m2, r2, want_planes=self.emit_planes)
             else:
                 _, f, slope, offset = branch
@@ -181,19 +196,29 @@ class SeparableSO3ConvBlock(nn.Module):
             cloud = sptk.SphericalPointCloud(y.xyz, None, z.anchors, feats_cl=out)
             if planes is not None:
                 cloud.feats_planes = planes
+            if amean is not None:
+                cloud.anchor_mean = amean
             return inter_idx, None, sample_idx, cloud
         s, m3, r3 = branch
         # emit_planes (set by EquivBackbone when the NEXT conv gathers planes; True / "bf16" / "f16" = their format): the output is also written split, once, by this pass
-        planes = None
+        planes, amean = None, None
         if self.emit_planes:
             out, planes = ops.instnorm_act_add(z.feats_cl, m2, r2, s, m3, r3, want_planes=self.emit_planes)
+        elif self._wants_anchor_mean(z.feats_cl):
+            out, amean = ops.instnorm_act_add_mean(z.feats_cl, m2, r2, s, m3, r3)
         else:
             out = ops.instnorm_act_add(z.feats_cl, m2, r2, s, m3, r3)
         # x.anchors after the intra conv = the INTRA conv's anchors buffer (vgtk modules.py:153; so3conv.py:182 passes it on)
         cloud = sptk.SphericalPointCloud(y.xyz, None, z.anchors, feats_cl=out)
         if planes is not None:
             cloud.feats_planes = planes
+        if amean is not None:
+            cloud.anchor_mean = amean         # (b * p, C): the mean over the anchors of feats_cl, read by GT_network_equiv._forward
         return inter_idx, None, sample_idx, cloud
+
+    def _wants_anchor_mean(self, x):
+        return (self.emit_anchor_mean and self.anchor_mean_fused and x.is_cuda and not self.emit_planes
+                and x.shape[2] == 60 and x.shape[-1] in ops.ANCHOR_MEAN_WIDTHS)
 
 
 class BasicSO3ConvBlock(nn.Module):

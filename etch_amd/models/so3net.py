@@ -89,6 +89,9 @@ class EquivBackbone(nn.Module):
         for cur, nxt in zip(convs[:-1], convs[1:]):
             if isinstance(cur, M.SeparableSO3ConvBlock) and isinstance(nxt, M.SeparableSO3ConvBlock):
                 cur.emit_planes = nxt.inter_conv.conv.wants_planes()
+        # the last block's output feeds the heads, which read its mean over the anchors: its final pass writes that mean too
+        if convs and isinstance(convs[-1], M.SeparableSO3ConvBlock):
+            convs[-1].emit_anchor_mean = True
 
     def _apply(self, fn, *a, **k):
         super()._apply(fn, *a, **k)

@@ -239,6 +239,36 @@ def linear(x, weight, bias=None, scale=None, shift=None, act=None, res=None, res
     return out
 
 
+LINEAR_STATS_SHAPES = ((32, 32), (64, 64), (32, 64))      # (K, O) of the encoder's skip convs: the shapes etch_linear_stats is built for
+
+
+def linear_stats_supported(x, weight, strided=False):
+    shape = (x.shape[-1], weight.shape[0])
+    return (shape == (32, 64) if strided else shape in LINEAR_STATS_SHAPES) and x.is_contiguous() and weight.is_contiguous()
+
+
+def linear_stats(x, weight, bias, b, rows, row_idx=None, grp=1, p_in=0, p_out=1):
+    """The skip conv with its InstanceNorm statistics from the GEMM's epilogue (etch_linear_stats): Y = X[rowmap] W^T + bias for b samples of `rows` rows
+    each -> Y (b * rows, O), mean (b, O), rstd (b, O).  x (b * rows_in, K) contiguous; row_idx (b, p_out) int32 with grp / p_in / p_out as in linear()
+    (rows = p_out * grp).  (K, O) in LINEAR_STATS_SHAPES; with row_idx (32, 64) only.  Y is bitwise linear()'s with the same arguments."""
+    _need(x, torch.float32, "x"), _need(weight, torch.float32, "weight")
+    K, O = x.shape[-1], weight.shape[0]
+    assert weight.shape[1] == K
+    if row_idx is not None:
+        _need(row_idx, torch.int32, "row_idx")
+        assert row_idx.numel() == b * p_out and rows == p_out * grp
+    lib = _lib.lib()
+    parts = lib.etch_linear_stats_parts(int(rows), 0 if row_idx is None else 1)
+    out = torch.empty((b * rows, O), dtype=torch.float32, device=x.device)
+    part = torch.empty((b, parts, 2, O), dtype=torch.float64, device=x.device)
+    mean = torch.empty((b, O), dtype=torch.float32, device=x.device)
+    rstd = torch.empty((b, O), dtype=torch.float32, device=x.device)
+    _lib.check(lib.etch_linear_stats(int(b), int(rows), int(K), int(O), _ptr(x), _c_long(K), _optptr(row_idx), int(grp), int(p_in), int(p_out),
+                                     _ptr(weight), _c_long(K), _optptr(bias), _ptr(out), _c_long(O), _ptr(part), _ptr(mean), _ptr(rstd), _stream()),
+               "etch_linear_stats")
+    return out, mean, rstd
+
+
 def permute_weight_frag(w2):
     """[O, K] (O % 16 == 0, K % 16 == 0) -> MFMA fragment order Wp[t][mt][lane][s] = W2[16mt + lane%16][16t + 4(lane//16) + s]."""
     O, K = w2.shape
@@ -600,6 +630,37 @@ def instnorm_stats(x_cl):
     rstd = torch.empty((b, C), dtype=torch.float32, device=x_cl.device)
     _lib.check(_lib.lib().etch_instnorm_stats(b, rows, C, _ptr(x_cl), _ptr(ws), _ptr(mean), _ptr(rstd), _stream()), "etch_instnorm_stats")
     return mean, rstd
+
+
+def instnorm_from_partials(part, total, wide=True):
+    """part (b, nparts, 2, C) fp64 sums / sums of squares over `total` values per (sample, channel) -> mean (b, C), rstd (b, C).  wide: one workgroup per
+    channel quad and sample; False: the one-workgroup form (the same bits)."""
+    _need(part, torch.float64, "part")
+    b, nparts, two, C = part.shape
+    assert two == 2
+    mean = torch.empty((b, C), dtype=torch.float32, device=part.device)
+    rstd = torch.empty((b, C), dtype=torch.float32, device=part.device)
+    _lib.check(_lib.lib().etch_instnorm_from_partials_n(b, nparts, C, _c_long(int(total)), _ptr(part), _ptr(mean), _ptr(rstd), 1 if wide else 0, _stream()),
+               "etch_instnorm_from_partials_n")
+    return mean, rstd
+
+
+ANCHOR_MEAN_WIDTHS = (32, 64, 128, 256)
+
+
+def instnorm_act_add_mean(x1, m1, r1, x2=None, m2=None, r2=None):
+    """instnorm_act_add for x1 (b, p, 60, C) that also returns the mean of the result over each point's 60 anchor rows, (b * p, C): bitwise
+    token_mean(out.view(b * p, 60, C)), from the pass that wrote out.  C in ANCHOR_MEAN_WIDTHS."""
+    _need(x1, torch.float32, "x1")
+    b, p, na, C = x1.shape
+    assert na == 60 and C in ANCHOR_MEAN_WIDTHS
+    if x2 is not None:
+        _need(x2, torch.float32, "x2")
+    out = torch.empty_like(x1)
+    mean = torch.empty((b * p, C), dtype=torch.float32, device=x1.device)
+    _lib.check(_lib.lib().etch_instnorm_act_add_mean(b, p, C, _ptr(x1), _ptr(m1), _ptr(r1), _optptr(x2), _optptr(m2), _optptr(r2), _ptr(out), _ptr(mean),
+                                                    _stream()), "etch_instnorm_act_add_mean")
+    return out, mean
 
 
 def instnorm_act_add_k1(x1, m1, r1, f, slope, offset, want_planes=False):

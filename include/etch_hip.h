@@ -120,6 +120,20 @@ int etch_linear(int R, int K, int O, const float* X, long ldx, const int* row_id
                 const float* W, long ldw, const float* bias, const float* scale, const float* shift, int act,
                 const float* res, long ldr, int res_mode, float* Y, long ldy, void* stream);
 
+/* The encoder's skip conv with the InstanceNorm2d statistics of its output (src/models/so3conv.py:166-168,181) from the GEMM's epilogue:
+ *   Y[s][r] = X[rowmap(s, r)] W^T + bias for b samples of `rows` rows each (X and Y contiguous over the samples), mean / rstd (b,O) of Y per
+ *   (sample, channel), eps 1e-5 -- what etch_instnorm_stats gives on Y (fp64 sums of the same fp32 values, in another fixed order).
+ * rowmap: identity when row_idx == NULL; else rows = p_out * grp and sample s reads source row (s * p_in + row_idx[s * p_out + r / grp]) * grp + r % grp.
+ * Y is bitwise etch_linear's: the weight-stationary three-plane kernel without a row map, the fp32 MFMA tile kernel with one (strided = 1 below;
+ * (K, O) = (32,64) only).  A sample's rows are divided among etch_linear_stats_parts(rows, strided) workgroups of
+ * etch_linear_stats_rows_per_part(rows, strided) rows each (the last one ragged): a function of `rows` alone, so a scan's statistics do not depend
+ * on its batch neighbours or on the chip.  partial: workspace of parts * b * 2 * O doubles (16-byte aligned).
+ * (K, O) in {(32,32), (64,64), (32,64)}, 16-byte aligned X / W / Y with ld % 4 == 0; otherwise ETCH_EUNSUPPORTED (etch_linear + etch_instnorm_stats). */
+int etch_linear_stats(int b, int rows, int K, int O, const float* X, long ldx, const int* row_idx, int grp, int p_in, int p_out,
+                      const float* W, long ldw, const float* bias, float* Y, long ldy, double* partial, float* mean, float* rstd, void* stream);
+int etch_linear_stats_parts(int rows, int strided);
+int etch_linear_stats_rows_per_part(int rows, int strided);
+
 /* ---- EPN encoder (channels-last activations F[b][p][60][c]) -------------------------------------------- */
 
 /* Fused inter-SO(3) convolution.  Replaces inter_so3conv_grouping_anchor + inter_so3conv_feat_grouping
@@ -221,6 +235,9 @@ int etch_split3_planes(long rows, int C, const float* x, void* planes, void* str
 /* mean / rstd (b,C) of InstanceNorm2d(affine=False, eps 1e-5) from per-part partial sums: partial (b,nparts,2,C) fp64, each over `count`
  * values.  Same result as etch_instnorm_stats over the full tensor (fp64 accumulation, fixed order). */
 int etch_instnorm_from_partials(int b, int nparts, int C, int count, const double* partial, float* mean, float* rstd, void* stream);
+/* The same with the TRUE number of values per (sample, channel) (`total`: the parts need not be equally large).  wide != 0: one workgroup per channel
+ * quad and sample instead of one per sample (the same slices and the same order of every sum: the same bits); wide == 0: the one-workgroup form. */
+int etch_instnorm_from_partials_n(int b, int nparts, int C, long total, const double* partial, float* mean, float* rstd, int wide, void* stream);
 
 /* Morton (Z-curve) order of each scan's points on its own bounding box, ties by index: xyz (b,3,n) -> order (b,n) int32, a
  * permutation of 0..n-1 per scan.  n <= 16384: 10 bits per axis; larger scans: 5 bits per axis, sorted in independent slices of
@@ -266,6 +283,10 @@ int etch_instnorm_stats_workspace_bytes(int b, int C);
 int etch_instnorm_act_add(int b, int rows, int C, const float* x1, const float* m1, const float* r1, const float* x2,
                           const float* m2, const float* r2, float* out, void* stream);
 /* The same, additionally writing the result as three bf16 planes (b, rows, 3, C) for etch_inter_so3conv_planes (planes may be NULL). */
+/* The same for x1 / x2 / out (b,p,60,C), additionally writing mean (b*p,C) = the mean of out over each point's 60 anchor rows: bitwise what
+ * etch_token_mean(b*p, 60, C, out) gives, without re-reading out.  C in {32, 64, 128, 256}; otherwise ETCH_EUNSUPPORTED. */
+int etch_instnorm_act_add_mean(int b, int p, int C, const float* x1, const float* m1, const float* r1, const float* x2, const float* m2, const float* r2,
+                               float* out, float* mean, void* stream);
 int etch_instnorm_act_add_planes(int b, int rows, int C, const float* x1, const float* m1, const float* r1, const float* x2,
                                  const float* m2, const float* r2, float* out, void* planes, void* stream);
 /* The same with two fp16 planes (b, rows, 2, C) for etch_inter_so3conv_planes_kq. */
