@@ -1,5 +1,6 @@
 // The training step's own kernels (train.py:81-125): the four losses with their gradients in one launch, and Adam with the reference's NaN guards in
-// two launches whatever the number of parameter tensors.  DESIGN section 11.
+// two launches whatever the number of parameter tensors; the pack of the gradients into one flat buffer for accumulated and data-parallel steps.
+// DESIGN section 11.
 #include "common.h"
 #include "etch_hip.h"
 
@@ -281,6 +282,84 @@ int etch_guarded_adam_step(int T, int C, const int* chunk_tensor, const int* fir
     ETCH_RETURN_IF_LAUNCH_FAILED();
     hipLaunchKernelGGL(guarded_adam_update_kernel, dim3((unsigned)C), dim3(ADAM_THREADS), 0, st, chunk_tensor, first_chunk, numel, pmv, T, grads, status,
                        steps, chunkflags, lr, beta1, beta2, eps, counters);
+    ETCH_RETURN_IF_LAUNCH_FAILED();
+    return ETCH_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- gradient pack
+// Accumulated and data-parallel steps: every contribution's gradients go, scaled, into one flat buffer over the Adam chunk table -- one
+// workgroup per chunk, tensor t at flat[off[t], off[t] + numel[t]) with off[t] a multiple of 4 elements -- and the step's small words into the
+// GRAD_TAIL floats at `tail`: one SUM all-reduce then moves everything.  The product and the sum are rounded separately (no FMA), as torch's
+// `flat + g * s` is: contributions combine to the same bits whether they were added here or by the collective.
+#define GRAD_TAIL 8                       /* 5 losses, NaN-total count, bad-label count, spare (zero) */
+
+int etch_grad_tail_floats(void) { return GRAD_TAIL; }
+
+__device__ __forceinline__ float grad_pack_value(float g, float s, float prev, bool add) {
+#pragma clang fp contract(off)
+    const float v = g * s;
+    return add ? prev + v : v;
+}
+
+__global__ void __launch_bounds__(ADAM_THREADS) grad_pack_kernel(const int* __restrict__ chunk_tensor, const int* __restrict__ first_chunk,
+                                                                  const long long* __restrict__ numel, const unsigned long long* __restrict__ gtab,
+                                                                  const long long* __restrict__ off, float* flat, float s, int mode,
+                                                                  const float* __restrict__ losses, const int* __restrict__ status, long long tail) {
+    const bool add = mode != 0;
+    if (blockIdx.x == 0 && threadIdx.x < GRAD_TAIL && tail >= 0) {
+        const int k = threadIdx.x;
+        float v = 0.f;              // a count needs no scale: the unpack asks only whether it is zero
+        if (k < 5) v = losses ? losses[k] : 0.f;
+        else if (k == 5) v = status && (status[0] & ETCH_TRAIN_STATUS_NAN) ? 1.f : 0.f;
+        else if (k == 6) v = status && (status[0] & ETCH_TRAIN_STATUS_BAD_LABEL) ? 1.f : 0.f;
+        float* d = flat + tail + k;
+        *d = grad_pack_value(v, k < 5 ? s : 1.f, add ? *d : 0.f, add);
+    }
+    const AdamChunk c = adam_chunk(chunk_tensor, first_chunk, numel);
+    const float* g = reinterpret_cast<const float*>(gtab[c.t]);
+    float* d = flat + off[c.t] + c.start;
+    if (!g) {                       // no gradient in this contribution: zeros for the first, nothing to add afterwards
+        if (!add)
+            for (int i = threadIdx.x; i < c.len; i += ADAM_THREADS) d[i] = 0.f;
+        return;
+    }
+    g += c.start;
+    const bool vec = ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(d)) & 15) == 0;
+    const int n4 = vec ? c.len >> 2 : 0;
+    for (int i = threadIdx.x; i < n4; i += ADAM_THREADS) {
+        const float4 gq = reinterpret_cast<const float4*>(g)[i];
+        float4 dq = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (add) dq = reinterpret_cast<const float4*>(d)[i];
+        dq.x = grad_pack_value(gq.x, s, dq.x, add);
+        dq.y = grad_pack_value(gq.y, s, dq.y, add);
+        dq.z = grad_pack_value(gq.z, s, dq.z, add);
+        dq.w = grad_pack_value(gq.w, s, dq.w, add);
+        reinterpret_cast<float4*>(d)[i] = dq;
+    }
+    for (int i = (n4 << 2) + threadIdx.x; i < c.len; i += ADAM_THREADS) d[i] = grad_pack_value(g[i], s, add ? d[i] : 0.f, add);
+}
+
+int etch_grad_pack(int T, int C, const int* chunk_tensor, const int* first_chunk, const long long* numel, const unsigned long long* grads,
+                   const long long* offsets, float* flat, float scale, int mode, const float* losses, const int* status, long long tail_offset,
+                   void* stream) {
+    if (T <= 0 || C <= 0 || !chunk_tensor || !first_chunk || !numel || !grads || !offsets || !flat || (mode != 0 && mode != 1)) return ETCH_EINVAL;
+    hipLaunchKernelGGL(grad_pack_kernel, dim3((unsigned)C), dim3(ADAM_THREADS), 0, (hipStream_t)stream, chunk_tensor, first_chunk, numel, grads, offsets,
+                       flat, scale, mode, losses, status, tail_offset);
+    ETCH_RETURN_IF_LAUNCH_FAILED();
+    return ETCH_OK;
+}
+
+// After the reduction: the tail back into the words the step reads -- the (5) losses, and the status word etch_guarded_adam_step obeys (a bit is set
+// if any contribution set it).
+__global__ void __launch_bounds__(64) grad_unpack_tail_kernel(const float* __restrict__ tail, float* __restrict__ losses, int* __restrict__ status) {
+    const int k = threadIdx.x;
+    if (k < 5) losses[k] = tail[k];
+    else if (k == 5) status[0] = (tail[5] != 0.f ? ETCH_TRAIN_STATUS_NAN : 0) | (tail[6] != 0.f ? ETCH_TRAIN_STATUS_BAD_LABEL : 0);
+}
+
+int etch_grad_unpack_tail(const float* tail, float* losses, int* status, void* stream) {
+    if (!tail || !losses || !status) return ETCH_EINVAL;
+    hipLaunchKernelGGL(grad_unpack_tail_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, tail, losses, status);
     ETCH_RETURN_IF_LAUNCH_FAILED();
     return ETCH_OK;
 }

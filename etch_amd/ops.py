@@ -8,6 +8,7 @@ import ctypes
 import math
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1511,6 +1512,56 @@ def guarded_adam_step(T, C, chunk_tensor, first_chunk, numel, pmv, grads, status
     _lib.check(_lib.lib().etch_guarded_adam_step(int(T), int(C), _ptr(chunk_tensor), _ptr(first_chunk), _ptr(numel), _ptr(pmv), _ptr(grads), _optptr(status),
                                                  _ptr(steps), _ptr(chunkflags), ctypes.c_double(lr), ctypes.c_double(betas[0]), ctypes.c_double(betas[1]),
                                                  ctypes.c_double(eps), _ptr(counters), _stream()), "etch_guarded_adam_step")
+
+
+def grad_tail_floats():
+    return int(_lib.lib().etch_grad_tail_floats())
+
+
+def grad_pack(T, C, chunk_tensor, first_chunk, numel, grads, offsets, flat, scale, mode, losses=None, status=None, tail_offset=-1, *, layout):
+    """etch_grad_pack: one contribution's gradients (grads (T) int64 addresses, 0 = none) times `scale` into the fp32 buffer `flat` at offsets (T) int64
+    elements, over GuardedAdam's chunk table.  mode 0 writes, mode 1 adds (product and sum rounded separately).  tail_offset >= 0: losses (5) * scale
+    and the two bits of status as 0/1 go into the grad_tail_floats() floats there.  layout = (offsets, numel) as HOST integer arrays, the copies of
+    the two device tables: every slot is checked against the buffer here, on the host, before the launch."""
+    _need(flat, torch.float32, "flat"), _need(offsets, torch.int64, "offsets"), _need(grads, torch.int64, "grads"), _need(numel, torch.int64, "numel")
+    if mode not in (0, 1):
+        raise _lib.EtchHipError(f"grad_pack: mode must be 0 (write) or 1 (add), got {mode}")
+    if flat.data_ptr() % 16:
+        raise _lib.EtchHipError("grad_pack: the flat buffer must be 16-byte aligned")
+    off_h, numel_h = (np.asarray(a, np.int64).reshape(-1) for a in layout)
+    if not (off_h.size == numel_h.size == int(T) == offsets.numel() == numel.numel() == grads.numel()):
+        raise _lib.EtchHipError(f"grad_pack: the tables and the layout must hold T = {T} entries each")
+    if (off_h < 0).any() or (off_h % 4).any() or (numel_h < 0).any():
+        raise _lib.EtchHipError("grad_pack: offsets must be non-negative multiples of 4 elements")
+    if int((off_h + numel_h).max()) > (tail_offset if tail_offset >= 0 else flat.numel()):
+        raise _lib.EtchHipError("grad_pack: a slot reaches beyond the flat buffer (or into its tail)")
+    if tail_offset >= 0:
+        if tail_offset + grad_tail_floats() > flat.numel():
+            raise _lib.EtchHipError("grad_pack: the tail does not fit the flat buffer")
+        if losses is not None:
+            _need(losses, torch.float32, "losses")
+            if losses.numel() < 5:
+                raise _lib.EtchHipError("grad_pack: losses must hold 5 values")
+        if status is not None:
+            _need(status, torch.int32, "status")
+    _lib.check(_lib.lib().etch_grad_pack(int(T), int(C), _ptr(chunk_tensor), _ptr(first_chunk), _ptr(numel), _ptr(grads), _ptr(offsets), _ptr(flat),
+                                         ctypes.c_float(float(scale)), int(mode), _optptr(losses), _optptr(status), ctypes.c_longlong(int(tail_offset)),
+                                         _stream()), "etch_grad_pack")
+
+
+def grad_unpack_tail(tail, losses=None, status=None):
+    """etch_grad_unpack_tail: the (reduced) tail of a flat gradient buffer -> (losses (5) fp32, status (1) int32 with the ETCH_TRAIN_STATUS_* bits any
+    contribution set); `losses` / `status` are written in place when given."""
+    _need(tail, torch.float32, "tail")
+    if tail.numel() < grad_tail_floats():
+        raise _lib.EtchHipError(f"grad_unpack_tail: the tail holds {grad_tail_floats()} floats")
+    if losses is None:
+        losses = torch.empty((5,), dtype=torch.float32, device=tail.device)
+    if status is None:
+        status = torch.zeros((1,), dtype=torch.int32, device=tail.device)
+    _need(losses, torch.float32, "losses"), _need(status, torch.int32, "status")
+    _lib.check(_lib.lib().etch_grad_unpack_tail(_ptr(tail), _ptr(losses), _ptr(status), _stream()), "etch_grad_unpack_tail")
+    return losses, status
 
 
 # ------------------------------------------------------------------ scan ingestion (csrc/mesh_sample.hip; DESIGN section 12)

@@ -23,7 +23,12 @@ class GuardedAdam(torch.optim.Optimizer):
     The step counts live on the device (one fp32 per tensor; bias corrections are computed from them in the kernel).  Gradient addresses change from
     step to step (`zero_grad(set_to_none=True)`): they go up through a ring of pinned buffers, asynchronously; step() waits only if the host is more
     than RING steps ahead of the device.  `state_dict()` / `load_state_dict()` use torch.optim.Adam's layout, so a state saved by either loads into
-    the other.  `step()` returns nothing; `report()` is the step's one readback."""
+    the other.  `step()` returns nothing; `report()` is the step's one readback.
+
+    Accumulated and data-parallel steps: `accumulate(scale, first, losses)` packs each contribution's `.grad`s, scaled, into one flat buffer
+    (`flat_gradients()`), the caller SUM-reduces that buffer over the ranks, and `step()` then takes its gradients from it: the guards above run on
+    the combined gradient, and a NaN total in ANY contribution skips the step.  With one contribution and scale 1 the result is bit for bit the
+    step from `.grad`."""
 
     RING = 4
 
@@ -39,7 +44,9 @@ class GuardedAdam(torch.optim.Optimizer):
         self._groups = None
         self._status = None         # int32 (1): the loss kernel's status word
         self._counters = None       # int32 (4): tensors stepped with a zeroed gradient, skipped steps, bad-label flag (all cumulative), spare
-        self._calls = 0
+        self._flat = None           # (fp32 buffer, layout) of flat_gradients()
+        self._flat_losses = None
+        self._flat_pending = False  # accumulate() since the last step(): the step reads the flat buffer
 
     # ---- tables
     def _check(self, p):
@@ -87,7 +94,8 @@ class GuardedAdam(torch.optim.Optimizer):
              "pmv_host": np.zeros((3, T), np.uint64), "pmv": torch.zeros((3, T), dtype=torch.int64, device=dev), "dirty": True,
              "ring": [torch.zeros((T,), dtype=torch.int64).pin_memory() for _ in range(self.RING)], "events": [None] * self.RING,
              "gdev": torch.zeros((T,), dtype=torch.int64, device=dev), "keep": None,
-             "pptr": [-1] * T}          # the parameter address the tables hold; -1 = no state yet
+             "pptr": [-1] * T,          # the parameter address the tables hold; -1 = no state yet
+             "numel_np": numel, "uploads": 0}
         g["ring_np"] = [r.numpy() for r in g["ring"]]
         # state that exists already (load_state_dict before the first step)
         for i, p in enumerate(params):
@@ -113,54 +121,127 @@ class GuardedAdam(torch.optim.Optimizer):
 
     def _tables(self):
         if self._groups is None:
+            self._flat, self._flat_pending = None, False          # the flat layout follows the tables
             self._groups = [self._build(group) if any(p.numel() for p in group["params"]) else None for group in self.param_groups]
         return self._groups
 
     # ---- the step
+    def _gather(self, g):
+        """The addresses of the group's current `.grad`s (0 = None), creating Adam state for a tensor that sees its first gradient."""
+        ptrs, keep, pptr, f32 = [], [], g["pptr"], torch.float32
+        for i, p in enumerate(g["params"]):
+            grad = p.grad
+            if grad is None:
+                ptrs.append(0)
+                continue
+            if grad.dtype is not f32 or grad.device != p.device or grad.is_sparse:
+                raise ValueError("GuardedAdam: gradients must be dense fp32 tensors on the parameters' device")
+            if not grad.is_contiguous():
+                grad = grad.contiguous()
+                keep.append(grad)
+            if pptr[i] != p.data_ptr():              # no state yet (torch.optim.Adam's lazy state: made at the first step that sees a gradient), or moved
+                self._check(p)
+                st = self.state[p]
+                if "exp_avg" not in st:
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                self._adopt(g, i, p, st)
+            ptrs.append(grad.data_ptr())
+        g["keep"] = keep
+        return ptrs
+
+    def _upload(self, g, ptrs):
+        """An address table to the device through the pinned ring, asynchronously (and the parameter / moment table if it changed)."""
+        slot = g["uploads"] % self.RING
+        g["uploads"] += 1
+        if g["events"][slot] is not None:
+            g["events"][slot].synchronize()          # the copy of RING uploads ago: long done unless the host runs that far ahead
+        g["ring_np"][slot][:] = ptrs
+        if g["dirty"]:
+            g["pmv"].copy_(torch.from_numpy(g["pmv_host"].view(np.int64)))
+            g["dirty"] = False
+        g["gdev"].copy_(g["ring"][slot], non_blocking=True)
+        ev = g["events"][slot] or torch.cuda.Event()
+        ev.record()
+        g["events"][slot] = ev
+
     @torch.no_grad()
     def step(self, closure=None):
+        """One Adam step from the `.grad`s -- or, if accumulate() was called since the last step, from the flat buffer: the tail is unpacked first (the
+        status word and `flat_losses`), and a tensor is stepped iff one of the local contributions held a gradient for it."""
         if closure is not None:
             raise ValueError("GuardedAdam.step takes no closure: a closure's loss would have to be read back")
+        from_flat = self._flat_pending
+        if from_flat:
+            flat, layout = self.flat_gradients()
+            ops.grad_unpack_tail(flat[layout["tail"]:], self._flat_losses, self._status)
         for group, g in zip(self.param_groups, self._tables()):
             if g is None:
                 continue
-            slot = self._calls % self.RING
-            if g["events"][slot] is not None:
-                g["events"][slot].synchronize()          # the copy of RING steps ago: long done unless the host runs RING steps ahead
-            ptrs, keep, pptr, f32 = [], [], g["pptr"], torch.float32
-            for i, p in enumerate(g["params"]):
-                grad = p.grad
-                if grad is None:
-                    ptrs.append(0)
-                    continue
-                if grad.dtype is not f32 or grad.device != p.device or grad.is_sparse:
-                    raise ValueError("GuardedAdam: gradients must be dense fp32 tensors on the parameters' device")
-                if not grad.is_contiguous():
-                    grad = grad.contiguous()
-                    keep.append(grad)
-                if pptr[i] != p.data_ptr():              # no state yet (torch.optim.Adam's lazy state: made at the first step that sees a gradient), or moved
-                    self._check(p)
-                    st = self.state[p]
-                    if "exp_avg" not in st:
-                        st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                        st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    self._adopt(g, i, p, st)
-                ptrs.append(grad.data_ptr())
-            g["ring_np"][slot][:] = ptrs
-            if g["dirty"]:
-                g["pmv"].copy_(torch.from_numpy(g["pmv_host"].view(np.int64)))
-                g["dirty"] = False
-            g["gdev"].copy_(g["ring"][slot], non_blocking=True)
-            ev = g["events"][slot] or torch.cuda.Event()
-            ev.record()
-            g["events"][slot] = ev
-            g["keep"] = keep
+            if from_flat:
+                ptrs = np.where(g["has_grad"], flat.data_ptr() + 4 * g["off_np"], 0)
+            else:
+                ptrs = self._gather(g)
+            self._upload(g, ptrs)
             lr, betas, eps = group["lr"], group["betas"], group["eps"]
             if group.get("weight_decay", 0) != 0 or group.get("amsgrad") or group.get("maximize"):
                 raise ValueError("GuardedAdam supports weight_decay=0, amsgrad=False, maximize=False only")
             ops.guarded_adam_step(g["T"], g["C"], g["chunk_tensor"], g["first_chunk"], g["numel"], g["pmv"], g["gdev"], self._status, g["steps"],
                                   g["chunkflags"], float(lr), (float(betas[0]), float(betas[1])), float(eps), self._counters)
-        self._calls += 1
+        self._flat_pending = False
+
+    # ---- gradients through a flat buffer (accumulated and data-parallel steps)
+    def flat_gradients(self):
+        """(flat, layout): the fp32 device buffer accumulate() packs into, allocated at the first call, and its static layout -- {"params": the
+        tensors, "offsets" / "numel": int64 arrays (tensor k at flat[offsets[k] : offsets[k] + numel[k]], every slot rounded up to 4 elements),
+        "tail": the offset of the ops.grad_tail_floats() floats behind the slots (5 losses, NaN-total count, bad-label count, spare), "size"}.  The
+        layout depends on the parameters alone, never on which gradients are None: it is the same on every rank."""
+        if self._flat is None:
+            groups = [g for g in self._tables() if g is not None]
+            if not groups:
+                raise ValueError("GuardedAdam.flat_gradients: no parameters")
+            base, params, offs = 0, [], []
+            for g in groups:
+                slots = (g["numel_np"] + 3) // 4 * 4
+                g["off_np"] = base + np.cumsum(slots) - slots
+                g["off"] = torch.from_numpy(g["off_np"]).to(g["dev"])
+                g["has_grad"] = np.zeros(g["T"], bool)
+                base += int(slots.sum())
+                params += g["params"]
+                offs.append(g["off_np"])
+            layout = {"params": params, "offsets": np.concatenate(offs), "numel": np.concatenate([g["numel_np"] for g in groups]), "tail": base,
+                      "size": base + ops.grad_tail_floats()}
+            self._flat = (torch.zeros((layout["size"],), dtype=torch.float32, device=groups[0]["dev"]), layout)
+            self._flat_losses = torch.zeros((5,), dtype=torch.float32, device=groups[0]["dev"])
+        return self._flat
+
+    @property
+    def flat_losses(self):
+        """(5,) device tensor: the tail's losses as the last step from the flat buffer unpacked them (the sum over contributions of loss * scale)."""
+        self.flat_gradients()
+        return self._flat_losses
+
+    @torch.no_grad()
+    def accumulate(self, scale, first, losses=None):
+        """Pack the current `.grad`s times `scale` into the flat buffer (csrc/train_step.hip: etch_grad_pack, one launch per param group): written if
+        `first`, added otherwise; a None gradient contributes zeros.  The tail takes `losses` (the (5,) tensor of etch_amd.losses.train_losses, or
+        None) times `scale` and the status word's bits.  The next step() reads the flat buffer -- reduce it over the ranks in between.
+
+        Which tensors that step updates is decided per rank (a tensor is skipped iff its gradient was None in every LOCAL contribution): a model
+        whose set of tensors with a gradient differs between ranks would step a tensor on one rank and not on another, and the replicas would
+        drift apart unnoticed.  The set must be the same on every rank, as it is when every rank runs the same heads (`--pred_items`)."""
+        flat, layout = self.flat_gradients()
+        tail = layout["tail"]
+        for g in self._tables():
+            if g is None:
+                continue
+            ptrs = np.asarray(self._gather(g), np.int64)
+            g["has_grad"] = (ptrs != 0) if first else (g["has_grad"] | (ptrs != 0))
+            self._upload(g, ptrs)
+            ops.grad_pack(g["T"], g["C"], g["chunk_tensor"], g["first_chunk"], g["numel"], g["gdev"], g["off"], flat, float(scale), 0 if first else 1,
+                          losses if tail >= 0 else None, self._status if tail >= 0 else None, tail, layout=(g["off_np"], g["numel_np"]))
+            tail = -1                                 # one tail per contribution: the first group's launch carries it
+        self._flat_pending = True
 
     def report(self, losses=None):
         """The step's single readback: {"losses": the (5,) tensor the trainer hands over as a list (direction, magnitude, confidence, part label,

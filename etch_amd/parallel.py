@@ -1,7 +1,15 @@
 """Multi-GPU harness for the hot path: one process per GPU, scans sharded contiguously over ranks, no
 collective on the data path (scans are independent end to end); ONE all_gather of the per-scan
-result rows at the end of a batch (RCCL over xGMI via torch.distributed backend "nccl"; "gloo" in CPU tests)."""
+result rows at the end of a batch (RCCL over xGMI via torch.distributed backend "nccl"; "gloo" in CPU tests).
+
+Training (etch_amd.train) adds one SUM all-reduce of the flat gradient buffer per step (`reduce_flat`) and `launch_ranks`, the
+self-launcher of `--gpus N` from a plain interpreter."""
+import datetime
 import os
+import subprocess
+import sys
+import threading
+import time
 
 import torch
 import torch.distributed as dist
@@ -29,7 +37,9 @@ def init(backend=None):
         os.environ.setdefault("MASTER_PORT", "29531")
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         backend = backend or os.environ.get("ETCH_DIST_BACKEND") or ("nccl" if torch.cuda.is_available() else "gloo")
-        dist.init_process_group(backend, rank=rank, world_size=world)
+        # a finite timeout: a lost rank ends the job instead of leaving its peers in a collective for ever
+        timeout = datetime.timedelta(seconds=float(os.environ.get("ETCH_DIST_TIMEOUT", "600")))
+        dist.init_process_group(backend, rank=rank, world_size=world, timeout=timeout)
     return rank, world, local
 
 
@@ -189,3 +199,89 @@ def max_over_ranks(value, device):
     t = _coll(torch.tensor([value], dtype=torch.float64, device=device))
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     return float(t.item())
+
+
+def reduce_flat(t):
+    """SUM all-reduce of the fp32 buffer `t` in place, on the current stream (RCCL takes the device tensor: no host synchronisation; gloo, for
+    tests, goes through a host copy as `_coll` does).  Returns `t`; a no-op without an active group."""
+    if not _active():
+        return t
+    if dist.get_backend() == "gloo" and t.is_cuda:
+        h = t.cpu()
+        dist.all_reduce(h, op=dist.ReduceOp.SUM)
+        t.copy_(h)
+    else:
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return t
+
+
+MAX_RANKS = 16
+
+
+def _free_port():
+    import socket
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+def launch_ranks(argv, world, timeout=None):
+    """Start `world` ranks of the command `argv` (a full command line: [sys.executable, "-m", ...]) as child processes with RANK / LOCAL_RANK /
+    WORLD_SIZE / MASTER_ADDR / MASTER_PORT set, relay rank 0's standard output as it comes (the other ranks' is dropped; every rank's standard
+    error is inherited) and return the exit code: 0, or the first failing rank's code -- when a rank exits non-zero its peers, which would wait in
+    their next collective, are terminated.  `timeout` seconds (None: none) end the whole job with code 124.  The caller must not have initialised
+    the GPU; nothing is exec'ed.  Each child pins itself (`pin_to_local_cores`) before it initialises the GPU."""
+    if not 1 <= world <= MAX_RANKS:
+        raise ValueError(f"launch_ranks: world must be in [1, {MAX_RANKS}], got {world}")
+    port = os.environ.get("MASTER_PORT") or str(_free_port())
+    procs = []
+
+    def relay(pipe):
+        for line in pipe:
+            sys.stdout.write(line)
+            sys.stdout.flush()
+
+    def stop_all():
+        for p in procs:
+            if p.poll() is None:
+                p.terminate()
+        for p in procs:
+            try:
+                p.wait(timeout=20)
+            except subprocess.TimeoutExpired:
+                p.kill()
+                p.wait()
+
+    reader = None
+    t0 = time.monotonic()
+    try:
+        for r in range(world):
+            env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world), LOCAL_WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
+                       MASTER_PORT=port, HSA_ENABLE_IPC_MODE_LEGACY="0")
+            procs.append(subprocess.Popen(list(argv), env=env, stdout=subprocess.PIPE if r == 0 else subprocess.DEVNULL, stderr=None, text=True))
+        reader = threading.Thread(target=relay, args=(procs[0].stdout,), daemon=True)
+        reader.start()
+        bad, timed_out = [], False
+        while any(p.poll() is None for p in procs):
+            bad = [(r, p.returncode) for r, p in enumerate(procs) if p.poll() not in (None, 0)]
+            timed_out = timeout is not None and time.monotonic() - t0 > timeout
+            if bad or timed_out:
+                stop_all()
+                break
+            time.sleep(0.02)
+    except BaseException:
+        stop_all()
+        raise
+    finally:
+        if reader is not None:
+            reader.join(timeout=5)
+    if timed_out and not bad:
+        print(f"launch_ranks: no result after {timeout} s: ranks stopped", file=sys.stderr)
+        return 124
+    bad = bad or [(r, p.returncode) for r, p in enumerate(procs) if p.returncode != 0]
+    if bad:
+        print(f"launch_ranks: ranks failed (rank, rc): {bad}", file=sys.stderr)
+        return bad[0][1] if bad[0][1] and bad[0][1] > 0 else 1
+    return 0

@@ -765,6 +765,21 @@ int etch_guarded_adam_step(int T, int C, const int* chunk_tensor, const int* fir
                            const unsigned long long* grads, const int* status, float* steps, unsigned* chunkflags, double lr, double beta1,
                            double beta2, double eps, int* counters, void* stream);
 
+/* Accumulated and data-parallel steps: one contribution's gradients into a flat fp32 buffer, one launch over the chunk table of
+ * etch_guarded_adam_step.  Tensor t occupies flat[offsets[t], offsets[t] + numel[t]); offsets are multiples of 4 elements, so 16-byte accesses hold on
+ * a 16-byte aligned buffer.  mode 0: flat = g * scale (zeros for a gradient address of 0); mode 1: flat += g * scale (nothing for address 0).  Product
+ * and sum are rounded separately (no FMA); non-finite values pass through.  16-byte accesses where source and destination are 16-byte aligned, scalar
+ * otherwise.  Nothing between the slots is written.  tail_offset >= 0: the etch_grad_tail_floats() floats there receive (mode 0) or are advanced by
+ * (mode 1) losses[0..5) * scale, 1 if status[0] has ETCH_TRAIN_STATUS_NAN, 1 if it has ETCH_TRAIN_STATUS_BAD_LABEL, 0 (losses, status may be NULL:
+ * zeros); tail_offset < 0: no tail. */
+int etch_grad_tail_floats(void);
+int etch_grad_pack(int T, int C, const int* chunk_tensor, const int* first_chunk, const long long* numel, const unsigned long long* grads,
+                   const long long* offsets, float* flat, float scale, int mode, const float* losses, const int* status, long long tail_offset,
+                   void* stream);
+/* The (summed) tail back into what the step reads: losses (5) = tail[0..5); status[0] = ETCH_TRAIN_STATUS_NAN if tail[5] != 0, | ETCH_TRAIN_STATUS_BAD_LABEL
+ * if tail[6] != 0. */
+int etch_grad_unpack_tail(const float* tail, float* losses, int* status, void* stream);
+
 /* ---- scan ingestion: OBJ reader / writer (host) and the surface sampler (inference_demo.py:19-39, eval.py) ------- */
 
 /* Status codes of the etch_obj_* calls beyond 0 and -1.  The calls are host code on HOST buffers, keep no state and may run concurrently. */
