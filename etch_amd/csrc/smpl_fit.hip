@@ -8,6 +8,8 @@
 //                      (~2.2 GFLOP / scan / iteration); here the forward and an ANALYTIC Jacobian are restricted to the
 //                      marker vertices (Appendix C): one persistent workgroup per scan keeps the whole fit on chip
 //                      through all iterations.
+//                      etch_smpl_lm_fit_prior: the same fit warm-started at a caller's x and / or under a diagonal Gaussian prior
+//                      (lm_add_prior) -- what the sequence tracker (etch_amd/sequence.py) runs; no counterpart in the reference.
 //   etch_smpl_lbs      the final smpl_model(...) call (fit_SMPL.py:258-259): vertices (B,V,3) and the joints.
 //
 // Body models: the kernels are templated on (joints NJ, shape coefficients NB) and instantiated for SMPL (24, 10: the
@@ -131,6 +133,10 @@ struct LmShared {
     SmplConsts consts;                // the kernel's table pointers and the split state live HERE, not in a by-reference struct of the noinline
     LmSplit split;                    // phases' caller (that is a private-memory copy: 88 + 32 bytes of scratch per thread)
     int split_failed;                 // a partner workgroup of a split fit never arrived (or had given up): this scan's fit is abandoned, its results are NaN
+    const float* x_init;              // this scan's rows of the optional warm start and prior (null: absent), kept here for the same reason as consts;
+                                      // LAST, so that every offset the phases use is what it was
+    const float* prior_mean;
+    const float* prior_weight;
 };
 
 __device__ inline double& Apk(double* A, int i, int j) { return A[i * (i + 1) / 2 + j]; }   // i >= j
@@ -907,14 +913,42 @@ __device__ __attribute__((LM_PHASE_INLINE)) void lm_solve(LmShared<BM>& s, doubl
 #endif
 }
 
+// Diagonal Gaussian prior 0.5 sum_i w_i (x_i - mu_i)^2 over the stage's active DoFs (all but betas[nb:]) on top of what lm_linearize left:
+// A_ii += w_i, rhs_i -= w_i (x_i - mu_i) (row DOF holds -J^T r), s.err += the prior's value -- before lm_solve adds lambda, so the freeze
+// test and the trace see the full objective.  fp64; one wave, a fixed summation order: the G workgroups of a split scan (which call this
+// after their exchange, on identical state) stay bit-identical.  mu / w: this scan's (DOF) rows in global memory (L2-resident).
+// Out of line like the phases, and outside them: the phases' register allocation is the one without a prior.
+template <class BM>
+__device__ __attribute__((noinline)) void lm_add_prior(LmShared<BM>& s, int nb) {
+    constexpr int DOF = BM::DOF;
+    const int tid = threadIdx.x;
+    if (tid < 64) {
+        const float* __restrict__ mu = s.prior_mean;
+        const float* __restrict__ w = s.prior_weight;
+        double e = 0.0;
+        for (int i = tid; i < DOF; i += 64) {
+            if (i >= BM::NPOSE + nb && i < BM::NPOSE + BM::NB) continue;      // stage 0: the inactive betas have no prior and do not move
+            const double wi = (double)w[i], d = s.x[i] - (double)mu[i];
+            Apk(s.A, i, i) += wi;
+            Apk(s.A, DOF, i) -= wi * d;
+            e += 0.5 * wi * d * d;
+        }
+        e = wave_sum_f64(e);
+        if (tid == 0) s.err += e;
+    }
+    __syncthreads();
+}
+
 template <class BM>
 __global__ void __launch_bounds__(BM::THREADS) smpl_lm_fit_kernel(SmplConsts C, int M, const float* __restrict__ markers,
                                                                 const float* __restrict__ valid, int it0, float step0, float damp0,
                                                                 int it1, float step1, float damp1, float* __restrict__ x_out,
                                                                 float* __restrict__ x_stage0, float* __restrict__ err_trace, long long* __restrict__ phase_out,
                                                                 int G, double* __restrict__ split_ws, unsigned* __restrict__ split_ctr,
-                                                                unsigned spin_limit, int drop_group) {
+                                                                unsigned spin_limit, int drop_group, const float* __restrict__ x_init,
+                                                                const float* __restrict__ prior_mean, const float* __restrict__ prior_weight) {
     constexpr int DOF = BM::DOF;
+    constexpr int NB0 = BM::NB < NB_STAGE0 ? BM::NB : NB_STAGE0;
     extern __shared__ __attribute__((aligned(16))) unsigned char lm_smem[];
     LmShared<BM>& s = *reinterpret_cast<LmShared<BM>*>(lm_smem);
     const int b = blockIdx.x / G, tid = threadIdx.x;
@@ -925,12 +959,25 @@ __global__ void __launch_bounds__(BM::THREADS) smpl_lm_fit_kernel(SmplConsts C, 
         s.split_failed = 0;
     }
     if (!lead) { x_stage0 = nullptr; err_trace = nullptr; phase_out = nullptr; }
-    for (int i = tid; i < DOF; i += BM::THREADS) s.x[i] = 0.0;
+    const bool has_init = x_init != nullptr, has_prior = prior_weight != nullptr;
+    if (tid == 0) {
+        s.x_init = has_init ? x_init + (size_t)b * DOF : nullptr;
+        s.prior_mean = has_prior ? prior_mean + (size_t)b * DOF : nullptr;
+        s.prior_weight = has_prior ? prior_weight + (size_t)b * DOF : nullptr;
+    }
+    if (has_init) {
+        // warm start.  Stage 0 runs with its inactive betas at 0 (its forward reads all NB coefficients of s.x; the reference's stage 0 works on
+        // the reduced vector, i.e. with zeros there): they are put back after stage 0, untouched, and enter stage 1 at their x_init value
+        for (int i = tid; i < DOF; i += BM::THREADS)
+            s.x[i] = (i >= BM::NPOSE + NB0 && i < BM::NPOSE + BM::NB) ? 0.0 : (double)x_init[(size_t)b * DOF + i];
+    } else {
+        for (int i = tid; i < DOF; i += BM::THREADS) s.x[i] = 0.0;
+    }
     lm_setup(s, C, M, markers + (size_t)b * M * 3, valid + (size_t)b * M);
     int trace_pos = 0;
     for (int stage = 0; stage < 2; ++stage) {
         const int iters = stage == 0 ? it0 : it1;
-        const int nb = stage == 0 ? (BM::NB < NB_STAGE0 ? BM::NB : NB_STAGE0) : BM::NB;
+        const int nb = stage == 0 ? NB0 : BM::NB;
         const double step = stage == 0 ? (double)step0 : (double)step1;
         const double lambda = stage == 0 ? (double)damp0 : (double)damp1;
         float last = 0.f;
@@ -944,6 +991,7 @@ __global__ void __launch_bounds__(BM::THREADS) smpl_lm_fit_kernel(SmplConsts C, 
                 }
                 lm_linearize(s, M, nb, nullptr, false, G > 1);
                 if (G > 1 && s.split_failed) break;            // abandoned (uniform): fall through to the NaN write-out
+                if (has_prior) lm_add_prior(s, nb);   // uniform over the launch; absent: today's instruction stream
                 const float err = (float)s.err;
                 if (it >= 0) {
                     const float a = fabsf(last - err);
@@ -955,6 +1003,9 @@ __global__ void __launch_bounds__(BM::THREADS) smpl_lm_fit_kernel(SmplConsts C, 
             ++trace_pos;
         }
         if (G > 1 && s.split_failed) break;
+        if (stage == 0 && has_init)                             // (entry i by the thread that updates it above and writes it below: no barrier)
+            for (int i = tid; i < DOF; i += BM::THREADS)
+                if (i >= BM::NPOSE + NB0 && i < BM::NPOSE + BM::NB) s.x[i] = (double)s.x_init[i];
         if (stage == 0 && x_stage0)
             for (int i = tid; i < DOF; i += BM::THREADS) x_stage0[(size_t)b * DOF + i] = (float)s.x[i];
         __syncthreads();
@@ -1278,7 +1329,7 @@ static int g_lm_drop_group = -1;                 // test hook: this group index 
 template <class BM>
 static int launch_lm_fit(int B, int M, const void* const* consts, const float* markers, const float* valid, int it0, float step0, float damp0,
                          int it1, float step1, float damp1, float* x_out, float* x_stage0, float* err_trace, long long* phase_ticks, int G,
-                         void* workspace, hipStream_t st) {
+                         void* workspace, const float* x_init, const float* prior_mean, const float* prior_weight, hipStream_t st) {
     const int lds = (int)sizeof(LmShared<BM>);
     static_assert(sizeof(LmShared<BM>) <= 160 * 1024, "LM state must fit the 160 KB LDS of a gfx950 CU");
     hipError_t e = hipFuncSetAttribute((const void*)smpl_lm_fit_kernel<BM>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -1296,7 +1347,7 @@ static int launch_lm_fit(int B, int M, const void* const* consts, const float* m
     }
     hipLaunchKernelGGL(smpl_lm_fit_kernel<BM>, dim3(B * G), dim3(BM::THREADS), lds, st, lm_consts(consts), M, markers, valid, it0, step0, damp0, it1,
                        step1, damp1, x_out, x_stage0, err_trace, phase_ticks, G, ws, reinterpret_cast<unsigned*>(ctr ? ctr : nullptr), g_lm_spin_limit,
-                       g_lm_drop_group);
+                       g_lm_drop_group, x_init, prior_mean, prior_weight);
     ETCH_RETURN_IF_LAUNCH_FAILED();
     return ETCH_OK;
 }
@@ -1367,19 +1418,27 @@ int etch_smpl_lm_workspace_bytes(int nj, int nb) {
     return ETCH_EUNSUPPORTED;
 }
 
-// consts: 7 device pointers {J0, Jd, parents, mk_vt, mk_S, mk_P, mk_W}
-int etch_smpl_lm_fit_split(int B, int M, int nj, int nb, const void* const* consts, const float* markers, const float* valid, int it0, float step0,
+// consts: 7 device pointers {J0, Jd, parents, mk_vt, mk_S, mk_P, mk_W}.  x_init / prior_mean / prior_weight: (B, DOF) or NULL.
+int etch_smpl_lm_fit_prior(int B, int M, int nj, int nb, const void* const* consts, const float* markers, const float* valid, int it0, float step0,
                            float damp0, int it1, float step1, float damp1, float* x_out, float* x_stage0, float* err_trace, long long* phase_ticks,
-                           int G, void* workspace, void* stream) {
+                           int G, void* workspace, const float* x_init, const float* prior_mean, const float* prior_weight, void* stream) {
+    if ((prior_mean == nullptr) != (prior_weight == nullptr)) return ETCH_EINVAL;
     if (B <= 0) return ETCH_OK;
     if (M <= 0 || M > LM_MAXM || G < 1 || G > 8) return ETCH_EUNSUPPORTED;
     if (nj == 24 && nb == 10)
         return launch_lm_fit<BodySMPL>(B, M, consts, markers, valid, it0, step0, damp0, it1, step1, damp1, x_out, x_stage0, err_trace, phase_ticks, G,
-                                       workspace, (hipStream_t)stream);
+                                       workspace, x_init, prior_mean, prior_weight, (hipStream_t)stream);
     if (nj == 55 && nb == 20)
         return launch_lm_fit<BodySMPLX>(B, M, consts, markers, valid, it0, step0, damp0, it1, step1, damp1, x_out, x_stage0, err_trace, phase_ticks, G,
-                                        workspace, (hipStream_t)stream);
+                                        workspace, x_init, prior_mean, prior_weight, (hipStream_t)stream);
     return ETCH_EUNSUPPORTED;
+}
+
+int etch_smpl_lm_fit_split(int B, int M, int nj, int nb, const void* const* consts, const float* markers, const float* valid, int it0, float step0,
+                           float damp0, int it1, float step1, float damp1, float* x_out, float* x_stage0, float* err_trace, long long* phase_ticks,
+                           int G, void* workspace, void* stream) {
+    return etch_smpl_lm_fit_prior(B, M, nj, nb, consts, markers, valid, it0, step0, damp0, it1, step1, damp1, x_out, x_stage0, err_trace, phase_ticks,
+                                  G, workspace, nullptr, nullptr, nullptr, stream);
 }
 
 // Test hook of the split fit's failure path: spin_limit = polls before a workgroup gives up (0: the default, ~10 s); drop_group >= 0: that

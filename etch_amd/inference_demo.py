@@ -79,9 +79,8 @@ def predict_smpl(args, model, points, gender="neutral"):
     return meshes[0], info
 
 
-def parse_args(argv=None):
-    parser = argparse.ArgumentParser()
-    parser.add_argument("--scan_path", type=str, required=True, help="Path to input scan OBJ file")
+def add_flags(parser):
+    """Every flag of this command but --scan_path (etch_amd.track takes the same ones for a list of scans)."""
     parser.add_argument("--gender", type=str, default="neutral", choices=["neutral", "male", "female"])
     parser.add_argument("--model_path", type=str, default="", help="Path to trained model")
     parser.add_argument("--markerset_path", default="datafolder/useful_data_4d-dress/superset_smpl.json", type=str)
@@ -102,7 +101,13 @@ def parse_args(argv=None):
     parser.add_argument("--ingest", type=str, default=argparse.SUPPRESS, choices=["host", "device"],
                         help="host (default): the Python OBJ reader / writer and the numpy sampler; device: the native reader and writer and "
                              "the GPU sampler keyed by --seed (etch_amd.mesh_io; same distribution, other points)")
-    return parser.parse_args(argv)
+    return parser
+
+
+def parse_args(argv=None):
+    parser = argparse.ArgumentParser()
+    parser.add_argument("--scan_path", type=str, required=True, help="Path to input scan OBJ file")
+    return add_flags(parser).parse_args(argv)
 
 
 def _refine_and_save(args, model, points, centered_mesh, original_center, scan_name, export=Mesh.export):

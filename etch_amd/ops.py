@@ -1076,11 +1076,42 @@ def lm_split_default(B, nj):
     return LM_SPLIT_WGS_BY_JOINTS.get(int(nj), LM_SPLIT_WGS) if B <= LM_SPLIT_MAX_BATCH else 1
 
 
-def smpl_lm_fit(consts, markers, valid_f, it0, step0, damp0, it1, step1, damp1, want_trace=False, phase_ticks=None, nj=24, nb=10, split=None):
+def _lm_dof_arg(t, name, B, dof, like):
+    """Host-side checks of an optional (B, DOF) input of the LM fit: no launch happens before they pass."""
+    if not isinstance(t, torch.Tensor):
+        raise _lib.EtchHipError(f"{name} must be a tensor of shape ({B}, {dof})")
+    if tuple(t.shape) != (B, dof):
+        raise _lib.EtchHipError(f"{name} must have shape ({B}, {dof}), got {tuple(t.shape)}")
+    if t.dtype != torch.float32 or t.device != like.device or not t.is_contiguous():
+        raise _lib.EtchHipError(f"{name} must be a contiguous float32 tensor on {like.device}")
+    return t
+
+
+def smpl_lm_fit(consts, markers, valid_f, it0, step0, damp0, it1, step1, damp1, want_trace=False, phase_ticks=None, nj=24, nb=10, split=None,
+                x_init=None, prior=None, check=True):
     """x (B, 3 nj + nb + 3) = pose | betas | orient | transl.  (nj, nb) = (24, 10) SMPL or (55, 20) SMPL-X-sized.
-    split = workgroups per scan (None: lm_split_default -- 3 / 4 when B <= LM_SPLIT_MAX_BATCH, else one persistent workgroup per scan)."""
+    split = workgroups per scan (None: lm_split_default -- 3 / 4 when B <= LM_SPLIT_MAX_BATCH, else one persistent workgroup per scan).
+    x_init (B, DOF): the starting point instead of 0 (stage 0 still evaluates with betas[2:] = 0 and hands them to stage 1 unchanged).
+    prior = (mean, weight), both (B, DOF), weight >= 0: adds 0.5 sum_i w_i (x_i - mean_i)^2 over each stage's active variables to the
+    objective; the trace then holds the full objective.  check=True (the default) rejects negative or non-finite weights and non-finite
+    means / x_init: ONE device-to-host read that synchronises the stream -- pass check=False on a pipelined path that guarantees them itself.
+    With x_init and prior both None this is the call it always was (etch_smpl_lm_fit_split)."""
     B, M = valid_f.shape
     dof = 3 * nj + nb + 3
+    if prior is not None:
+        if not isinstance(prior, (tuple, list)) or len(prior) != 2 or prior[0] is None or prior[1] is None:
+            raise _lib.EtchHipError("prior must be (mean, weight): a mean without a weight (or the reverse) is not a prior")
+        _lm_dof_arg(prior[0], "prior mean", B, dof, markers), _lm_dof_arg(prior[1], "prior weight", B, dof, markers)
+    if x_init is not None:
+        _lm_dof_arg(x_init, "x_init", B, dof, markers)
+    if check and (prior is not None or x_init is not None):
+        bad = torch.zeros((), dtype=torch.bool, device=markers.device)
+        if prior is not None:
+            bad = bad | ~torch.isfinite(prior[0]).all() | ~(torch.isfinite(prior[1]) & (prior[1] >= 0)).all()
+        if x_init is not None:
+            bad = bad | ~torch.isfinite(x_init).all()
+        if bool(bad):           # synchronises
+            raise _lib.EtchHipError("smpl_lm_fit: prior weights must be finite and >= 0, prior means and x_init finite")
     arr = (ctypes.c_void_p * 7)(*[t.data_ptr() for t in consts])
     x = torch.empty((B, dof), dtype=torch.float32, device=markers.device)
     x0 = torch.empty((B, dof), dtype=torch.float32, device=markers.device)
@@ -1092,9 +1123,16 @@ def smpl_lm_fit(consts, markers, valid_f, it0, step0, damp0, it1, step1, damp1, 
     if G > 1:
         nbytes = _lib.lib().etch_smpl_lm_split_workspace_bytes(B, int(nj), int(nb), G)
         ws = torch.empty((nbytes // 8 + 1,), dtype=torch.float64, device=markers.device)
-    _lib.check(_lib.lib().etch_smpl_lm_fit_split(B, M, int(nj), int(nb), arr, _ptr(markers), _ptr(valid_f), int(it0), _c_float(step0), _c_float(damp0),
-                                                 int(it1), _c_float(step1), _c_float(damp1), _ptr(x), _ptr(x0), _optptr(tr), _optptr(phase_ticks),
-                                                 G, _optptr(ws), _stream()), "etch_smpl_lm_fit_split")
+    if x_init is None and prior is None:
+        _lib.check(_lib.lib().etch_smpl_lm_fit_split(B, M, int(nj), int(nb), arr, _ptr(markers), _ptr(valid_f), int(it0), _c_float(step0), _c_float(damp0),
+                                                     int(it1), _c_float(step1), _c_float(damp1), _ptr(x), _ptr(x0), _optptr(tr), _optptr(phase_ticks),
+                                                     G, _optptr(ws), _stream()), "etch_smpl_lm_fit_split")
+    else:
+        mean, weight = prior if prior is not None else (None, None)
+        _lib.check(_lib.lib().etch_smpl_lm_fit_prior(B, M, int(nj), int(nb), arr, _ptr(markers), _ptr(valid_f), int(it0), _c_float(step0), _c_float(damp0),
+                                                     int(it1), _c_float(step1), _c_float(damp1), _ptr(x), _ptr(x0), _optptr(tr), _optptr(phase_ticks),
+                                                     G, _optptr(ws), _optptr(x_init), _optptr(mean), _optptr(weight), _stream()),
+                   "etch_smpl_lm_fit_prior")
     x._etch_split_ws = ws       # the split fit's workspace carries the per-scan give-up flags (smpl_lm_split_failed); None for one workgroup per scan
     return x, x0, tr
 

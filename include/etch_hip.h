@@ -628,6 +628,15 @@ int etch_smpl_lm_fit(int B, int M, int nj, int nb, const void* const* consts, co
 int etch_smpl_lm_fit_split(int B, int M, int nj, int nb, const void* const* consts, const float* markers, const float* valid, int it0, float step0,
                            float damp0, int it1, float step1, float damp1, float* x_out, float* x_stage0, float* err_trace, long long* phase_ticks,
                            int G, void* workspace, void* stream);
+/* The same fit (G workgroups per scan, G = 1: workspace may be NULL) with an optional warm start and an optional diagonal Gaussian prior, each
+ * (B, DOF) fp32 in x's layout, NULL = absent.  x_init: the fit starts there instead of at 0; stage 0 evaluates with betas[2:] = 0 as always
+ * (they do not move and get no prior) and hands them to stage 1 at their x_init value, so with it0 = 0 x_stage0 = x_init bitwise.
+ * prior_mean / prior_weight (w >= 0, the caller's duty): the objective becomes 0.5 |r|^2 + 0.5 sum_i w_i (x_i - mean_i)^2 over the stage's
+ * active variables -- added to the normal equations in fp64 after every linearisation, before the damping -- and that sum is what the
+ * convergence freeze and err_trace see.  Exactly one of the two non-NULL: ETCH_EINVAL.  All three NULL: etch_smpl_lm_fit_split. */
+int etch_smpl_lm_fit_prior(int B, int M, int nj, int nb, const void* const* consts, const float* markers, const float* valid, int it0, float step0,
+                           float damp0, int it1, float step1, float damp1, float* x_out, float* x_stage0, float* err_trace, long long* phase_ticks,
+                           int G, void* workspace, const float* x_init, const float* prior_mean, const float* prior_weight, void* stream);
 /* Failure path of the split fit.  A workgroup that waits longer than its spin limit for its partners (they were not co-resident: another kernel, a CU
  * partition) flags the scan and every workgroup of the scan abandons the fit: the scan's x_out / x_stage0 / err_trace rows are NaN -- never a fit of
  * partial sums -- and the flag stays set in the workspace.  etch_smpl_lm_split_failed counts the flagged scans (synchronises the stream).
