@@ -10,6 +10,9 @@
 //                      through all iterations.
 //                      etch_smpl_lm_fit_prior: the same fit warm-started at a caller's x and / or under a diagonal Gaussian prior
 //                      (lm_add_prior) -- what the sequence tracker (etch_amd/sequence.py) runs; no counterpart in the reference.
+//                      etch_smpl_lm_fit_pose_prior / etch_smpl_adam_fit_prior / etch_pose_prior_eval: the fits under the reference's pose priors
+//                      (src/utils/prior.py: MaxMixturePrior's max-mixture GMM, SMPLifyAnglePrior's elbow / knee terms; fit_SMPL_Adam.py:141-153
+//                      for the Adam fitter's two terms) -- lm_add_pose_prior; DESIGN 14.
 //   etch_smpl_lbs      the final smpl_model(...) call (fit_SMPL.py:258-259): vertices (B,V,3) and the joints.
 //
 // Body models: the kernels are templated on (joints NJ, shape coefficients NB) and instantiated for SMPL (24, 10: the
@@ -114,6 +117,28 @@ struct LmSplit {
     unsigned spin_limit;    // polls before a workgroup gives up waiting for its partners
 };
 
+// Pose prior of the fits: a max-mixture GMM on x[:D] and exponential joint-angle terms.  The tables are shared by all scans and
+// stay in global memory (L2-resident; G D^2 fp32 <= 305 KB).  Passed to the kernels by value; G = 0 / n_ang = 0: that part is absent.
+#define LM_PP_MAXG 16
+#define LM_PP_MAXANG 8
+#define LM_PP_MAXD 162                // NPOSE of the largest instantiation
+struct PosePriorDesc {
+    const float* means;     // [G][D]
+    const float* prec;      // [G][D][D], symmetric
+    const float* nllw;      // [G]  c_k > 0
+    const int* ang_idx;     // [n_ang] indices into x[:NPOSE]
+    const float* ang_sign;  // [n_ang]
+    int G, D, n_ang;
+    float w_gmm, w_ang;
+};
+struct LmPosePrior {                  // LDS state of lm_add_pose_prior
+    PosePriorDesc d;
+    double q[LM_PP_MAXG];             // the G brackets 0.5 d_k^T P_k d_k - log c_k
+    double g[LM_PP_MAXD];             // P_k* d_k* (the bracket's gradient)
+    double val;                       // the selected bracket
+    int k;                            // k* = argmin, ties to the lowest index
+};
+
 template <class BM>
 struct LmShared {
     union {
@@ -137,6 +162,14 @@ struct LmShared {
                                       // LAST, so that every offset the phases use is what it was
     const float* prior_mean;
     const float* prior_weight;
+};
+
+// The fit kernels' dynamic LDS: LmShared as it always was, then the pose prior's state BEHIND it -- LmShared keeps its type, its size and
+// every offset the phases use.
+template <class BM>
+struct LmSmem {
+    LmShared<BM> s;
+    LmPosePrior pp;
 };
 
 __device__ inline double& Apk(double* A, int i, int j) { return A[i * (i + 1) / 2 + j]; }   // i >= j
@@ -939,6 +972,79 @@ __device__ __attribute__((noinline)) void lm_add_prior(LmShared<BM>& s, int nb) 
     __syncthreads();
 }
 
+// Max-mixture pose prior and joint-angle terms at x = s.x, in fp64.  Always: p.q[k] = 0.5 d_k^T P_k d_k - log c_k for the G components
+// (d_k = x[:D] - mu_k), p.k = argmin (ties: lowest index), p.val = p.q[p.k], p.g = P_k* d_k*.  With to_normal, on A = s.A (the packed normal
+// equations lm_linearize left, row DOF = -J^T r) and err = s.err: the Gauss-Newton rows of the selected component and of the angle terms are added --
+//     A_ij += w_gmm P_k*,ij,  rhs_i -= w_gmm (P_k* d_k*)_i,  err += w_gmm p.val,
+//     e_t = 2 w_ang exp(2 s_t x[a_t]):  A_aa += e_t,  rhs_a -= s_t e_t,  err += e_t / 2
+// -- before lm_solve adds lambda.  A wave per component, a lane per row (P is symmetric: lane i walks COLUMN i, so a wave's loads are contiguous);
+// every sum runs in an order fixed by (G, D, n_ang) alone, so the workgroups of a split scan stay bit-identical.  All threads must call it.
+// Out of line like lm_add_prior, and with the same two LDS objects at every call site of an instantiation (s, and p behind it: LmSmem), so that
+// the compiler still folds them to constants in the phases.
+template <class BM>
+__device__ __attribute__((noinline)) void lm_add_pose_prior(LmShared<BM>& s, LmPosePrior& p, bool to_normal) {
+    constexpr int dof = BM::DOF, nwaves = BM::WAVES, nthreads = BM::THREADS;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const double* x = s.x;
+    double* A = to_normal ? s.A : nullptr;
+    double* err = &s.err;
+    const int G = p.d.G, D = p.d.D;
+    if (G > 0) {
+        for (int k = wave; k < G; k += nwaves) {
+            const float* __restrict__ Pk = p.d.prec + (size_t)k * D * D;
+            const float* __restrict__ mk = p.d.means + (size_t)k * D;
+            double acc = 0.0;
+            for (int i0 = 0; i0 < D; i0 += 64) {
+                const int i = i0 + lane;
+                if (i < D) {
+                    double pd = 0.0;
+                    for (int j = 0; j < D; ++j) pd += (double)Pk[(size_t)j * D + i] * (x[j] - (double)mk[j]);
+                    acc += pd * (x[i] - (double)mk[i]);
+                }
+            }
+            acc = wave_sum_f64(acc);
+            if (lane == 0) p.q[k] = 0.5 * acc - log((double)p.d.nllw[k]);
+        }
+        __syncthreads();
+        int ks = 0;
+        double qs = p.q[0];
+        for (int k = 1; k < G; ++k) { const double qk = p.q[k]; if (qk < qs) { qs = qk; ks = k; } }
+        const float* __restrict__ Pk = p.d.prec + (size_t)ks * D * D;
+        const float* __restrict__ mk = p.d.means + (size_t)ks * D;
+        for (int i = tid; i < D; i += nthreads) {
+            double pd = 0.0;
+            for (int j = 0; j < D; ++j) pd += (double)Pk[(size_t)j * D + i] * (x[j] - (double)mk[j]);
+            p.g[i] = pd;
+        }
+        if (tid == 0) { p.k = ks; p.val = qs; }
+        __syncthreads();
+        if (A) {
+            const double w = (double)p.d.w_gmm;
+            for (int e = tid; e < D * D; e += nthreads) {
+                const int i = e / D, j = e - i * D;
+                if (j <= i) Apk(A, i, j) += w * (double)Pk[e];
+            }
+            for (int i = tid; i < D; i += nthreads) Apk(A, dof, i) -= w * p.g[i];
+            __syncthreads();                   // the angle terms below touch the same entries
+        }
+    }
+    if (A && tid == 0) {
+        double e_sum = *err;
+        if (G > 0) e_sum += (double)p.d.w_gmm * p.val;
+        for (int t = 0; t < p.d.n_ang; ++t) {
+            const int a = p.d.ang_idx[t];
+            if (a < 0 || a >= BM::NPOSE) continue;       // (the host refuses such an index; never write outside the matrix)
+            const double sg = (double)p.d.ang_sign[t];
+            const double e = 2.0 * (double)p.d.w_ang * exp(2.0 * sg * x[a]);
+            Apk(A, a, a) += e;
+            Apk(A, dof, a) -= sg * e;
+            e_sum += 0.5 * e;
+        }
+        *err = e_sum;
+    }
+    __syncthreads();
+}
+
 template <class BM>
 __global__ void __launch_bounds__(BM::THREADS) smpl_lm_fit_kernel(SmplConsts C, int M, const float* __restrict__ markers,
                                                                 const float* __restrict__ valid, int it0, float step0, float damp0,
@@ -946,11 +1052,13 @@ __global__ void __launch_bounds__(BM::THREADS) smpl_lm_fit_kernel(SmplConsts C, 
                                                                 float* __restrict__ x_stage0, float* __restrict__ err_trace, long long* __restrict__ phase_out,
                                                                 int G, double* __restrict__ split_ws, unsigned* __restrict__ split_ctr,
                                                                 unsigned spin_limit, int drop_group, const float* __restrict__ x_init,
-                                                                const float* __restrict__ prior_mean, const float* __restrict__ prior_weight) {
+                                                                const float* __restrict__ prior_mean, const float* __restrict__ prior_weight,
+                                                                PosePriorDesc pp) {
     constexpr int DOF = BM::DOF;
     constexpr int NB0 = BM::NB < NB_STAGE0 ? BM::NB : NB_STAGE0;
     extern __shared__ __attribute__((aligned(16))) unsigned char lm_smem[];
     LmShared<BM>& s = *reinterpret_cast<LmShared<BM>*>(lm_smem);
+    LmPosePrior& spp = *reinterpret_cast<LmPosePrior*>(lm_smem + offsetof(LmSmem<BM>, pp));
     const int b = blockIdx.x / G, tid = threadIdx.x;
     const bool lead = blockIdx.x % G == 0;                      // the scan's workgroup that writes the results (all G hold the same state)
     if (G > 1 && (int)(blockIdx.x % G) == drop_group) return;   // test hook (etch_smpl_lm_debug): a partner that never becomes resident
@@ -959,7 +1067,8 @@ __global__ void __launch_bounds__(BM::THREADS) smpl_lm_fit_kernel(SmplConsts C, 
         s.split_failed = 0;
     }
     if (!lead) { x_stage0 = nullptr; err_trace = nullptr; phase_out = nullptr; }
-    const bool has_init = x_init != nullptr, has_prior = prior_weight != nullptr;
+    const bool has_init = x_init != nullptr, has_prior = prior_weight != nullptr, has_pp = pp.G > 0 || pp.n_ang > 0;
+    if (has_pp && tid == 0) spp.d = pp;
     if (tid == 0) {
         s.x_init = has_init ? x_init + (size_t)b * DOF : nullptr;
         s.prior_mean = has_prior ? prior_mean + (size_t)b * DOF : nullptr;
@@ -992,6 +1101,7 @@ __global__ void __launch_bounds__(BM::THREADS) smpl_lm_fit_kernel(SmplConsts C, 
                 lm_linearize(s, M, nb, nullptr, false, G > 1);
                 if (G > 1 && s.split_failed) break;            // abandoned (uniform): fall through to the NaN write-out
                 if (has_prior) lm_add_prior(s, nb);   // uniform over the launch; absent: today's instruction stream
+                if (has_pp) lm_add_pose_prior(s, spp, true);   // likewise
                 const float err = (float)s.err;
                 if (it >= 0) {
                     const float a = fabsf(last - err);
@@ -1042,11 +1152,15 @@ template <class BM>
 __global__ void __launch_bounds__(BM::THREADS) smpl_adam_fit_kernel(SmplConsts C, int M, int B, const float* __restrict__ markers,
                                                                   const float* __restrict__ valid, int it0, int it1, float lr, float beta1,
                                                                   float beta2, float eps, float* __restrict__ x_out, float* __restrict__ x_last,
-                                                                  float* __restrict__ loss_trace) {
+                                                                  float* __restrict__ loss_trace, PosePriorDesc pp, float w_pp, float w_ms) {
     constexpr int DOF = BM::DOF;
     extern __shared__ __attribute__((aligned(16))) unsigned char lm_smem[];
     LmShared<BM>& s = *reinterpret_cast<LmShared<BM>*>(lm_smem);
+    LmPosePrior& spp = *reinterpret_cast<LmPosePrior*>(lm_smem + offsetof(LmSmem<BM>, pp));
     const int b = blockIdx.x, tid = threadIdx.x;
+    // the reference's two optional loss terms (fit_SMPL_Adam.py:141-153, 202-214): w_pp * sum_b min_k [.] and w_ms * mean(betas_active^2)
+    const bool has_pp = pp.G > 0, has_ms = w_ms != 0.f;             // uniform over the launch; both absent: today's instruction stream
+    if (has_pp && tid == 0) spp.d = pp;
     for (int i = tid; i < DOF; i += BM::THREADS) s.x[i] = 0.0;
     lm_setup(s, C, M, markers + (size_t)b * M * 3, valid + (size_t)b * M);
     // n = number of valid marker coordinates of the whole batch (every workgroup counts them: B * M flags)
@@ -1073,11 +1187,25 @@ __global__ void __launch_bounds__(BM::THREADS) smpl_adam_fit_kernel(SmplConsts C
             if (x_last && it == iters - 1 && (stage == 1 || it1 == 0))
                 for (int i = tid; i < DOF; i += BM::THREADS) x_last[(size_t)b * DOF + i] = (float)s.x[i];
             lm_linearize(s, M, nb, nullptr, true);
-            if (loss_trace && tid == 0) loss_trace[(size_t)b * (it0 + it1) + trace_pos] = (float)(2.0 * s.err * ninv);   // this scan's share of L
+            if (has_pp) lm_add_pose_prior(s, spp, false);        // value and gradient only
+            const double msc = has_ms ? (double)w_ms / ((double)B * (double)nb) : 0.0;   // mean over the batch's B * nb active coefficients
+            if (has_pp || has_ms) {
+                if (loss_trace && tid == 0) {
+                    double l = 2.0 * s.err * ninv;
+                    if (has_pp) l += (double)w_pp * spp.val;
+                    if (has_ms) { double sq = 0.0; for (int i = 0; i < nb; ++i) sq += s.x[BM::NPOSE + i] * s.x[BM::NPOSE + i]; l += msc * sq; }
+                    loss_trace[(size_t)b * (it0 + it1) + trace_pos] = (float)l;
+                }
+                __syncthreads();               // the betas are read above before the step below moves them
+            } else if (loss_trace && tid == 0) {
+                loss_trace[(size_t)b * (it0 + it1) + trace_pos] = (float)(2.0 * s.err * ninv);   // this scan's share of L
+            }
             ++trace_pos;
             b1t *= (double)beta1; b2t *= (double)beta2;
             for (int i = tid; i < DOF; i += BM::THREADS) {
-                const double g = -2.0 * ninv * Apk(s.A, DOF, i);           // row DOF of the packed matrix holds -J^T r
+                double g = -2.0 * ninv * Apk(s.A, DOF, i);                 // row DOF of the packed matrix holds -J^T r
+                if (has_pp && i < pp.D) g += (double)w_pp * spp.g[i];
+                if (has_ms && i >= BM::NPOSE && i < BM::NPOSE + nb) g += 2.0 * msc * s.x[i];
                 const double m1 = (double)beta1 * mom[i] + (1.0 - (double)beta1) * g;
                 const double v1 = (double)beta2 * var[i] + (1.0 - (double)beta2) * g * g;
                 mom[i] = m1; var[i] = v1;
@@ -1113,6 +1241,23 @@ __global__ void __launch_bounds__(BM::THREADS) smpl_lm_linearize_kernel(SmplCons
             const int i = e / (DOF + 1), j = e - i * (DOF + 1);
             normal[(size_t)b * (DOF + 1) * (DOF + 1) + e] = j <= i ? Apk(s.A, i, j) : 0.0;
         }
+}
+
+// lm_add_pose_prior in isolation (tests, MaxMixturePrior.forward): pose (B, D) fp32 -> the bracket's value (B) fp64, the selected component (B)
+// and the gradient P_k* d_k* (B, D) fp64.  One workgroup per row, in the fits' LDS layout (the function's LDS objects are the fits').
+template <class BM>
+__global__ void __launch_bounds__(BM::THREADS) pose_prior_eval_kernel(PosePriorDesc pp, const float* __restrict__ pose, double* __restrict__ value,
+                                                                    int* __restrict__ comp, double* __restrict__ grad) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lm_smem[];
+    LmShared<BM>& s = *reinterpret_cast<LmShared<BM>*>(lm_smem);
+    LmPosePrior& spp = *reinterpret_cast<LmPosePrior*>(lm_smem + offsetof(LmSmem<BM>, pp));
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (tid == 0) spp.d = pp;
+    for (int i = tid; i < pp.D; i += BM::THREADS) s.x[i] = (double)pose[(size_t)b * pp.D + i];
+    __syncthreads();
+    lm_add_pose_prior(s, spp, false);
+    if (tid == 0) { value[b] = spp.val; comp[b] = spp.k; }
+    for (int i = tid; i < pp.D; i += BM::THREADS) grad[(size_t)b * pp.D + i] = spp.g[i];
 }
 
 // rodrigues_d of the LM / LBS kernels on n rotation vectors: R (n,9) fp64 and dR/dtheta_q (n,3,9) -- pinned by the golden
@@ -1329,9 +1474,10 @@ static int g_lm_drop_group = -1;                 // test hook: this group index 
 template <class BM>
 static int launch_lm_fit(int B, int M, const void* const* consts, const float* markers, const float* valid, int it0, float step0, float damp0,
                          int it1, float step1, float damp1, float* x_out, float* x_stage0, float* err_trace, long long* phase_ticks, int G,
-                         void* workspace, const float* x_init, const float* prior_mean, const float* prior_weight, hipStream_t st) {
-    const int lds = (int)sizeof(LmShared<BM>);
-    static_assert(sizeof(LmShared<BM>) <= 160 * 1024, "LM state must fit the 160 KB LDS of a gfx950 CU");
+                         void* workspace, const float* x_init, const float* prior_mean, const float* prior_weight, const PosePriorDesc& pp,
+                         hipStream_t st) {
+    const int lds = (int)sizeof(LmSmem<BM>);
+    static_assert(sizeof(LmSmem<BM>) <= 160 * 1024, "LM state must fit the 160 KB LDS of a gfx950 CU");
     hipError_t e = hipFuncSetAttribute((const void*)smpl_lm_fit_kernel<BM>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return (int)e;
     unsigned* ctr = nullptr;
@@ -1347,7 +1493,7 @@ static int launch_lm_fit(int B, int M, const void* const* consts, const float* m
     }
     hipLaunchKernelGGL(smpl_lm_fit_kernel<BM>, dim3(B * G), dim3(BM::THREADS), lds, st, lm_consts(consts), M, markers, valid, it0, step0, damp0, it1,
                        step1, damp1, x_out, x_stage0, err_trace, phase_ticks, G, ws, reinterpret_cast<unsigned*>(ctr ? ctr : nullptr), g_lm_spin_limit,
-                       g_lm_drop_group, x_init, prior_mean, prior_weight);
+                       g_lm_drop_group, x_init, prior_mean, prior_weight, pp);
     ETCH_RETURN_IF_LAUNCH_FAILED();
     return ETCH_OK;
 }
@@ -1366,12 +1512,13 @@ static int launch_lm_linearize(int B, int M, int nb, const void* const* consts, 
 
 template <class BM>
 static int launch_adam_fit(int B, int M, const void* const* consts, const float* markers, const float* valid, int it0, int it1, float lr,
-                           float beta1, float beta2, float eps, float* x_out, float* x_last, float* loss_trace, hipStream_t st) {
-    const int lds = (int)sizeof(LmShared<BM>);
+                           float beta1, float beta2, float eps, float* x_out, float* x_last, float* loss_trace, const PosePriorDesc& pp, float w_pp,
+                           float w_ms, hipStream_t st) {
+    const int lds = (int)sizeof(LmSmem<BM>);
     hipError_t e = hipFuncSetAttribute((const void*)smpl_adam_fit_kernel<BM>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(smpl_adam_fit_kernel<BM>, dim3(B), dim3(BM::THREADS), lds, st, lm_consts(consts), M, B, markers, valid, it0, it1, lr, beta1,
-                       beta2, eps, x_out, x_last, loss_trace);
+                       beta2, eps, x_out, x_last, loss_trace, pp, w_pp, w_ms);
     ETCH_RETURN_IF_LAUNCH_FAILED();
     return ETCH_OK;
 }
@@ -1413,8 +1560,37 @@ int etch_marker_status(int B, int M, const float* markers, const float* valid_f,
 }
 
 int etch_smpl_lm_workspace_bytes(int nj, int nb) {
-    if (nj == 24 && nb == 10) return (int)sizeof(LmShared<BodySMPL>);
-    if (nj == 55 && nb == 20) return (int)sizeof(LmShared<BodySMPLX>);
+    if (nj == 24 && nb == 10) return (int)sizeof(LmSmem<BodySMPL>);
+    if (nj == 55 && nb == 20) return (int)sizeof(LmSmem<BodySMPLX>);
+    return ETCH_EUNSUPPORTED;
+}
+
+// Checks of a pose-prior descriptor against a model's NPOSE; tables: {means, precisions, nll_weights, angle_idx, angle_sign} (the last two may be
+// absent from a 3-entry array when n_ang = 0: they are not read then).
+static int pose_prior_desc(const void* const* tables, int G, int D, int n_ang, float w_gmm, float w_ang, int npose, PosePriorDesc* out) {
+    if (G < 0 || n_ang < 0 || (G == 0 && n_ang == 0) || G > LM_PP_MAXG || n_ang > LM_PP_MAXANG) return ETCH_EINVAL;
+    if (G > 0 && (D < 1 || D > npose)) return ETCH_EINVAL;
+    if (!tables) return ETCH_EINVAL;
+    if (G > 0 && (!tables[0] || !tables[1] || !tables[2])) return ETCH_EINVAL;
+    if (n_ang > 0 && (!tables[3] || !tables[4])) return ETCH_EINVAL;
+    *out = PosePriorDesc{G > 0 ? (const float*)tables[0] : nullptr, G > 0 ? (const float*)tables[1] : nullptr, G > 0 ? (const float*)tables[2] : nullptr,
+                         n_ang > 0 ? (const int*)tables[3] : nullptr, n_ang > 0 ? (const float*)tables[4] : nullptr, G, G > 0 ? D : 0, n_ang, w_gmm, w_ang};
+    return ETCH_OK;
+}
+
+static int lm_fit_dispatch(int B, int M, int nj, int nb, const void* const* consts, const float* markers, const float* valid, int it0, float step0,
+                           float damp0, int it1, float step1, float damp1, float* x_out, float* x_stage0, float* err_trace, long long* phase_ticks,
+                           int G, void* workspace, const float* x_init, const float* prior_mean, const float* prior_weight, const PosePriorDesc& pp,
+                           void* stream) {
+    if ((prior_mean == nullptr) != (prior_weight == nullptr)) return ETCH_EINVAL;
+    if (B <= 0) return ETCH_OK;
+    if (M <= 0 || M > LM_MAXM || G < 1 || G > 8) return ETCH_EUNSUPPORTED;
+    if (nj == 24 && nb == 10)
+        return launch_lm_fit<BodySMPL>(B, M, consts, markers, valid, it0, step0, damp0, it1, step1, damp1, x_out, x_stage0, err_trace, phase_ticks, G,
+                                       workspace, x_init, prior_mean, prior_weight, pp, (hipStream_t)stream);
+    if (nj == 55 && nb == 20)
+        return launch_lm_fit<BodySMPLX>(B, M, consts, markers, valid, it0, step0, damp0, it1, step1, damp1, x_out, x_stage0, err_trace, phase_ticks, G,
+                                        workspace, x_init, prior_mean, prior_weight, pp, (hipStream_t)stream);
     return ETCH_EUNSUPPORTED;
 }
 
@@ -1422,16 +1598,38 @@ int etch_smpl_lm_workspace_bytes(int nj, int nb) {
 int etch_smpl_lm_fit_prior(int B, int M, int nj, int nb, const void* const* consts, const float* markers, const float* valid, int it0, float step0,
                            float damp0, int it1, float step1, float damp1, float* x_out, float* x_stage0, float* err_trace, long long* phase_ticks,
                            int G, void* workspace, const float* x_init, const float* prior_mean, const float* prior_weight, void* stream) {
-    if ((prior_mean == nullptr) != (prior_weight == nullptr)) return ETCH_EINVAL;
+    return lm_fit_dispatch(B, M, nj, nb, consts, markers, valid, it0, step0, damp0, it1, step1, damp1, x_out, x_stage0, err_trace, phase_ticks, G, workspace,
+                           x_init, prior_mean, prior_weight, PosePriorDesc{}, stream);
+}
+
+// etch_smpl_lm_fit_prior under a pose prior.  pp_tables: {means (pp_G, pp_D), precisions (pp_G, pp_D, pp_D) symmetric, nll_weights (pp_G),
+// angle_idx (n_ang) int32, angle_sign (n_ang)} device pointers.
+int etch_smpl_lm_fit_pose_prior(int B, int M, int nj, int nb, const void* const* consts, const float* markers, const float* valid, int it0, float step0,
+                                float damp0, int it1, float step1, float damp1, float* x_out, float* x_stage0, float* err_trace, long long* phase_ticks,
+                                int G, void* workspace, const float* x_init, const float* prior_mean, const float* prior_weight,
+                                const void* const* pp_tables, int pp_G, int pp_D, int n_ang, float w_gmm, float w_ang, void* stream) {
+    if (!((nj == 24 && nb == 10) || (nj == 55 && nb == 20))) return ETCH_EUNSUPPORTED;
+    PosePriorDesc pp;
+    const int rc = pose_prior_desc(pp_tables, pp_G, pp_D, n_ang, w_gmm, w_ang, 3 * (nj - 1), &pp);
+    if (rc != ETCH_OK) return rc;
+    return lm_fit_dispatch(B, M, nj, nb, consts, markers, valid, it0, step0, damp0, it1, step1, damp1, x_out, x_stage0, err_trace, phase_ticks, G, workspace,
+                           x_init, prior_mean, prior_weight, pp, stream);
+}
+
+// pose (B, D) -> value (B) fp64, component (B) int32, gradient (B, D) fp64 of the max-mixture bracket; tables: {means, precisions, nll_weights}.
+int etch_pose_prior_eval(int B, const void* const* tables, int G, int D, const float* pose, double* value, int* component, double* grad, void* stream) {
+    PosePriorDesc pp;
+    if (G < 1) return ETCH_EINVAL;
+    const int rc = pose_prior_desc(tables, G, D, 0, 0.f, 0.f, LM_PP_MAXD, &pp);
+    if (rc != ETCH_OK) return rc;
     if (B <= 0) return ETCH_OK;
-    if (M <= 0 || M > LM_MAXM || G < 1 || G > 8) return ETCH_EUNSUPPORTED;
-    if (nj == 24 && nb == 10)
-        return launch_lm_fit<BodySMPL>(B, M, consts, markers, valid, it0, step0, damp0, it1, step1, damp1, x_out, x_stage0, err_trace, phase_ticks, G,
-                                       workspace, x_init, prior_mean, prior_weight, (hipStream_t)stream);
-    if (nj == 55 && nb == 20)
-        return launch_lm_fit<BodySMPLX>(B, M, consts, markers, valid, it0, step0, damp0, it1, step1, damp1, x_out, x_stage0, err_trace, phase_ticks, G,
-                                        workspace, x_init, prior_mean, prior_weight, (hipStream_t)stream);
-    return ETCH_EUNSUPPORTED;
+    if (!pose || !value || !component || !grad) return ETCH_EINVAL;
+    const int lds = (int)sizeof(LmSmem<BodySMPLX>);           // the largest instantiation: D <= its NPOSE
+    hipError_t e = hipFuncSetAttribute((const void*)pose_prior_eval_kernel<BodySMPLX>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(pose_prior_eval_kernel<BodySMPLX>, dim3(B), dim3(BodySMPLX::THREADS), lds, (hipStream_t)stream, pp, pose, value, component, grad);
+    ETCH_RETURN_IF_LAUNCH_FAILED();
+    return ETCH_OK;
 }
 
 int etch_smpl_lm_fit_split(int B, int M, int nj, int nb, const void* const* consts, const float* markers, const float* valid, int it0, float step0,
@@ -1478,15 +1676,39 @@ int etch_smpl_lm_fit(int B, int M, int nj, int nb, const void* const* consts, co
                                   nullptr, stream);
 }
 
-int etch_smpl_adam_fit(int B, int M, int nj, int nb, const void* const* consts, const float* markers, const float* valid, int it0, int it1,
-                       float lr, float beta1, float beta2, float eps, float* x_out, float* x_last, float* loss_trace, void* stream) {
+static int adam_fit_dispatch(int B, int M, int nj, int nb, const void* const* consts, const float* markers, const float* valid, int it0, int it1,
+                             float lr, float beta1, float beta2, float eps, float* x_out, float* x_last, float* loss_trace, const PosePriorDesc& pp,
+                             float w_pp, float w_ms, void* stream) {
     if (B <= 0) return ETCH_OK;
     if (M <= 0 || M > LM_MAXM) return ETCH_EUNSUPPORTED;
     if (nj == 24 && nb == 10)
-        return launch_adam_fit<BodySMPL>(B, M, consts, markers, valid, it0, it1, lr, beta1, beta2, eps, x_out, x_last, loss_trace, (hipStream_t)stream);
+        return launch_adam_fit<BodySMPL>(B, M, consts, markers, valid, it0, it1, lr, beta1, beta2, eps, x_out, x_last, loss_trace, pp, w_pp, w_ms,
+                                         (hipStream_t)stream);
     if (nj == 55 && nb == 20)
-        return launch_adam_fit<BodySMPLX>(B, M, consts, markers, valid, it0, it1, lr, beta1, beta2, eps, x_out, x_last, loss_trace, (hipStream_t)stream);
+        return launch_adam_fit<BodySMPLX>(B, M, consts, markers, valid, it0, it1, lr, beta1, beta2, eps, x_out, x_last, loss_trace, pp, w_pp, w_ms,
+                                          (hipStream_t)stream);
     return ETCH_EUNSUPPORTED;
+}
+
+int etch_smpl_adam_fit(int B, int M, int nj, int nb, const void* const* consts, const float* markers, const float* valid, int it0, int it1,
+                       float lr, float beta1, float beta2, float eps, float* x_out, float* x_last, float* loss_trace, void* stream) {
+    return adam_fit_dispatch(B, M, nj, nb, consts, markers, valid, it0, it1, lr, beta1, beta2, eps, x_out, x_last, loss_trace, PosePriorDesc{}, 0.f, 0.f,
+                             stream);
+}
+
+// etch_smpl_adam_fit with the reference's two optional loss terms: w_pp * sum_b min_k [0.5 d^T P_k d - log c_k] on pose[:pp_D] (pp_tables: {means,
+// precisions, nll_weights}; pp_G = 0: absent) and w_ms * mean(active betas^2).  Neither: ETCH_EINVAL.
+int etch_smpl_adam_fit_prior(int B, int M, int nj, int nb, const void* const* consts, const float* markers, const float* valid, int it0, int it1,
+                             float lr, float beta1, float beta2, float eps, float* x_out, float* x_last, float* loss_trace,
+                             const void* const* pp_tables, int pp_G, int pp_D, float w_pp, float w_ms, void* stream) {
+    if (!((nj == 24 && nb == 10) || (nj == 55 && nb == 20))) return ETCH_EUNSUPPORTED;
+    if (pp_G < 0 || pp_G > LM_PP_MAXG || (pp_G == 0 && w_ms == 0.f)) return ETCH_EINVAL;
+    PosePriorDesc pp{};
+    if (pp_G > 0) {
+        const int rc = pose_prior_desc(pp_tables, pp_G, pp_D, 0, w_pp, 0.f, 3 * (nj - 1), &pp);
+        if (rc != ETCH_OK) return rc;
+    }
+    return adam_fit_dispatch(B, M, nj, nb, consts, markers, valid, it0, it1, lr, beta1, beta2, eps, x_out, x_last, loss_trace, pp, w_pp, w_ms, stream);
 }
 
 int etch_smpl_lm_linearize(int B, int M, int nj, int nb_model, int nb_active, const void* const* consts, const float* x, const float* markers,

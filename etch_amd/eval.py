@@ -181,7 +181,9 @@ def evaluate_batch(args, model, hitpts, gender_list, ids=None, gt_vertices=None,
         results, _ = model(hitpts, pred_items=["confidence", "direction", "magnitude"], direction_mode="standard_vector")
         labels = ops.argmax_rows(results["part_labels"])
         inner = ops.inner_points(hitpts.contiguous(), results["direction"], results["magnitude"], float(args.scale_magnitude))
-        meshes, markers, valid, info = fit_smpl_by_gender(args, inner, labels, results["confidences"], gender_list)
+        pp = getattr(args, "fit_pose_prior", None)              # --pose_prior (main)
+        meshes, markers, valid, info = fit_smpl_by_gender(args, inner, labels, results["confidences"], gender_list,
+                                                          **({} if pp is None else {"pose_prior": pp}))
     out = []
     vsum = valid.sum(1).tolist()
     for j in range(B):
@@ -227,6 +229,8 @@ def build_parser():
                         help="device: native OBJ reader one batch ahead on worker threads, GPU surface sampler, native writer; host: the Python "
                              "reader and writer and the numpy sampler, one scan at a time")
     parser.add_argument("--prefetch", type=int, default=1, help="--ingest device: batches read ahead of the GPU (0: none)")
+    from .utils.prior import add_pose_prior_flags
+    add_pose_prior_flags(parser)
     return parser
 
 
@@ -246,6 +250,8 @@ def main(argv=None):
     with open(args.markerset_path, "r") as f:
         args.markerset = json.load(f)
     resolve_body_model(args)
+    from .utils.prior import pose_prior_from_args
+    args.fit_pose_prior = pose_prior_from_args(args, args.device)
     if not args.model_path:
         print("WARNING: no --model_path: scoring the seeded INITIAL weights, not a trained model (smoke runs only)", file=sys.stderr)
         args.model_path = ""

@@ -65,6 +65,8 @@ def sample_points_from_mesh(mesh, num_points=5000, seed=0):
 
 def predict_smpl_batch(args, model, points_tensor, gender="neutral", **fit_kwargs):
     """inference_demo.py:41-66 for a batch (B,N,3) already on the device: stage 1 -> labels / inner points -> stage 2."""
+    if getattr(args, "fit_pose_prior", None) is not None:       # --pose_prior (main): the marker fit under the mixture prior
+        fit_kwargs.setdefault("pose_prior", args.fit_pose_prior)
     with torch.no_grad():
         results, _ = model(points_tensor, pred_items=["confidence", "direction", "magnitude"], direction_mode="standard_vector")
         labels = ops.argmax_rows(results["part_labels"])
@@ -101,6 +103,8 @@ def add_flags(parser):
     parser.add_argument("--ingest", type=str, default=argparse.SUPPRESS, choices=["host", "device"],
                         help="host (default): the Python OBJ reader / writer and the numpy sampler; device: the native reader and writer and "
                              "the GPU sampler keyed by --seed (etch_amd.mesh_io; same distribution, other points)")
+    from .utils.prior import add_pose_prior_flags
+    add_pose_prior_flags(parser)
     return parser
 
 
@@ -169,6 +173,8 @@ def main(argv=None):
         from . import constants
         args.markerset = constants.default_markerset()
     resolve_body_model(args)
+    from .utils.prior import pose_prior_from_args
+    args.fit_pose_prior = pose_prior_from_args(args, args.device)
     os.makedirs(args.output_folder, exist_ok=True)
     model = load_model(args)
     export = Mesh.export

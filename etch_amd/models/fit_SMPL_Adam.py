@@ -18,13 +18,19 @@ from .. import ops
 from .fit_SMPL import Mesh, _device_body, _resolve_body_model, get_markers  # noqa: F401  (get_markers: fit_SMPL_Adam.py:17-62, identical)
 
 
-def fit_smpl(args, inner_points, part_labels, confidences, steps_stage0=400, steps_stage1=800, lr=1e-2, return_aux=False):
-    """fit_SMPL_Adam.py:68-225."""
+def fit_smpl(args, inner_points, part_labels, confidences, steps_stage0=400, steps_stage1=800, lr=1e-2, return_aux=False, pose_prior=None,
+             pose_prior_w=1e-7, mean_shape_w=None):
+    """fit_SMPL_Adam.py:68-225.  pose_prior / mean_shape_w are the reference's switches use_pose_prior / use_mean_shape (:79-80), off by default:
+    pose_prior = a utils.prior.MaxMixturePrior or an ops.PosePrior adds pose_prior_w * sum_b prior(pose_b) (the reference's weight: 1e-7),
+    mean_shape_w (the reference's: 1e-2) adds mean_shape_w * mean(optimised betas^2)."""
+    if pose_prior is not None and not isinstance(pose_prior, ops.PosePrior):
+        pose_prior = pose_prior.fit_tables()                    # cached on the module; the Adam fit weighs them with pose_prior_w
     M = len(args.markerset)
     bm = _resolve_body_model(args, "neutral")
     db = _device_body(bm, list(args.markerset.values()), inner_points.device)
     markers, valid_f, valid_b = ops.get_markers(inner_points.contiguous(), part_labels.contiguous(), confidences.contiguous(), M)
-    x, x_last, trace = ops.smpl_adam_fit(db.lm_consts, markers, valid_f, steps_stage0, steps_stage1, lr, want_trace=return_aux, nj=db.nj, nb=db.nb)
+    x, x_last, trace = ops.smpl_adam_fit(db.lm_consts, markers, valid_f, steps_stage0, steps_stage1, lr, want_trace=return_aux, nj=db.nj, nb=db.nb,
+                                         pose_prior=pose_prior, pose_prior_w=pose_prior_w, mean_shape_w=0.0 if mean_shape_w is None else mean_shape_w)
     verts, joints = ops.smpl_lbs(db.lbs_consts, x_last, db.V, db.n_extra, nj=db.nj, nb=db.nb)      # the last forward of the loop (:221-225)
     vn = verts.detach().cpu().numpy()
     meshes = [Mesh(vn[b], db.faces, process=False, maintain_order=True) for b in range(vn.shape[0])]

@@ -1087,17 +1087,130 @@ def _lm_dof_arg(t, name, B, dof, like):
     return t
 
 
+POSE_PRIOR_MAX_G, POSE_PRIOR_MAX_ANG, POSE_PRIOR_MAX_D = 16, 8, 162
+
+
+class PosePrior:
+    """Device tables of the fits' pose prior, built ONCE: a max-mixture GMM min_k [0.5 d_k^T P_k d_k - log c_k] on x[:D] with weight
+    w_gmm (means (G, D), precisions (G, D, D), nll_weights (G) = MaxMixturePrior's buffers; all three None: no GMM) and joint-angle terms
+    w_ang sum_t exp(2 s_t x[a_t]) (angle_idx into the body pose WITHOUT the global orientation, angle_sign; both None: none).
+    The constructor does every value check, on host copies of the tables (the only place this object synchronises): finite tables, nll_weights > 0, weights >= 0, every
+    symmetrised precision positive definite (an indefinite one can make the damped normal matrix indefinite, and the kernel's Cholesky then yields
+    NaN silently).  The precisions are stored symmetrised, 0.5 (P + P^T) formed in fp64 and rounded to fp32.  Calls that take the object only
+    check shapes and the device, and never synchronise."""
+    __slots__ = ("means", "precisions", "nll_weights", "angle_idx", "angle_sign", "G", "D", "n_ang", "w_gmm", "w_ang", "max_angle_idx", "device",
+                 "_tables", "_frozen")
+
+    def __init__(self, means=None, precisions=None, nll_weights=None, w_gmm=0.0, angle_idx=None, angle_sign=None, w_ang=0.0, device="cuda"):
+        err = _lib.EtchHipError
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        w_gmm, w_ang = float(w_gmm), float(w_ang)
+        if not (math.isfinite(w_gmm) and math.isfinite(w_ang) and w_gmm >= 0.0 and w_ang >= 0.0):
+            raise err("PosePrior: w_gmm and w_ang must be finite and >= 0")
+        gmm = [means, precisions, nll_weights]
+        if any(t is None for t in gmm) and not all(t is None for t in gmm):
+            raise err("PosePrior: means, precisions and nll_weights come together")
+        if (angle_idx is None) != (angle_sign is None):
+            raise err("PosePrior: angle_idx and angle_sign come together")
+        if means is None and angle_idx is None:
+            raise err("PosePrior: neither a mixture nor angle terms")
+        host64 = lambda t: torch.as_tensor(t).detach().to("cpu", torch.float64)
+        G = D = 0
+        m32 = p32 = c32 = None
+        if means is not None:
+            m, P, c = host64(means), host64(precisions), host64(nll_weights).reshape(-1)
+            if m.dim() != 2 or P.dim() != 3:
+                raise err(f"PosePrior: means must be (G, D) and precisions (G, D, D), got {tuple(m.shape)} and {tuple(P.shape)}")
+            G, D = m.shape
+            if not 1 <= G <= POSE_PRIOR_MAX_G or not 1 <= D <= POSE_PRIOR_MAX_D:
+                raise err(f"PosePrior: 1 <= G <= {POSE_PRIOR_MAX_G} and 1 <= D <= {POSE_PRIOR_MAX_D}, got G = {G}, D = {D}")
+            if tuple(P.shape) != (G, D, D) or c.numel() != G:
+                raise err(f"PosePrior: precisions must be ({G}, {D}, {D}) and nll_weights ({G}), got {tuple(P.shape)} and {tuple(c.shape)}")
+            if not (torch.isfinite(m).all() and torch.isfinite(P).all() and torch.isfinite(c).all()):
+                raise err("PosePrior: means, precisions and nll_weights must be finite")
+            if not (c > 0).all():
+                raise err("PosePrior: nll_weights must be > 0")
+            p32 = (0.5 * (P + P.transpose(1, 2))).to(torch.float32)
+            if not (torch.linalg.cholesky_ex(p32.double()).info == 0).all():
+                raise err("PosePrior: every (symmetrised) precision matrix must be positive definite")
+            m32, c32 = m.to(torch.float32), c.to(torch.float32)
+            if not (c32 > 0).all():
+                raise err("PosePrior: nll_weights underflow in float32")
+        n_ang, amax, ai, asg = 0, -1, None, None
+        if angle_idx is not None:
+            ai64 = torch.as_tensor(angle_idx).detach().to("cpu")
+            if ai64.dtype.is_floating_point or ai64.dtype == torch.bool:
+                raise err("PosePrior: angle_idx must be integers")
+            ai64, asg64 = ai64.reshape(-1).long(), host64(angle_sign).reshape(-1)
+            n_ang = ai64.numel()
+            if not 1 <= n_ang <= POSE_PRIOR_MAX_ANG or asg64.numel() != n_ang:
+                raise err(f"PosePrior: 1 <= n_ang <= {POSE_PRIOR_MAX_ANG} indices with as many signs, got {n_ang} and {asg64.numel()}")
+            if int(ai64.min()) < 0 or not torch.isfinite(asg64).all():
+                raise err("PosePrior: angle indices must be >= 0 and the signs finite")
+            amax = int(ai64.max())
+            ai, asg = ai64.to(torch.int32), asg64.to(torch.float32)
+        put = lambda t: None if t is None else t.contiguous().to(dev)
+        object.__setattr__(self, "_frozen", False)
+        self.means, self.precisions, self.nll_weights, self.angle_idx, self.angle_sign = put(m32), put(p32), put(c32), put(ai), put(asg)
+        self.G, self.D, self.n_ang, self.w_gmm, self.w_ang, self.max_angle_idx, self.device = int(G), int(D), int(n_ang), w_gmm, w_ang, amax, dev
+        self._tables = (ctypes.c_void_p * 5)(*[None if t is None else t.data_ptr()
+                                               for t in (self.means, self.precisions, self.nll_weights, self.angle_idx, self.angle_sign)])
+        self._frozen = True
+
+    def __setattr__(self, name, value):
+        if getattr(self, "_frozen", False):
+            raise AttributeError("PosePrior is immutable: build a new one")
+        object.__setattr__(self, name, value)
+
+
+def _pose_prior_arg(pp, like, npose, what, need_gmm=False):
+    """Per-call checks of a PosePrior: type, device, sizes against the model.  Host-side only."""
+    if not isinstance(pp, PosePrior):
+        raise _lib.EtchHipError(f"{what}: pose_prior must be an ops.PosePrior")
+    if pp.device != like.device:
+        raise _lib.EtchHipError(f"{what}: pose_prior lives on {pp.device}, the fit on {like.device}")
+    if need_gmm and pp.G == 0:
+        raise _lib.EtchHipError(f"{what}: pose_prior has no mixture")
+    if pp.D > npose:
+        raise _lib.EtchHipError(f"{what}: the prior's dimension {pp.D} exceeds the model's {npose} pose variables")
+    if pp.max_angle_idx >= npose:
+        raise _lib.EtchHipError(f"{what}: angle index {pp.max_angle_idx} is outside the model's {npose} pose variables")
+    return pp
+
+
+def pose_prior_eval(pose, pose_prior):
+    """The max-mixture bracket as the fit kernels evaluate it: pose (B, D) fp32 -> value (B) fp64 = min_k [0.5 d_k^T P_k d_k - log c_k],
+    component (B) int32 (ties: the lowest index), gradient P_k* d_k* (B, D) fp64."""
+    _need(pose, torch.float32, "pose")
+    _pose_prior_arg(pose_prior, pose, POSE_PRIOR_MAX_D, "pose_prior_eval", need_gmm=True)
+    if pose.dim() != 2 or pose.shape[1] != pose_prior.D:
+        raise _lib.EtchHipError(f"pose must be (B, {pose_prior.D}), got {tuple(pose.shape)}")
+    B = pose.shape[0]
+    val = torch.empty((B,), dtype=torch.float64, device=pose.device)
+    comp = torch.empty((B,), dtype=torch.int32, device=pose.device)
+    grad = torch.empty((B, pose_prior.D), dtype=torch.float64, device=pose.device)
+    _lib.check(_lib.lib().etch_pose_prior_eval(B, pose_prior._tables, pose_prior.G, pose_prior.D, _ptr(pose), _ptr(val), _ptr(comp), _ptr(grad),
+                                               _stream()), "etch_pose_prior_eval")
+    return val, comp, grad
+
+
 def smpl_lm_fit(consts, markers, valid_f, it0, step0, damp0, it1, step1, damp1, want_trace=False, phase_ticks=None, nj=24, nb=10, split=None,
-                x_init=None, prior=None, check=True):
+                x_init=None, prior=None, check=True, pose_prior=None):
     """x (B, 3 nj + nb + 3) = pose | betas | orient | transl.  (nj, nb) = (24, 10) SMPL or (55, 20) SMPL-X-sized.
     split = workgroups per scan (None: lm_split_default -- 3 / 4 when B <= LM_SPLIT_MAX_BATCH, else one persistent workgroup per scan).
     x_init (B, DOF): the starting point instead of 0 (stage 0 still evaluates with betas[2:] = 0 and hands them to stage 1 unchanged).
     prior = (mean, weight), both (B, DOF), weight >= 0: adds 0.5 sum_i w_i (x_i - mean_i)^2 over each stage's active variables to the
     objective; the trace then holds the full objective.  check=True (the default) rejects negative or non-finite weights and non-finite
     means / x_init: ONE device-to-host read that synchronises the stream -- pass check=False on a pipelined path that guarantees them itself.
-    With x_init and prior both None this is the call it always was (etch_smpl_lm_fit_split)."""
+    pose_prior: an ops.PosePrior (max-mixture GMM on the pose and / or joint-angle terms), added like the diagonal prior; its values
+    were checked when it was built, so this adds no synchronisation.
+    With x_init, prior and pose_prior all None this is the call it always was (etch_smpl_lm_fit_split)."""
     B, M = valid_f.shape
     dof = 3 * nj + nb + 3
+    if pose_prior is not None:
+        _pose_prior_arg(pose_prior, markers, 3 * (nj - 1), "smpl_lm_fit")
     if prior is not None:
         if not isinstance(prior, (tuple, list)) or len(prior) != 2 or prior[0] is None or prior[1] is None:
             raise _lib.EtchHipError("prior must be (mean, weight): a mean without a weight (or the reverse) is not a prior")
@@ -1123,7 +1236,15 @@ def smpl_lm_fit(consts, markers, valid_f, it0, step0, damp0, it1, step1, damp1, 
     if G > 1:
         nbytes = _lib.lib().etch_smpl_lm_split_workspace_bytes(B, int(nj), int(nb), G)
         ws = torch.empty((nbytes // 8 + 1,), dtype=torch.float64, device=markers.device)
-    if x_init is None and prior is None:
+    if pose_prior is not None:
+        mean, weight = prior if prior is not None else (None, None)
+        pp = pose_prior
+        _lib.check(_lib.lib().etch_smpl_lm_fit_pose_prior(B, M, int(nj), int(nb), arr, _ptr(markers), _ptr(valid_f), int(it0), _c_float(step0),
+                                                          _c_float(damp0), int(it1), _c_float(step1), _c_float(damp1), _ptr(x), _ptr(x0), _optptr(tr),
+                                                          _optptr(phase_ticks), G, _optptr(ws), _optptr(x_init), _optptr(mean), _optptr(weight),
+                                                          pp._tables, pp.G, pp.D, pp.n_ang, _c_float(pp.w_gmm), _c_float(pp.w_ang), _stream()),
+                   "etch_smpl_lm_fit_pose_prior")
+    elif x_init is None and prior is None:
         _lib.check(_lib.lib().etch_smpl_lm_fit_split(B, M, int(nj), int(nb), arr, _ptr(markers), _ptr(valid_f), int(it0), _c_float(step0), _c_float(damp0),
                                                      int(it1), _c_float(step1), _c_float(damp1), _ptr(x), _ptr(x0), _optptr(tr), _optptr(phase_ticks),
                                                      G, _optptr(ws), _stream()), "etch_smpl_lm_fit_split")
@@ -1148,14 +1269,30 @@ def smpl_lm_split_failed(x):
     return int(n.value)
 
 
-def smpl_adam_fit(consts, markers, valid_f, it0, it1, lr=1e-2, beta1=0.9, beta2=0.999, eps=1e-8, want_trace=False, nj=24, nb=10):
-    """First-order fitter (fit_SMPL_Adam.py): -> x (B,DOF), x_last (parameters of the last forward pass), loss trace (B, it0+it1) or None."""
+def smpl_adam_fit(consts, markers, valid_f, it0, it1, lr=1e-2, beta1=0.9, beta2=0.999, eps=1e-8, want_trace=False, nj=24, nb=10,
+                  pose_prior=None, pose_prior_w=1e-7, mean_shape_w=0.0):
+    """First-order fitter (fit_SMPL_Adam.py): -> x (B,DOF), x_last (parameters of the last forward pass), loss trace (B, it0+it1) or None.
+    pose_prior (an ops.PosePrior with a mixture; its own weights are not used here) adds pose_prior_w * sum_b min_k [.] to the loss and
+    mean_shape_w adds mean_shape_w * mean(active betas^2): the reference's use_pose_prior / use_mean_shape (1e-7, 1e-2).  There are no angle terms."""
     B, M = valid_f.shape
     dof = 3 * nj + nb + 3
+    pose_prior_w, mean_shape_w = float(pose_prior_w), float(mean_shape_w)
+    if pose_prior is not None:
+        _pose_prior_arg(pose_prior, markers, 3 * (nj - 1), "smpl_adam_fit", need_gmm=True)
+    if not (math.isfinite(pose_prior_w) and math.isfinite(mean_shape_w) and pose_prior_w >= 0.0 and mean_shape_w >= 0.0):
+        raise _lib.EtchHipError("smpl_adam_fit: pose_prior_w and mean_shape_w must be finite and >= 0")
     arr = (ctypes.c_void_p * 7)(*[t.data_ptr() for t in consts])
     x = torch.empty((B, dof), dtype=torch.float32, device=markers.device)
     xl = torch.empty((B, dof), dtype=torch.float32, device=markers.device)
     tr = torch.zeros((B, it0 + it1), dtype=torch.float32, device=markers.device) if want_trace else None
+    if pose_prior is not None or mean_shape_w != 0.0:
+        pp = pose_prior
+        _lib.check(_lib.lib().etch_smpl_adam_fit_prior(B, M, int(nj), int(nb), arr, _ptr(markers), _ptr(valid_f), int(it0), int(it1), _c_float(lr),
+                                                       _c_float(beta1), _c_float(beta2), _c_float(eps), _ptr(x), _ptr(xl), _optptr(tr),
+                                                       pp._tables if pp is not None else None, pp.G if pp is not None else 0,
+                                                       pp.D if pp is not None else 0, _c_float(pose_prior_w), _c_float(mean_shape_w), _stream()),
+                   "etch_smpl_adam_fit_prior")
+        return x, xl, tr
     _lib.check(_lib.lib().etch_smpl_adam_fit(B, M, int(nj), int(nb), arr, _ptr(markers), _ptr(valid_f), int(it0), int(it1), _c_float(lr),
                                              _c_float(beta1), _c_float(beta2), _c_float(eps), _ptr(x), _ptr(xl), _optptr(tr), _stream()),
                "etch_smpl_adam_fit")

@@ -104,7 +104,7 @@ def sweep_prior(x, idx, offsets, beta_mean, temporal_w, shape_w, nj, nb):
 
 
 def fit_sequence(args, markers, valid, gender, offsets=None, temporal_w=DEFAULT_TEMPORAL_W, shape_w=DEFAULT_SHAPE_W, sweeps=DEFAULT_SWEEPS,
-                 refit_steps=DEFAULT_REFIT_STEPS, steps_stage0=30, steps_stage1=50, lr_stage0=5e-1, lr_stage1=2e-1, want_trace=False):
+                 refit_steps=DEFAULT_REFIT_STEPS, steps_stage0=30, steps_stage1=50, lr_stage0=5e-1, lr_stage1=2e-1, want_trace=False, pose_prior=None):
     """markers (T,M,3), valid (T,M) bool -> the dict of fit_smpl_device (x, verts, joints, ... of the TRACKED sequence; x_stage0 / err_trace of
     pass 0) + x_independent (pass 0's x: bitwise fit_smpl_device's on the same markers), beta_mean (nb,) and status (T,) int32.
 
@@ -115,6 +115,7 @@ def fit_sequence(args, markers, valid, gender, offsets=None, temporal_w=DEFAULT_
        (`refit_steps` iterations), prior mean = mean of the neighbours t +- 1 (weight temporal_w[group] x number of neighbours) for pose /
        orient / transl and beta_mean (weight shape_w) for betas; beta_mean is recomputed after every full sweep.
     4. the final LBS from the final x.
+    pose_prior: an ops.PosePrior handed to pass 0 and to every refit, on top of the temporal prior.
     sweeps = 0 returns pass 0 untouched.  Synchronises (the dead frames are decided on the host): not a pipelined path."""
     from .models.fit_SMPL import _device_body, _resolve_body_model
     temporal_w = tuple(float(w) for w in temporal_w)
@@ -139,7 +140,7 @@ def fit_sequence(args, markers, valid, gender, offsets=None, temporal_w=DEFAULT_
     valid_b = valid.bool().contiguous()
     valid_f = valid_b.float().contiguous()
     x, x0, trace = ops.smpl_lm_fit(db.lm_consts, markers, valid_f, steps_stage0, lr_stage0, 0.01, steps_stage1, lr_stage1, 1e-3, want_trace,
-                                   nj=nj, nb=nb)
+                                   nj=nj, nb=nb, pose_prior=pose_prior)
     status = ops.marker_status(markers, valid_f)
     x_independent = x
     live = (status == 0).cpu()
@@ -157,7 +158,7 @@ def fit_sequence(args, markers, valid, gender, offsets=None, temporal_w=DEFAULT_
                 mean, weight = sweep_prior(x, idx, offsets, beta_mean, temporal_w, shape_w, nj, nb)
                 xi, _, _ = ops.smpl_lm_fit(db.lm_consts, fit_markers[idx].contiguous(), fit_valid[idx].contiguous(), 0, lr_stage0, 0.01,
                                            int(refit_steps), lr_stage1, 1e-3, nj=nj, nb=nb, x_init=x[idx].contiguous(), prior=(mean, weight),
-                                           check=False)      # finite by construction: live or filled frames, weights validated above
+                                           check=False, pose_prior=pose_prior)      # finite by construction: live or filled frames, weights validated above
                 x = x.index_copy(0, idx, xi)
             beta_mean = shape_mean(x, fit_valid, nj, nb)
     else:

@@ -95,6 +95,8 @@ def main(argv=None):
         from . import constants
         args.markerset = constants.default_markerset()
     D.resolve_body_model(args)
+    from .utils.prior import pose_prior_from_args
+    pose_prior = pose_prior_from_args(args, args.device)
     os.makedirs(args.output_folder, exist_ok=True)
     model = D.load_model(args)
     export = mesh_io.write_obj if getattr(args, "ingest", "host") == "device" else Mesh.export
@@ -103,7 +105,7 @@ def main(argv=None):
     offsets = torch.from_numpy(centers).float().to(args.device)
     fit = sequence.fit_sequence(args, markers, valid, args.gender, offsets=offsets,
                                 temporal_w=(args.temporal_w_pose, args.temporal_w_orient, args.temporal_w_transl), shape_w=args.shape_w,
-                                sweeps=args.sweeps, refit_steps=args.refit_steps)
+                                sweeps=args.sweeps, refit_steps=args.refit_steps, pose_prior=pose_prior)
     nj, nb = fit["nj"], fit["nb"]
     npose = 3 * (nj - 1)
     x, verts, joints = fit["x"].cpu().numpy(), fit["verts"].cpu().numpy(), fit["joints"].cpu().numpy()

@@ -637,6 +637,21 @@ int etch_smpl_lm_fit_split(int B, int M, int nj, int nb, const void* const* cons
 int etch_smpl_lm_fit_prior(int B, int M, int nj, int nb, const void* const* consts, const float* markers, const float* valid, int it0, float step0,
                            float damp0, int it1, float step1, float damp1, float* x_out, float* x_stage0, float* err_trace, long long* phase_ticks,
                            int G, void* workspace, const float* x_init, const float* prior_mean, const float* prior_weight, void* stream);
+/* The same fit under a pose prior on top of whatever etch_smpl_lm_fit_prior takes:
+ *     + w_gmm min_k [0.5 d_k^T P_k d_k - log c_k],  d_k = x[:pp_D] - mu_k     (max-mixture GMM, MaxMixturePrior.merged_log_likelihood)
+ *     + w_ang sum_t exp(2 s_t x[a_t])                                        (SMPLifyAnglePrior, indices without the global orientation)
+ * as Gauss-Newton rows added in fp64 after every linearisation (the component is chosen again each time); err_trace holds the full objective.
+ * pp_tables: 5 device pointers {means (pp_G, pp_D), precisions (pp_G, pp_D, pp_D) fp32 SYMMETRIC and positive definite, nll_weights (pp_G) > 0,
+ * angle_idx (n_ang) int32 in [0, NPOSE), angle_sign (n_ang) fp32} -- values are the caller's duty.  pp_G = 0 or n_ang = 0 leaves that part (and
+ * its tables) out.  ETCH_EINVAL: pp_G == 0 && n_ang == 0, pp_G > 16, n_ang > 8, pp_D outside [1, NPOSE], a NULL table that is needed. */
+int etch_smpl_lm_fit_pose_prior(int B, int M, int nj, int nb, const void* const* consts, const float* markers, const float* valid, int it0, float step0,
+                                float damp0, int it1, float step1, float damp1, float* x_out, float* x_stage0, float* err_trace, long long* phase_ticks,
+                                int G, void* workspace, const float* x_init, const float* prior_mean, const float* prior_weight,
+                                const void* const* pp_tables, int pp_G, int pp_D, int n_ang, float w_gmm, float w_ang, void* stream);
+/* The max-mixture bracket alone, as the fits evaluate it (the same device function): pose (B, D) fp32 -> value (B) fp64 = min_k [...],
+ * component (B) int32 = argmin (ties: lowest index), grad (B, D) fp64 = P_k* d_k*.  tables: {means, precisions, nll_weights}; 1 <= G <= 16,
+ * 1 <= D <= 162. */
+int etch_pose_prior_eval(int B, const void* const* tables, int G, int D, const float* pose, double* value, int* component, double* grad, void* stream);
 /* Failure path of the split fit.  A workgroup that waits longer than its spin limit for its partners (they were not co-resident: another kernel, a CU
  * partition) flags the scan and every workgroup of the scan abandons the fit: the scan's x_out / x_stage0 / err_trace rows are NaN -- never a fit of
  * partial sums -- and the flag stays set in the workspace.  etch_smpl_lm_split_failed counts the flagged scans (synchronises the stream).
@@ -653,6 +668,15 @@ int etch_smpl_lm_workspace_bytes(int nj, int nb);
  * step): the reference builds its output meshes from that forward.  loss_trace (B, it0+it1, optional): this scan's share of L. */
 int etch_smpl_adam_fit(int B, int M, int nj, int nb, const void* const* consts, const float* markers, const float* valid, int it0, int it1,
                        float lr, float beta1, float beta2, float eps, float* x_out, float* x_last, float* loss_trace, void* stream);
+
+/* etch_smpl_adam_fit with the two optional loss terms of the reference's fitter (fit_SMPL_Adam.py:141-153, 202-214):
+ *     + w_pp sum_b min_k [0.5 d^T P_k d - log c_k] on pose[:pp_D]  (pp_tables: {means, precisions, nll_weights}; pp_G = 0: absent)
+ *     + w_ms mean(betas_active^2) over the batch (2 coefficients in stage 0, all in stage 1)
+ * and loss_trace rows that still sum to the batch loss.  ETCH_EINVAL: neither term (pp_G == 0 && w_ms == 0), pp_G > 16, pp_D outside
+ * [1, NPOSE], a NULL table. */
+int etch_smpl_adam_fit_prior(int B, int M, int nj, int nb, const void* const* consts, const float* markers, const float* valid, int it0, int it1,
+                             float lr, float beta1, float beta2, float eps, float* x_out, float* x_last, float* loss_trace,
+                             const void* const* pp_tables, int pp_G, int pp_D, float w_pp, float w_ms, void* stream);
 
 /* Diagnostics of the LM kernel (tests): ONE linearisation at a caller-given x (B,DOF) with nb_active betas -> residual
  * (B,3M) = mask * (target - markers(x)) (fit_SMPL.py:127-131), the analytic Jacobian d resid / d x (B,3M,DOF) the fit uses in place
