@@ -11,12 +11,6 @@ import torch
 
 from . import _lib
 from . import ops
-from .ops import _c_float, _ptr, _stream
-
-
-def _check(status, what):
-    _lib.check(status, what)
-
 
 import os
 
@@ -40,10 +34,9 @@ def gemm_tn(A, B, out=None, accumulate=False):
     R, M = A.shape
     N = B.shape[1]
     C = out if out is not None else torch.empty((M, N), dtype=torch.float32, device=A.device)
-    ws = torch.empty((_lib.lib().etch_gemm_tn_workspace_floats(ctypes.c_long(R), M, N),), dtype=torch.float32, device=A.device)
+    ws = torch.empty((_lib.call("etch_gemm_tn_workspace_floats", R, M, N),), dtype=torch.float32, device=A.device)
     counters = reduce_counters(A.device)
-    _check(_lib.lib().etch_gemm_tn_fused(ctypes.c_long(R), M, N, _ptr(A), ctypes.c_long(A.stride(0)), _ptr(B), ctypes.c_long(B.stride(0)), _ptr(C),
-                                         1 if accumulate else 0, _ptr(ws), _ptr(counters), _stream()), "etch_gemm_tn_fused")
+    _lib.call("etch_gemm_tn_fused", R, M, N, A, A.stride(0), B, B.stride(0), C, 1 if accumulate else 0, ws, counters)
     return C
 
 
@@ -52,8 +45,7 @@ def colsum(x2d):
     ws = torch.empty((64 * C,), dtype=torch.float64, device=x2d.device)
     out = torch.empty((C,), dtype=torch.float32, device=x2d.device)
     counters = reduce_counters(x2d.device)
-    _check(_lib.lib().etch_colsum_fused(ctypes.c_long(R), C, _ptr(x2d), ctypes.c_long(x2d.stride(0)), _ptr(ws), _ptr(counters), _ptr(out),
-                                        _stream()), "etch_colsum_fused")
+    _lib.call("etch_colsum_fused", R, C, x2d, x2d.stride(0), ws, counters, out)
     return out
 
 
@@ -77,7 +69,6 @@ class InterSO3ConvFunction(torch.autograd.Function):
         b, p1, na, cin = feats.shape
         p2, nn = idx.shape[1], idx.shape[2]
         cout, kk = W.shape
-        lib = _lib.lib()
         need_df = ctx.needs_input_grad[0]
         dW = torch.zeros_like(W)
         dfeats = None
@@ -90,15 +81,13 @@ class InterSO3ConvFunction(torch.autograd.Function):
         for s in range(0, p2, chunk):
             pc = min(chunk, p2 - s)
             x1 = torch.empty((b, pc, na, kk), dtype=torch.float32, device=feats.device)
-            _check(lib.etch_inter_x1_rows(b, cin, p1, p2, s, pc, nn, _c_float(ctx.sigma), _ptr(xyz), _ptr(new_xyz), _ptr(idx), _ptr(feats), _ptr(rk),
-                                          _ptr(x1), _stream()), "etch_inter_x1_rows")
+            _lib.call("etch_inter_x1_rows", b, cin, p1, p2, s, pc, nn, float(ctx.sigma), xyz, new_xyz, idx, feats, rk, x1)
             dyc = dy[:, s:s + pc].contiguous().view(b * pc * na, cout)
             gemm_tn(dyc, x1.view(b * pc * na, kk), out=dW, accumulate=True)   # dW += dY^T X1
             if need_df and slots:
                 dx1 = ops.linear(dyc, Wt)                                    # (rows, kk) = dY W
                 contrib = torch.empty((b * pc * nn, na * cin), dtype=torch.float32, device=feats.device)
-                _check(lib.etch_inter_dfeat_slots(b, cin, p1, p2, s, pc, nn, _c_float(ctx.sigma), _ptr(xyz), _ptr(new_xyz), _ptr(idx), _ptr(rk), _ptr(dx1),
-                                                  _ptr(contrib), _stream()), "etch_inter_dfeat_slots")
+                _lib.call("etch_inter_dfeat_slots", b, cin, p1, p2, s, pc, nn, float(ctx.sigma), xyz, new_xyz, idx, rk, dx1, contrib)
                 del dx1
                 # rows of one source point, in slot order (stable sort): the reproducible scatter-add; padded slots (index < 0) go to a segment of their own
                 src = idx[:, s:s + pc].long() + (torch.arange(b, device=idx.device, dtype=torch.int64) * p1).view(b, 1, 1)
@@ -110,8 +99,7 @@ class InterSO3ConvFunction(torch.autograd.Function):
                 if dfeats is None:
                     dfeats = torch.zeros_like(feats)
                 dx1 = ops.linear(dyc, Wt)                                    # (rows, kk) = dY W
-                _check(lib.etch_inter_dfeat(b, cin, p1, p2, s, pc, nn, _c_float(ctx.sigma), _ptr(xyz), _ptr(new_xyz), _ptr(idx), _ptr(rk), _ptr(dx1),
-                                            _ptr(dfeats), 1, _stream()), "etch_inter_dfeat")
+                _lib.call("etch_inter_dfeat", b, cin, p1, p2, s, pc, nn, float(ctx.sigma), xyz, new_xyz, idx, rk, dx1, dfeats, 1)
         dbias = colsum(dy.view(-1, cout)).view(ctx.bias_shape)
         return dfeats, dW, dbias, None, None, None, None, None, None
 
@@ -166,7 +154,6 @@ class IntraSO3ConvFunction(torch.autograd.Function):
         b, p, na, C = x.shape
         nt = idx32.shape[1]
         cout = W.shape[0]
-        lib = _lib.lib()
         dx = None
         if ctx.needs_input_grad[0]:
             # dx[p,a',c] = sum_t sum_o W[o, c*nt+t] dy[p, inv_t(a'), o]: the forward kernel with inverse tables and W'[c, o*nt+t] = W[o, c*nt+t]
@@ -175,7 +162,7 @@ class IntraSO3ConvFunction(torch.autograd.Function):
             zero = torch.zeros((C,), dtype=torch.float32, device=x.device)
             dx = ops.intra_so3conv(dy, inv, IntraSO3ConvFunction._frag(Wb, cout, nt), zero, C)
         xg = torch.empty((b * p * na, nt * C), dtype=torch.float32, device=x.device)
-        _check(lib.etch_intra_rows(ctypes.c_long(b * p), C, nt, _ptr(idx32), _ptr(x), _ptr(xg), _stream()), "etch_intra_rows")
+        _lib.call("etch_intra_rows", b * p, C, nt, idx32, x, xg)
         dW2 = gemm_tn(dy.view(b * p * na, cout), xg)                          # (cout, nt*C), tap-major columns
         dW = dW2.view(cout, nt, C).permute(0, 2, 1).reshape(cout, C * nt).contiguous()
         dbias = colsum(dy.view(-1, cout)).view(ctx.bias_shape)
@@ -205,10 +192,9 @@ class InstanceNormLeakyReLUFunction(torch.autograd.Function):
         dy = dy.contiguous()
         b, C = x.shape[0], x.shape[-1]
         rows = x.numel() // (b * C)
-        ws = torch.empty((_lib.lib().etch_instnorm_act_backward_workspace_bytes(b, C) // 8,), dtype=torch.float64, device=x.device)
+        ws = torch.empty((_lib.call("etch_instnorm_act_backward_workspace_bytes", b, C) // 8,), dtype=torch.float64, device=x.device)
         dx = torch.empty_like(x)
-        _check(_lib.lib().etch_instnorm_act_backward(b, rows, C, _ptr(x), _ptr(dy), _ptr(mean), _ptr(rstd), _c_float(ctx.slope), _ptr(ws), _ptr(dx),
-                                                     _stream()), "etch_instnorm_act_backward")
+        _lib.call("etch_instnorm_act_backward", b, rows, C, x, dy, mean, rstd, float(ctx.slope), ws, dx)
         return dx, None
 
 
@@ -233,8 +219,7 @@ def _mhsa_forward(x2, wq, wk, wv, wc, bc, mode):
 
 def _mhsa_attention_backward(T, E, qkv, dO):
     dqkv = torch.empty_like(qkv)
-    _check(_lib.lib().etch_mhsa_attention_backward_dim(ctypes.c_long(T), int(E), _ptr(qkv), ctypes.c_long(3 * E), 0, E, 2 * E, _ptr(dO), ctypes.c_long(E),
-                                                       _ptr(dqkv), _stream()), "etch_mhsa_attention_backward")
+    _lib.call("etch_mhsa_attention_backward_dim", T, int(E), qkv, 3 * E, 0, E, 2 * E, dO, E, dqkv)
     return dqkv
 
 
@@ -280,8 +265,7 @@ def segment_sum_rows(src, index, nseg):
     key, perm = torch.sort(index.reshape(-1).long(), stable=True)
     seg = torch.searchsorted(key, torch.arange(nseg + 1, device=key.device, dtype=torch.int64)).contiguous()
     dst = torch.empty((nseg, src.shape[1]), dtype=torch.float32, device=src.device)
-    _check(_lib.lib().etch_segment_sum_rows(ctypes.c_long(nseg), src.shape[1], _ptr(src), _ptr(perm.contiguous()), _ptr(seg), _ptr(dst), _stream()),
-           "etch_segment_sum_rows")
+    _lib.call("etch_segment_sum_rows", nseg, src.shape[1], src, perm.contiguous(), seg, dst)
     return dst
 
 
@@ -316,10 +300,7 @@ class PTVectorAttentionFunction(torch.autograd.Function):
         parr = (ctypes.c_void_p * 16)(*([t.data_ptr() for t in params] + [0, 0]))
         oarr = (ctypes.c_void_p * 10)(*[t.data_ptr() for t in outs])
         base = qkv.data_ptr()
-        vp = ctypes.c_void_p
-        _check(_lib.lib().etch_pt_attention_backward(n, c, ns, _ptr(p), vp(base), vp(base + 4 * c), vp(base + 8 * c), ctypes.c_long(qkv.stride(0)),
-                                                     _ptr(idx), parr, _ptr(dout), ctypes.c_long(dout.stride(0)), oarr, _stream()),
-               "etch_pt_attention_backward")
+        _lib.call("etch_pt_attention_backward", n, c, ns, p, base, base + 4 * c, base + 8 * c, qkv.stride(0), idx, parr, dout, dout.stride(0), oarr)
         dxk = segment_sum_rows(GU, idx, n)
         dxv = segment_sum_rows(GV, idx, n)
         dW5, db5 = gemm_tn(DL, G), colsum(DL)
@@ -413,8 +394,7 @@ class PropInterpFunction(torch.autograd.Function):
         skey, perm = torch.sort(key, stable=True)
         seg = torch.searchsorted(skey, torch.arange(B * S + 1, device=key.device, dtype=torch.int64)).contiguous()
         dfe = torch.empty((B * S, A * C), dtype=torch.float32, device=dout.device)
-        _check(_lib.lib().etch_weighted_segment_sum_rows(ctypes.c_long(B * S), A * C, 3, _ptr(dout), _ptr(w.contiguous()), _ptr(perm.contiguous()), _ptr(seg),
-                                                         _ptr(dfe), _stream()), "etch_weighted_segment_sum_rows")
+        _lib.call("etch_weighted_segment_sum_rows", B * S, A * C, 3, dout, w.contiguous(), perm.contiguous(), seg, dfe)
         return dfe.view(B, S, A, C), None, None
 
 
@@ -469,8 +449,7 @@ class SO3MeanDirFunction(torch.autograd.Function):
         w, anchors = ctx.saved_tensors
         T, A = w.shape
         dw = torch.empty_like(w)
-        _check(_lib.lib().etch_so3_mean_dir_backward(ctypes.c_long(T), A, _ptr(w), _ptr(anchors), _ptr(dd.contiguous()), _ptr(dw), _stream()),
-               "etch_so3_mean_dir_backward")
+        _lib.call("etch_so3_mean_dir_backward", T, A, w, anchors, dd.contiguous(), dw)
         return dw, None
 
 

@@ -8,8 +8,6 @@ segment sum, BatchNorm reduction, max-pool routing and the softmax-aggregation r
 etch_gather_rows / etch_segment_sum_rows, csrc/train_ops.hip); broadcasts, adds and the 3 x 3 position encoder's first layer are torch
 element-wise ops.  FPS / kNN indices are functions of the coordinates only and carry no gradient (as in the reference, whose index
 kernels are not differentiable either).  Gradients are reproducible run to run (fixed-order reductions, no atomics)."""
-import ctypes
-
 import torch
 import torch.nn.functional as F
 
@@ -17,9 +15,6 @@ from . import _lib
 from . import autograd as A
 from . import ops
 from .models import pointops
-from .ops import _ptr, _stream
-
-_c_long = ctypes.c_long
 
 
 def _ws(C, device):
@@ -32,8 +27,7 @@ def bn_stats(x2):
     mean = torch.empty((C,), dtype=torch.float32, device=x2.device)
     var = torch.empty_like(mean)
     ws = _ws(C, x2.device)               # held in a name: a temporary would be back in the allocator (and could be handed out again) before the launch
-    _lib.check(_lib.lib().etch_bn_stats(_c_long(R), C, _ptr(x2), _c_long(x2.stride(0)), _ptr(ws), _ptr(mean), _ptr(var), _stream()),
-               "etch_bn_stats")
+    _lib.call("etch_bn_stats", R, C, x2, x2.stride(0), ws, mean, var)
     return mean, var
 
 
@@ -53,16 +47,12 @@ class BatchNormFunction(torch.autograd.Function):
             stats = torch.empty((3, C), dtype=torch.float32, device=x.device)
             ws, counters = _ws(C, x.device), A.reduce_counters(x.device)
             mean, rstd, scale = stats[0], stats[1], stats[2]
-            _lib.check(_lib.lib().etch_bn_train_forward(_c_long(R), C, _ptr(x), _c_long(x.stride(0)), _ptr(g), _ptr(beta.detach().contiguous()),
-                                                        ctypes.c_float(eps), ctypes.c_float(-1.0 if momentum is None else momentum), ops._optptr(rm),
-                                                        ops._optptr(rv), ops._optptr(nbt), 1 if relu else 0, _ptr(ws),
-                                                        _ptr(counters), _ptr(mean), _ptr(rstd), _ptr(scale), _ptr(y), _stream()),
-                       "etch_bn_train_forward")
+            _lib.call("etch_bn_train_forward", R, C, x, x.stride(0), g, beta.detach().contiguous(), float(eps), float(-1.0 if momentum is None else momentum),
+                      rm, rv, nbt, 1 if relu else 0, ws, counters, mean, rstd, scale, y)
         else:
             rstd = torch.rsqrt(var + eps)
             scale = (g * rstd).contiguous()
-            _lib.check(_lib.lib().etch_bn_apply(_c_long(R), C, _ptr(x), _c_long(x.stride(0)), _ptr(mean.contiguous()), _ptr(scale),
-                                                _ptr(beta.detach().contiguous()), 1 if relu else 0, _ptr(y), _stream()), "etch_bn_apply")
+            _lib.call("etch_bn_apply", R, C, x, x.stride(0), mean.contiguous(), scale, beta.detach().contiguous(), 1 if relu else 0, y)
         ctx.save_for_backward(x, y if relu else None, mean, rstd, g)
         ctx.relu, ctx.train = bool(relu), bool(train)
         return y
@@ -75,9 +65,8 @@ class BatchNormFunction(torch.autograd.Function):
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dgb = torch.empty((2, C), dtype=torch.float32, device=x.device)
         ws, counters = _ws(C, x.device), A.reduce_counters(x.device)
-        _lib.check(_lib.lib().etch_bn_backward_fused(_c_long(R), C, _ptr(x), _c_long(x.stride(0)), ops._optptr(y), _ptr(dy), _ptr(mean), _ptr(rstd), _ptr(g),
-                                                     1 if ctx.relu else 0, 1 if ctx.train else 0, _ptr(ws), _ptr(counters),
-                                                     ops._optptr(dx), _ptr(dgb[0]), _ptr(dgb[1]), _stream()), "etch_bn_backward_fused")
+        _lib.call("etch_bn_backward_fused", R, C, x, x.stride(0), y, dy, mean, rstd, g, 1 if ctx.relu else 0, 1 if ctx.train else 0, ws, counters, dx, dgb[0],
+                  dgb[1])
         return dx, dgb[0], dgb[1], None, None, None, None, None, None
 
 
@@ -106,8 +95,7 @@ def _segments(index, nseg):
 def _segment_sum(src, index, nseg):
     perm, seg = _segments(index, nseg)
     dst = torch.empty((nseg, src.shape[1]), dtype=torch.float32, device=src.device)
-    _lib.check(_lib.lib().etch_segment_sum_rows(_c_long(nseg), src.shape[1], _ptr(src), _ptr(perm), _ptr(seg), _ptr(dst), _stream()),
-               "etch_segment_sum_rows")
+    _lib.call("etch_segment_sum_rows", nseg, src.shape[1], src, perm, seg, dst)
     return dst
 
 
@@ -145,8 +133,7 @@ class RowsMaxPoolFunction(torch.autograd.Function):
         (y,) = ctx.saved_tensors
         m, c = y.shape[0] // ctx.ns, y.shape[1]
         dy = torch.empty_like(y)
-        _lib.check(_lib.lib().etch_rows_maxpool_backward(_c_long(m), ctx.ns, c, _ptr(y), _ptr(dout.contiguous()), _ptr(dy), _stream()),
-                   "etch_rows_maxpool_backward")
+        _lib.call("etch_rows_maxpool_backward", m, ctx.ns, c, y, dout.contiguous(), dy)
         return dy, None
 
 
@@ -161,7 +148,7 @@ class SoftmaxAggFunction(torch.autograd.Function):
         n = E // ns
         sm = torch.empty_like(logit)
         out = torch.empty((n, c), dtype=torch.float32, device=v.device)
-        _lib.check(_lib.lib().etch_pt_softmax_agg(_c_long(n), ns, c, cs, _ptr(logit), _ptr(v), _ptr(sm), _ptr(out), _stream()), "etch_pt_softmax_agg")
+        _lib.call("etch_pt_softmax_agg", n, ns, c, cs, logit, v, sm, out)
         ctx.save_for_backward(sm, v)
         ctx.ns = ns
         return out
@@ -172,8 +159,7 @@ class SoftmaxAggFunction(torch.autograd.Function):
         E, cs = sm.shape
         c = v.shape[1]
         dlogit, dv = torch.empty_like(sm), torch.empty_like(v)
-        _lib.check(_lib.lib().etch_pt_softmax_agg_backward(_c_long(E // ctx.ns), ctx.ns, c, cs, _ptr(sm), _ptr(v), _ptr(dout.contiguous()), _ptr(dlogit),
-                                                           _ptr(dv), _stream()), "etch_pt_softmax_agg_backward")
+        _lib.call("etch_pt_softmax_agg_backward", E // ctx.ns, ctx.ns, c, cs, sm, v, dout.contiguous(), dlogit, dv)
         return dlogit, dv, None
 
 
@@ -197,8 +183,7 @@ class InterpolationFunction(torch.autograd.Function):
         perm, seg = _segments(ctx.idx, ctx.m)
         dout = dout.contiguous()
         dfe = torch.empty((ctx.m, dout.shape[1]), dtype=torch.float32, device=dout.device)
-        _lib.check(_lib.lib().etch_weighted_segment_sum_rows(_c_long(ctx.m), dout.shape[1], 3, _ptr(dout), _ptr(w), _ptr(perm), _ptr(seg), _ptr(dfe),
-                                                             _stream()), "etch_weighted_segment_sum_rows")
+        _lib.call("etch_weighted_segment_sum_rows", ctx.m, dout.shape[1], 3, dout, w, perm, seg, dfe)
         return dfe, None, None
 
 

@@ -13,6 +13,7 @@
 //   etch_instnorm_act_backward  d/dx of leaky_relu(InstanceNorm(x)) given dy, mean, rstd
 // Activations are channels-last ([b, p, 60, c]) as in the forward kernels.
 #include "common.h"
+#include "etch_hip.h"
 #include "colstat.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));

@@ -9,6 +9,7 @@
 // whose result is the same in any order, and atomicAdd of fixed-point differences (2^-40 m), which is exact and so order-free too.
 // The TU is built with -ffp-contract=off: distances are etch_sqdist's bit-defined ((dx*dx)+(dy*dy))+(dz*dz).
 #include "common.h"
+#include "etch_hip.h"
 #include "smpl_common.h"
 #include <algorithm>
 

@@ -12,6 +12,7 @@
 //   etch_so3_mean               src/models/so3conv.py:186-225 lives in heads.hip (so3_mean_dir_kernel, want_R)
 // (paths relative to /root/reference/external/vgtk or /root/reference)
 #include "common.h"
+#include "etch_hip.h"
 
 // w[b,p,a,k,n] = relu(1 - sum_xyz (g[b,:,p,n] - rk[:,a,k])^2 / sigma);  g (b,3,p,nn), rk (na,ks,3) = anchors @ kernels^T
 __global__ void __launch_bounds__(256) inter_kernel_weights_kernel(long total, int p, int nn, int na, int ks, const float* __restrict__ g,

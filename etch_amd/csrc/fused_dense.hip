@@ -14,6 +14,7 @@
 // applies bias / ReLU / w2 in registers, sums the strip's 16 columns with DPP row reductions, and the 8 strips through a
 // double-buffered LDS table (one barrier per group, fixed summation order: results are run-to-run reproducible).
 #include "common.h"
+#include "etch_hip.h"
 #include "split_bf16.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));

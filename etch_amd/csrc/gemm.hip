@@ -9,6 +9,7 @@
 // interleaved order (lane group g = lane>>4 takes k = 16t + 4g + s in MFMA step s) so that one
 // ds_read_b128 per operand feeds four MFMAs; A and B use the same order, so the sum is unchanged.
 #include "common.h"
+#include "etch_hip.h"
 #include "split_bf16.h"
 #include <cstdlib>
 #include <cstring>

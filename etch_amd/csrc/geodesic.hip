@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "common.h"
+#include "etch_hip.h"
 
 #define GD_BLOCK 256
 #define GD_SOLVE_THREADS 1024

@@ -5,6 +5,7 @@
 //   etch_rowdot         so3_reg = Conv1d(128, 1, 1) (models_pointcloud.py:54,117)
 //   etch_so3_mean_dir   so3_mean + R @ [0,0,1] (src/models/so3conv.py:186-225, models_pointcloud.py:120-124)
 #include "common.h"
+#include "etch_hip.h"
 
 // ------------------------------------------------------------------------------------------------
 // 3-NN with the reference's expansion formula  d = ((-2 * dot) + |x|^2) + |y|^2  (pointnet2_utils.py:20-22):

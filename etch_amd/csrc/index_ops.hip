@@ -8,6 +8,7 @@
 // Results are bit-identical to oracle/discrete_ops.c (integer outputs equal, distances equal).
 // Built with -ffp-contract=off: distance arithmetic is "bit-defined fp32" (common.h).
 #include "common.h"
+#include "etch_hip.h"
 #include <cmath>
 #include <cstdio>
 

@@ -15,6 +15,7 @@
 //   C  head_combine (+ bias + residual) from the attention tile in LDS, float4 stores.
 // Keys 60..63 (tile padding) are masked to -inf; rows 60..63 are never stored.
 #include "common.h"
+#include "etch_hip.h"
 #include "split_bf16.h"
 #include <cstdlib>
 

@@ -10,6 +10,7 @@
 //   etch_softmax_dot       confidence = sum_k softmax(cls)_k * confi_k (:183-189)
 // Eval-mode BatchNorm is folded on the host into per-channel (scale, shift).
 #include "common.h"
+#include "etch_hip.h"
 
 struct PtAttnParams {
     const float* p;       // [n,3]

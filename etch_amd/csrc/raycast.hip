@@ -10,6 +10,7 @@
 // per operation, and tests/_raycast_oracle.py restates it term by term in numpy.  No atomics touch a value: the mesh kernels write one
 // candidate per (face chunk, query) and a final kernel reduces the chunks in ascending order, so the result does not depend on the launch shape.
 #include "common.h"
+#include "etch_hip.h"
 
 #define RC_BLOCK 256                 // queries per workgroup, one per lane
 #define RC_TILE 256                  // faces (points) staged in LDS per step

@@ -33,6 +33,7 @@
 // SMPL, 144 KB for the 188-DoF model) ALIASES the linearisation scratch: it is written from the accumulators after the last
 // chunk and consumed by the Cholesky solve before the next linearisation.
 #include "common.h"
+#include "etch_hip.h"
 #include <cstdlib>
 
 #ifndef LM_ELIM_COLS

@@ -13,6 +13,7 @@
 //                        InstanceNorm2d(affine=False, eps=1e-5) + leaky_relu(0.01) (+ residual branch)
 //                        (/root/reference/src/models/so3conv.py:36-44,96-99,178-182).
 #include "common.h"
+#include "etch_hip.h"
 #include "split_bf16.h"
 #include <cstdlib>
 #include <cstring>

@@ -20,6 +20,7 @@
 //           contraction: Y[o][col] += W[o][kappa] X1[col][kappa], W streamed from L2 in fragment order (ops.inter_weight_frag32).
 //   after the last slice: the K-split partial tiles meet in LDS, bias, output, InstanceNorm statistics (fp64) as in the 16-wide kernel.
 #include "common.h"
+#include "etch_hip.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));

@@ -17,6 +17,7 @@
 // as planes of its rows times their own powers of two, the epilogue multiplies by the inverse power), where that split carries the fp32 MFMA's error (profiles/r05_f16_two_plane_split.txt):
 // half the matrix instructions, two thirds of the LDS plane traffic, 48 / 96 instead of 72 / 144 registers of weight fragments.
 #include "common.h"
+#include "etch_hip.h"
 #include "split_bf16.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));

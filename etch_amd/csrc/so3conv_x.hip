@@ -21,6 +21,7 @@
 // Channel order: column r of channel tile ct is channel 16 ct + r, so the contraction of step 2 runs in W's natural column order
 // (ops.inter_weight_split(natural=True)).
 #include "common.h"
+#include "etch_hip.h"
 #include "split_bf16.h"
 
 #include "so3conv_x.h"

@@ -22,6 +22,7 @@
 // Step 1 (transposed product on the gathered bf16 planes), the X1 tile, step 2 and the epilogue are those of inter_so3conv_x32_kernel.
 // No inline-asm LDS reads are left in the loop (see etch_amd/isa_lint.py for why that matters); the W stream of step 2 keeps its asm ring.
 #include "so3conv_x.h"
+#include "etch_hip.h"
 
 #ifndef INTER_Y_WPE
 #define INTER_Y_WPE(CIN) ((CIN) <= 32 ? 2 : 1)

@@ -7,6 +7,7 @@
 //   etch_pt_softmax_agg        out[i, s*cs + j] = sum_k softmax_k(logit[i, k, j]) v[i, k, s*cs + j]   (pointtransformer_seg.py:34-36) and its backward
 // Reductions are fixed-order (no atomics): gradients are reproducible run to run.
 #include "common.h"
+#include "etch_hip.h"
 #include "colstat.h"
 
 #define TO_CHUNKS 64

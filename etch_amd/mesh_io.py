@@ -20,21 +20,21 @@ MAX_WORKERS = 16                  # never sized from os.cpu_count(): a shared ho
 
 _OBJ_ERRORS = {-3: "a 'v' line needs three numbers", -4: "a face token is no integer that fits int64", -5: "a face index is outside [1, number of vertices]",
                -6: "the text changed between the count and the parse"}
-_ll = ctypes.c_longlong
 
 
 def parse_obj(data, name="<buffer>"):
     """OBJ text (bytes) -> Mesh(vertices (V,3) float64, faces (F,3) int64); ValueError naming `name` and the line on a malformed text."""
-    lib = _lib.lib()
     data = bytes(data)
-    nv, nf, line = _ll(0), _ll(0), _ll(0)
-    _lib.check(lib.etch_obj_count(data, _ll(len(data)), ctypes.byref(nv), ctypes.byref(nf)), "etch_obj_count")
+    nv, nf, line = ctypes.c_longlong(0), ctypes.c_longlong(0), ctypes.c_longlong(0)
+    _lib.call("etch_obj_count", data, len(data), ctypes.byref(nv), ctypes.byref(nf))
     v = np.empty((nv.value, 3), np.float64)
     f = np.empty((nf.value, 3), np.int64)
-    r = lib.etch_obj_parse(data, _ll(len(data)), nv, nf, v.ctypes.data_as(ctypes.c_void_p), f.ctypes.data_as(ctypes.c_void_p), ctypes.byref(line))
-    if r in _OBJ_ERRORS:
-        raise ValueError(f"{name}, line {line.value}: {_OBJ_ERRORS[r]}")
-    _lib.check(r, "etch_obj_parse")
+    try:
+        _lib.call("etch_obj_parse", data, len(data), nv, nf, v.ctypes.data, f.ctypes.data, ctypes.byref(line))
+    except _lib.EtchHipError as e:
+        if e.status in _OBJ_ERRORS:
+            raise ValueError(f"{name}, line {line.value}: {_OBJ_ERRORS[e.status]}") from None
+        raise
     return Mesh(v, f)
 
 
@@ -55,21 +55,21 @@ def read_objs(paths, workers=None):
 
 def format_obj(mesh):
     """The bytes Mesh.export writes for `mesh`."""
-    lib = _lib.lib()
     v = np.ascontiguousarray(mesh.vertices, np.float64)
     f = np.ascontiguousarray(mesh.faces, np.int64)
     if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
         raise ValueError(f"a mesh is vertices (V,3) and faces (F,3), got {v.shape} and {f.shape}")
     cap = 16 + 3 * 24 * len(v) + 3 * 21 * len(f)        # enough below 1e13; the call reports the size it needs otherwise
-    for _ in range(2):
+    for attempt in range(2):
         out = ctypes.create_string_buffer(cap)
-        written = _ll(0)
-        r = lib.etch_obj_format(v.ctypes.data_as(ctypes.c_void_p), _ll(len(v)), f.ctypes.data_as(ctypes.c_void_p), _ll(len(f)), out, _ll(cap),
-                                ctypes.byref(written))
-        if r != -7:
+        written = ctypes.c_longlong(0)
+        try:
+            _lib.call("etch_obj_format", v.ctypes.data, len(v), f.ctypes.data, len(f), out, cap, ctypes.byref(written))
             break
-        cap = written.value
-    _lib.check(r, "etch_obj_format")
+        except _lib.EtchHipError as e:
+            if e.status != -7 or attempt:
+                raise
+            cap = written.value
     return out.raw[:written.value]
 
 

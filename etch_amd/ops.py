@@ -13,22 +13,13 @@ import torch
 
 from . import _lib
 
-_c_int, _c_float, _vp = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
 
-
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-
-def _stream():
-    """The current HIP stream's handle.  Asked ~300 times per step: torch.cuda.current_stream() builds a Stream object (10 us each, 3 ms of the host's
-    8.5 ms per step); the raw accessor returns the integer."""
-    if _raw_stream is not None:
-        return _vp(_raw_stream(torch.cuda.current_device()))
-    return _vp(torch.cuda.current_stream().cuda_stream)
+# For direct callers of the typed functions (`_lib.lib().etch_x(...)` in tests and profiles/scripts); the package itself goes through _lib.call.
+_stream = _lib.stream
 
 
 def _ptr(t):
-    return _vp(t.data_ptr())
+    return t.data_ptr()
 
 
 def _need(t, dtype, name):
@@ -48,8 +39,7 @@ def ball_query(new_xyz, xyz, radius, nsample):
     b, _, m = new_xyz.shape
     n = xyz.shape[2]
     idx = torch.empty((b, m, nsample), dtype=torch.int32, device=xyz.device)
-    _lib.check(_lib.lib().etch_ball_query(b, n, m, _c_float(radius), int(nsample), _ptr(new_xyz), _ptr(xyz), _ptr(idx), _stream()),
-               "etch_ball_query")
+    _lib.call("etch_ball_query", b, n, m, float(radius), int(nsample), new_xyz, xyz, idx)
     return idx
 
 
@@ -75,7 +65,7 @@ def fps_split_default(nseg, n_max, device=None):
 
 
 def _fps_split_ws(nseg, G, device):
-    ws = torch.empty((_lib.lib().etch_fps_split_workspace_bytes(nseg, G),), dtype=torch.uint8, device=device)
+    ws = torch.empty((_lib.call("etch_fps_split_workspace_bytes", nseg, G),), dtype=torch.uint8, device=device)
     return ws
 
 
@@ -85,7 +75,7 @@ def fps_split_failed(idx):
     if ws is None:
         return False
     out = ctypes.c_int(0)
-    _lib.check(_lib.lib().etch_fps_split_failed(_ptr(ws), ctypes.byref(out), _stream()), "etch_fps_split_failed")
+    _lib.call("etch_fps_split_failed", ws, ctypes.byref(out))
     return bool(out.value)
 
 
@@ -113,8 +103,7 @@ def fps_pair(xyz_b3n, m, xyz_packed, offset, new_offset, new_offset_host):
     assert xyz_packed.shape == (b * n, 3)
     idx_a = torch.zeros((b, m), dtype=torch.int32, device=xyz_b3n.device)
     idx_b = torch.zeros((int(new_offset_host[-1]),), dtype=torch.int32, device=xyz_b3n.device)
-    _lib.check(_lib.lib().etch_fps_pair(b, n, int(m), _ptr(xyz_b3n), _ptr(idx_a), _ptr(xyz_packed), _ptr(offset), _ptr(new_offset), _ptr(idx_b), _stream()),
-               "etch_fps_pair")
+    _lib.call("etch_fps_pair", b, n, int(m), xyz_b3n, idx_a, xyz_packed, offset, new_offset, idx_b)
     return idx_a, idx_b
 
 
@@ -129,11 +118,10 @@ def furthest_point_sampling(xyz, m, split=None):
     G = fps_split_default(b, n, xyz.device) if split is None else int(split)
     if G >= 2:
         ws = _fps_split_ws(b, G, xyz.device)
-        _lib.check(_lib.lib().etch_furthest_point_sampling_split(b, n, int(m), _ptr(xyz), _ptr(idx), G, _ptr(ws), _stream()),
-                   "etch_furthest_point_sampling_split")
+        _lib.call("etch_furthest_point_sampling_split", b, n, int(m), xyz, idx, G, ws)
         idx._etch_split_ws = ws
         return _fps_split_checked(idx, split)
-    _lib.check(_lib.lib().etch_furthest_point_sampling(b, n, int(m), _ptr(xyz), _ptr(idx), _stream()), "etch_furthest_point_sampling")
+    _lib.call("etch_furthest_point_sampling", b, n, int(m), xyz, idx)
     return idx
 
 
@@ -143,7 +131,7 @@ def gather_points_forward(points, idx):
     b, c, n = points.shape
     m = idx.shape[1]
     out = torch.empty((b, c, m), dtype=torch.float32, device=points.device)
-    _lib.check(_lib.lib().etch_gather_points(b, c, n, m, _ptr(points), _ptr(idx), _ptr(out), _stream()), "etch_gather_points")
+    _lib.call("etch_gather_points", b, c, n, m, points, idx, out)
     return out
 
 
@@ -152,8 +140,7 @@ def gather_points_backward(grad_out, idx, npoint):
     _need(grad_out, torch.float32, "grad_out"), _need(idx, torch.int32, "idx")
     b, c, m = grad_out.shape
     out = torch.empty((b, c, int(npoint)), dtype=torch.float32, device=grad_out.device)
-    _lib.check(_lib.lib().etch_gather_points_backward(b, c, int(npoint), m, _ptr(grad_out), _ptr(idx), _ptr(out), _stream()),
-               "etch_gather_points_backward")
+    _lib.call("etch_gather_points_backward", b, c, int(npoint), m, grad_out, idx, out)
     return out
 
 
@@ -180,9 +167,8 @@ def knnquery(nsample, xyz, new_xyz, offset, new_offset, new_offset_host=None, sq
     m = new_xyz.shape[0]
     idx = torch.empty((m, nsample), dtype=torch.int32, device=xyz.device)
     dist = torch.empty((m, nsample), dtype=torch.float32, device=xyz.device)
-    _lib.check(_lib.lib().etch_knnquery(len(new_offset_host), _seg_max(new_offset_host), int(m) if wave_kernel else 0, int(nsample), _ptr(xyz), _ptr(new_xyz),
-                                        _ptr(offset), _ptr(new_offset), _ptr(idx), _ptr(dist), 1 if sqrt else 0, _stream()),
-               "etch_knnquery")
+    _lib.call("etch_knnquery", len(new_offset_host), _seg_max(new_offset_host), int(m) if wave_kernel else 0, int(nsample), xyz, new_xyz, offset, new_offset,
+              idx, dist, 1 if sqrt else 0)
     return idx, dist
 
 
@@ -201,21 +187,15 @@ def furthestsampling(xyz, offset, new_offset, offset_host=None, new_offset_host=
     G = fps_split_default(nseg, n_max, xyz.device) if split is None else int(split)
     if G >= 2:
         ws = _fps_split_ws(nseg, G, xyz.device)
-        _lib.check(_lib.lib().etch_furthestsampling_split(nseg, n_max, _ptr(xyz), _ptr(offset), _ptr(new_offset), _ptr(idx), G, _ptr(ws), _stream()),
-                   "etch_furthestsampling_split")
+        _lib.call("etch_furthestsampling_split", nseg, n_max, xyz, offset, new_offset, idx, G, ws)
         idx._etch_split_ws = ws
         return _fps_split_checked(idx, split)
-    _lib.check(_lib.lib().etch_furthestsampling(nseg, n_max, _ptr(xyz), _ptr(offset), _ptr(new_offset), _ptr(idx), _stream()), "etch_furthestsampling")
+    _lib.call("etch_furthestsampling", nseg, n_max, xyz, offset, new_offset, idx)
     return idx
 
 
 # ------------------------------------------------------------------ dense layers
-_c_long = ctypes.c_long
 ACT = {None: 0, "none": 0, "relu": 1, "leaky_relu": 2}
-
-
-def _optptr(t):
-    return _vp(0) if t is None else _ptr(t)
 
 
 def linear(x, weight, bias=None, scale=None, shift=None, act=None, res=None, res_mode=0, row_idx=None, grp=1, p_in=0, p_out=1,
@@ -233,10 +213,8 @@ def linear(x, weight, bias=None, scale=None, shift=None, act=None, res=None, res
     if out is None:
         out = torch.empty((R, O), dtype=torch.float32, device=x.device)
     ldr = res.stride(0) if res is not None and res.dim() == 2 and res.shape[0] > 1 else O
-    _lib.check(_lib.lib().etch_linear(int(R), int(K), int(O), _ptr(x2), _c_long(ldx), _optptr(row_idx), int(grp), int(p_in), int(p_out),
-                                      _ptr(weight), _c_long(weight.stride(0)), _optptr(bias), _optptr(scale), _optptr(shift),
-                                      ACT[act], _optptr(res), _c_long(ldr), int(res_mode), _ptr(out), _c_long(out.stride(0)), _stream()),
-               "etch_linear")
+    _lib.call("etch_linear", int(R), int(K), int(O), x2, ldx, row_idx, int(grp), int(p_in), int(p_out), weight, weight.stride(0), bias, scale, shift, ACT[act],
+              res, ldr, int(res_mode), out, out.stride(0))
     return out
 
 
@@ -258,15 +236,12 @@ def linear_stats(x, weight, bias, b, rows, row_idx=None, grp=1, p_in=0, p_out=1)
     if row_idx is not None:
         _need(row_idx, torch.int32, "row_idx")
         assert row_idx.numel() == b * p_out and rows == p_out * grp
-    lib = _lib.lib()
-    parts = lib.etch_linear_stats_parts(int(rows), 0 if row_idx is None else 1)
+    parts = _lib.call("etch_linear_stats_parts", int(rows), 0 if row_idx is None else 1)
     out = torch.empty((b * rows, O), dtype=torch.float32, device=x.device)
     part = torch.empty((b, parts, 2, O), dtype=torch.float64, device=x.device)
     mean = torch.empty((b, O), dtype=torch.float32, device=x.device)
     rstd = torch.empty((b, O), dtype=torch.float32, device=x.device)
-    _lib.check(lib.etch_linear_stats(int(b), int(rows), int(K), int(O), _ptr(x), _c_long(K), _optptr(row_idx), int(grp), int(p_in), int(p_out),
-                                     _ptr(weight), _c_long(K), _optptr(bias), _ptr(out), _c_long(O), _ptr(part), _ptr(mean), _ptr(rstd), _stream()),
-               "etch_linear_stats")
+    _lib.call("etch_linear_stats", int(b), int(rows), int(K), int(O), x, K, row_idx, int(grp), int(p_in), int(p_out), weight, K, bias, out, O, part, mean, rstd)
     return out, mean, rstd
 
 
@@ -433,7 +408,7 @@ def split2_planes_f16(x_cl):
     _need(x_cl, torch.float32, "x")
     C = x_cl.shape[-1]
     planes = torch.empty(tuple(x_cl.shape[:-1]) + (2, C), dtype=torch.float16, device=x_cl.device)
-    _lib.check(_lib.lib().etch_split2_planes_f16(_c_long(x_cl.numel() // C), int(C), _ptr(x_cl), _ptr(planes), _stream()), "etch_split2_planes_f16")
+    _lib.call("etch_split2_planes_f16", x_cl.numel() // C, int(C), x_cl, planes)
     return planes
 
 
@@ -445,8 +420,7 @@ def split2_planes_f16_scaled(x_cl):
     planes = torch.empty(tuple(x_cl.shape[:-1]) + (2, C), dtype=torch.float16, device=x_cl.device)
     mx = torch.zeros((b,), dtype=torch.int32, device=x_cl.device)
     fsc = torch.empty((b,), dtype=torch.float32, device=x_cl.device)
-    _lib.check(_lib.lib().etch_split2_planes_f16_scaled(int(b), _c_long(x_cl.numel() // (b * C)), int(C), _ptr(x_cl), _ptr(mx), _ptr(planes), _ptr(fsc), _stream()),
-               "etch_split2_planes_f16_scaled")
+    _lib.call("etch_split2_planes_f16_scaled", int(b), x_cl.numel() // (b * C), int(C), x_cl, mx, planes, fsc)
     return planes, fsc
 
 
@@ -476,7 +450,7 @@ def inter_kpoint_operand(rk, sigma):
     _need(rk, torch.float32, "rk")
     assert tuple(rk.shape) == (60, 24, 3)
     kq = torch.empty((60, 2, 64, 8), dtype=torch.int16, device=rk.device)
-    _lib.check(_lib.lib().etch_inter_kpoint_operand(_c_float(sigma), _ptr(rk), _ptr(kq), _stream()), "etch_inter_kpoint_operand")
+    _lib.call("etch_inter_kpoint_operand", float(sigma), rk, kq)
     return kq
 
 
@@ -491,7 +465,7 @@ def split3_planes(x_cl):
     _need(x_cl, torch.float32, "x")
     C = x_cl.shape[-1]
     planes = torch.empty(tuple(x_cl.shape[:-1]) + (3, C), dtype=torch.int16, device=x_cl.device)
-    _lib.check(_lib.lib().etch_split3_planes(_c_long(x_cl.numel() // C), int(C), _ptr(x_cl), _ptr(planes), _stream()), "etch_split3_planes")
+    _lib.call("etch_split3_planes", x_cl.numel() // C, int(C), x_cl, planes)
     return planes
 
 
@@ -502,7 +476,7 @@ def spatial_order(xyz):
     _need(xyz, torch.float32, "xyz")
     b, _, n = xyz.shape
     order = torch.empty((b, n), dtype=torch.int32, device=xyz.device)
-    _lib.check(_lib.lib().etch_spatial_order(b, n, _ptr(xyz), _ptr(order), _stream()), "etch_spatial_order")
+    _lib.call("etch_spatial_order", b, n, xyz, order)
     return order
 
 
@@ -535,50 +509,40 @@ def inter_so3conv(xyz, new_xyz, ball_idx, feats_cl, rk, W, Wp, bias, sigma, orde
             feats_planes, fsc = split2_planes_f16_scaled(feats_cl)
         _need(feats_planes, torch.float16, "feats_planes")
         assert tuple(feats_planes.shape) == (b, p1, na, 2, cin) and kq.numel() == 60 * 2 * 64 * 8 and Wqh.numel() == 2 * cout * cin * 24
-        _lib.check(_lib.lib().etch_inter_so3conv_planes_kq(b, cin, cout, p1, p2, nn, _c_float(sigma), _ptr(xyz), _ptr(new_xyz), _ptr(ball_idx),
-                                                          _ptr(feats_planes), _ptr(kq), _ptr(Wqh), _ptr(Wqh.wsc), _optptr(fsc), _ptr(bias), _ptr(out), _optptr(order),
-                                                          _optptr(part), _stream()), "etch_inter_so3conv_planes_kq")
+        _lib.call("etch_inter_so3conv_planes_kq", b, cin, cout, p1, p2, nn, float(sigma), xyz, new_xyz, ball_idx, feats_planes, kq, Wqh, Wqh.wsc, fsc, bias,
+                  out, order, part)
     elif Wq32 is not None and cin == 64 and inter_planes_form(cin) == 32 and inter_planes_supported(cin, cout, nn) and _lib.has_experiments():
         _need(Wq32, torch.int16, "Wq32")
         if feats_planes is None or feats_planes.dtype != torch.int16:
             feats_planes = split3_planes(feats_cl)
         _need(feats_planes, torch.int16, "feats_planes")
         assert tuple(feats_planes.shape) == (b, p1, na, 3, cin)
-        _lib.check(_lib.lib().etch_inter_so3conv_planes32(b, cin, cout, p1, p2, nn, _c_float(sigma), _ptr(xyz), _ptr(new_xyz), _ptr(ball_idx),
-                                                         _ptr(feats_planes), _ptr(rk), _ptr(Wq32), _ptr(bias), _ptr(out), _optptr(order),
-                                                         _optptr(part), _stream()), "etch_inter_so3conv_planes32")
+        _lib.call("etch_inter_so3conv_planes32", b, cin, cout, p1, p2, nn, float(sigma), xyz, new_xyz, ball_idx, feats_planes, rk, Wq32, bias, out, order, part)
     elif Wqn is not None and inter_planes_supported(cin, cout, nn) and _lib.has_experiments():
         _need(Wqn, torch.int16, "Wqn")
         if feats_planes is None or feats_planes.dtype != torch.int16:
             feats_planes = split3_planes(feats_cl)
         _need(feats_planes, torch.int16, "feats_planes")
         assert tuple(feats_planes.shape) == (b, p1, na, 3, cin)
-        _lib.check(_lib.lib().etch_inter_so3conv_planes(b, cin, cout, p1, p2, nn, _c_float(sigma), _ptr(xyz), _ptr(new_xyz), _ptr(ball_idx),
-                                                       _ptr(feats_planes), _ptr(rk), _ptr(Wqn), _ptr(bias), _ptr(out), _optptr(order),
-                                                       _optptr(part), _stream()), "etch_inter_so3conv_planes")
+        _lib.call("etch_inter_so3conv_planes", b, cin, cout, p1, p2, nn, float(sigma), xyz, new_xyz, ball_idx, feats_planes, rk, Wqn, bias, out, order, part)
     elif Wp32 is not None and INTER_MFMA32 and (cin, cout) in INTER_MFMA32_SHAPES and _lib.has_experiments():
         _need(Wp32, torch.float32, "Wp32")
-        _lib.check(_lib.lib().etch_inter_so3conv32(b, cin, cout, p1, p2, nn, _c_float(sigma), _ptr(xyz), _ptr(new_xyz), _ptr(ball_idx),
-                                                   _ptr(feats_cl), _ptr(rk), _ptr(Wp32), _ptr(bias), _ptr(out), _optptr(order),
-                                                   _optptr(part), _stream()), "etch_inter_so3conv32")
+        _lib.call("etch_inter_so3conv32", b, cin, cout, p1, p2, nn, float(sigma), xyz, new_xyz, ball_idx, feats_cl, rk, Wp32, bias, out, order, part)
     elif Wq is not None and INTER_SPLIT and cin % 16 == 0:
         _need(Wq, torch.int16, "Wq")
-        _lib.check(_lib.lib().etch_inter_so3conv_split(b, cin, cout, p1, p2, nn, _c_float(sigma), _ptr(xyz), _ptr(new_xyz), _ptr(ball_idx),
-                                                      _ptr(feats_cl), _ptr(rk), _ptr(Wq), _ptr(bias), _ptr(out), _optptr(order),
-                                                      _optptr(part), _stream()), "etch_inter_so3conv_split")
+        _lib.call("etch_inter_so3conv_split", b, cin, cout, p1, p2, nn, float(sigma), xyz, new_xyz, ball_idx, feats_cl, rk, Wq, bias, out, order, part)
     else:
         # all-ones features (the encoder's occupancy tensor, tagged by models/so3conv.py): the one-channel kernel takes NULL and skips the feature gather
         unit = cin == 1 and getattr(feats_cl, "_etch_constant", None) == 1.0 and cout <= 64 and nn * 60 >= 1026
-        _lib.check(_lib.lib().etch_inter_so3conv_ordered(b, cin, cout, p1, p2, nn, _c_float(sigma), _ptr(xyz), _ptr(new_xyz), _ptr(ball_idx),
-                                                         _vp(0) if unit else _ptr(feats_cl), _ptr(rk), _ptr(W), _optptr(Wp), _ptr(bias), _ptr(out), _optptr(order),
-                                                         _optptr(part), _stream()), "etch_inter_so3conv")
+        _lib.call("etch_inter_so3conv_ordered", b, cin, cout, p1, p2, nn, float(sigma), xyz, new_xyz, ball_idx, None if unit else feats_cl, rk, W, Wp, bias, out,
+                  order, part)
     if not want_stats:
         return out
     if not fused:
         return out, instnorm_stats(out)
     mean = torch.empty((b, cout), dtype=torch.float32, device=xyz.device)
     rstd = torch.empty((b, cout), dtype=torch.float32, device=xyz.device)
-    _lib.check(_lib.lib().etch_instnorm_from_partials(b, p2, cout, 60, _ptr(part), _ptr(mean), _ptr(rstd), _stream()), "etch_instnorm_from_partials")
+    _lib.call("etch_instnorm_from_partials", b, p2, cout, 60, part, mean, rstd)
     return out, (mean, rstd)
 
 
@@ -599,25 +563,21 @@ def intra_so3conv(x_cl, intra_idx32, Wp, bias, cout, mean=None, rstd=None, want_
     # (> 65 504 -> inf, far below 1 -> the planes' absolute floor): those calls take the exact forms below
     if Wqh is not None and mean is not None and rstd is not None and INTRA_SPLIT and INTRA_F16 and c == cout and c in (32, 64) and (part is None or p % 2 == 0):
         _need(Wqh, torch.int16, "Wqh")
-        _lib.check(_lib.lib().etch_intra_so3conv_f16(b, c, cout, p, _ptr(x_cl), _optptr(mean), _optptr(rstd), _ptr(intra_idx32), _ptr(Wqh),
-                                                    _ptr(Wqh.wsc), _ptr(bias), _ptr(out), _optptr(part), _stream()), "etch_intra_so3conv_f16")
+        _lib.call("etch_intra_so3conv_f16", b, c, cout, p, x_cl, mean, rstd, intra_idx32, Wqh, Wqh.wsc, bias, out, part)
     elif Wq is not None and INTRA_SPLIT and c == cout and c in (32, 64) and (part is None or p % 2 == 0):
         _need(Wq, torch.int16, "Wq")
-        _lib.check(_lib.lib().etch_intra_so3conv_split(b, c, cout, p, _ptr(x_cl), _optptr(mean), _optptr(rstd), _ptr(intra_idx32), _ptr(Wq),
-                                                      _ptr(bias), _ptr(out), _optptr(part), _stream()), "etch_intra_so3conv_split")
+        _lib.call("etch_intra_so3conv_split", b, c, cout, p, x_cl, mean, rstd, intra_idx32, Wq, bias, out, part)
     elif Wp32 is not None and INTRA_MFMA32 and c == cout and c in (32, 64):
-        _lib.check(_lib.lib().etch_intra_so3conv32(b, c, cout, p, _ptr(x_cl), _optptr(mean), _optptr(rstd), _ptr(intra_idx32), _ptr(Wp32),
-                                                   _ptr(bias), _ptr(out), _optptr(part), _stream()), "etch_intra_so3conv32")
+        _lib.call("etch_intra_so3conv32", b, c, cout, p, x_cl, mean, rstd, intra_idx32, Wp32, bias, out, part)
     else:
-        _lib.check(_lib.lib().etch_intra_so3conv_stats(b, c, cout, p, _ptr(x_cl), _optptr(mean), _optptr(rstd), _ptr(intra_idx32), _ptr(Wp),
-                                                       _ptr(bias), _ptr(out), _optptr(part), _stream()), "etch_intra_so3conv")
+        _lib.call("etch_intra_so3conv_stats", b, c, cout, p, x_cl, mean, rstd, intra_idx32, Wp, bias, out, part)
     if not want_stats:
         return out
     if not fused:
         return out, instnorm_stats(out)
     m = torch.empty((b, cout), dtype=torch.float32, device=x_cl.device)
     r = torch.empty((b, cout), dtype=torch.float32, device=x_cl.device)
-    _lib.check(_lib.lib().etch_instnorm_from_partials(b, p // 2, cout, 120, _ptr(part), _ptr(m), _ptr(r), _stream()), "etch_instnorm_from_partials")
+    _lib.call("etch_instnorm_from_partials", b, p // 2, cout, 120, part, m, r)
     return out, (m, r)
 
 
@@ -626,10 +586,10 @@ def instnorm_stats(x_cl):
     _need(x_cl, torch.float32, "x")
     b, C = x_cl.shape[0], x_cl.shape[-1]
     rows = x_cl.numel() // (b * C)
-    ws = torch.empty((_lib.lib().etch_instnorm_stats_workspace_bytes(b, C) // 8,), dtype=torch.float64, device=x_cl.device)
+    ws = torch.empty((_lib.call("etch_instnorm_stats_workspace_bytes", b, C) // 8,), dtype=torch.float64, device=x_cl.device)
     mean = torch.empty((b, C), dtype=torch.float32, device=x_cl.device)
     rstd = torch.empty((b, C), dtype=torch.float32, device=x_cl.device)
-    _lib.check(_lib.lib().etch_instnorm_stats(b, rows, C, _ptr(x_cl), _ptr(ws), _ptr(mean), _ptr(rstd), _stream()), "etch_instnorm_stats")
+    _lib.call("etch_instnorm_stats", b, rows, C, x_cl, ws, mean, rstd)
     return mean, rstd
 
 
@@ -641,8 +601,7 @@ def instnorm_from_partials(part, total, wide=True):
     assert two == 2
     mean = torch.empty((b, C), dtype=torch.float32, device=part.device)
     rstd = torch.empty((b, C), dtype=torch.float32, device=part.device)
-    _lib.check(_lib.lib().etch_instnorm_from_partials_n(b, nparts, C, _c_long(int(total)), _ptr(part), _ptr(mean), _ptr(rstd), 1 if wide else 0, _stream()),
-               "etch_instnorm_from_partials_n")
+    _lib.call("etch_instnorm_from_partials_n", b, nparts, C, int(total), part, mean, rstd, 1 if wide else 0)
     return mean, rstd
 
 
@@ -659,8 +618,7 @@ def instnorm_act_add_mean(x1, m1, r1, x2=None, m2=None, r2=None):
         _need(x2, torch.float32, "x2")
     out = torch.empty_like(x1)
     mean = torch.empty((b * p, C), dtype=torch.float32, device=x1.device)
-    _lib.check(_lib.lib().etch_instnorm_act_add_mean(b, p, C, _ptr(x1), _ptr(m1), _ptr(r1), _optptr(x2), _optptr(m2), _optptr(r2), _ptr(out), _ptr(mean),
-                                                    _stream()), "etch_instnorm_act_add_mean")
+    _lib.call("etch_instnorm_act_add_mean", b, p, C, x1, m1, r1, x2, m2, r2, out, mean)
     return out, mean
 
 
@@ -674,8 +632,7 @@ def instnorm_act_add_k1(x1, m1, r1, f, slope, offset, want_planes=False):
     assert f.numel() == b * rows and tuple(slope.shape) == (b, C) and tuple(offset.shape) == (b, C) and want_planes in (False, None, "f16")
     out = torch.empty_like(x1)
     planes = torch.empty(tuple(x1.shape[:-1]) + (2, C), dtype=torch.float16, device=x1.device) if want_planes else None
-    _lib.check(_lib.lib().etch_instnorm_act_add_k1_planes_f16(b, rows, C, _ptr(x1), _ptr(m1), _ptr(r1), _ptr(f.contiguous()), _ptr(slope.contiguous()),
-                                                               _ptr(offset.contiguous()), _ptr(out), _optptr(planes), _stream()), "etch_instnorm_act_add_k1")
+    _lib.call("etch_instnorm_act_add_k1_planes_f16", b, rows, C, x1, m1, r1, f.contiguous(), slope.contiguous(), offset.contiguous(), out, planes)
     return (out, planes) if want_planes else out
 
 
@@ -690,9 +647,7 @@ def instnorm_act_add(x1, m1, r1, x2=None, m2=None, r2=None, want_planes=False):
     planes = None
     if want_planes:
         planes = torch.empty(tuple(x1.shape[:-1]) + ((2, C) if f16 else (3, C)), dtype=torch.float16 if f16 else torch.int16, device=x1.device)
-    fn = _lib.lib().etch_instnorm_act_add_planes_f16 if f16 else _lib.lib().etch_instnorm_act_add_planes
-    _lib.check(fn(b, rows, C, _ptr(x1), _ptr(m1), _ptr(r1), _optptr(x2), _optptr(m2), _optptr(r2), _ptr(out), _optptr(planes), _stream()),
-               "etch_instnorm_act_add")
+    _lib.call("etch_instnorm_act_add_planes_f16" if f16 else "etch_instnorm_act_add_planes", b, rows, C, x1, m1, r1, x2, m2, r2, out, planes)
     return (out, planes) if want_planes else out
 
 
@@ -703,7 +658,7 @@ def prop3nn(xyz1_bn3, xyz2_b3s):
     S = xyz2_b3s.shape[2]
     idx = torch.empty((B, N, 3), dtype=torch.int32, device=xyz1_bn3.device)
     w = torch.empty((B, N, 3), dtype=torch.float32, device=xyz1_bn3.device)
-    _lib.check(_lib.lib().etch_prop3nn(B, N, S, _ptr(xyz1_bn3), _ptr(xyz2_b3s), _ptr(idx), _ptr(w), _stream()), "etch_prop3nn")
+    _lib.call("etch_prop3nn", B, N, S, xyz1_bn3, xyz2_b3s, idx, w)
     return idx, w
 
 
@@ -716,8 +671,7 @@ def prop_interp(feats_cl, idx, w, order=None):
     N = idx.shape[1]
     out = torch.empty((B, N, A, C), dtype=torch.float32, device=feats_cl.device)
     inv = torch.empty((B, N, C), dtype=torch.float32, device=feats_cl.device)
-    _lib.check(_lib.lib().etch_prop_interp_ordered(B, N, S, A, C, _ptr(feats_cl), _ptr(idx), _ptr(w), _ptr(out), _ptr(inv), _optptr(order),
-                                                   _stream()), "etch_prop_interp")
+    _lib.call("etch_prop_interp_ordered", B, N, S, A, C, feats_cl, idx, w, out, inv, order)
     return out, inv
 
 
@@ -726,8 +680,7 @@ def mhsa_attention(qkv, T, qoff, koff, voff, embedding_dim=64):
     _need(qkv, torch.float32, "qkv")
     E = int(embedding_dim)
     out = torch.empty((T * 60, E), dtype=torch.float32, device=qkv.device)
-    _lib.check(_lib.lib().etch_mhsa_attention_dim(_c_long(T), E, _ptr(qkv), _c_long(qkv.stride(0)), qoff, koff, voff, _ptr(out), _c_long(E), _stream()),
-               "etch_mhsa_attention_dim")
+    _lib.call("etch_mhsa_attention_dim", T, E, qkv, qkv.stride(0), qoff, koff, voff, out, E)
     return out
 
 
@@ -738,8 +691,7 @@ def mhsa_layer(x, wq, wk, wv, wc=None, bc=None, mode=0):
     assert x.shape[-1] == 64 and x.numel() % (60 * 64) == 0 and wq.shape == (64, 64)
     T = x.numel() // (60 * 64)
     out = torch.empty((T * 60, 64), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().etch_mhsa_layer(_c_long(T), _ptr(x), _ptr(wq), _ptr(wk), _ptr(wv), _optptr(wc), _optptr(bc), int(mode), _ptr(out),
-                                          _stream()), "etch_mhsa_layer")
+    _lib.call("etch_mhsa_layer", T, x, wq, wk, wv, wc, bc, int(mode), out)
     return out
 
 
@@ -771,8 +723,7 @@ def mhsa_layer_dirtail(x, wq, wk, wv, Wfq, tab):
     assert x.shape[-1] == 64 and x.numel() % (60 * 64) == 0 and wq.shape == (64, 64) and Wfq.numel() == 2 * 128 * 64 and tab.numel() == 257
     T = x.numel() // (60 * 64)
     out = torch.empty((T, 60), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().etch_mhsa_layer_dirtail(_c_long(T), _ptr(x), _ptr(wq), _ptr(wk), _ptr(wv), _ptr(Wfq), _ptr(tab), _ptr(out), _stream()),
-               "etch_mhsa_layer_dirtail")
+    _lib.call("etch_mhsa_layer_dirtail", T, x, wq, wk, wv, Wfq, tab, out)
     return out
 
 
@@ -791,8 +742,7 @@ def mhsa_interp_layer(feats_cl, idx, w, wq, wk, wv, wc, bc, order=None):
     N = idx.shape[1]
     out = torch.empty((B * N * 60, 64), dtype=torch.float32, device=feats_cl.device)
     sched = torch.empty((B * N, 8), dtype=torch.int32, device=feats_cl.device)      # workspace: per-slot records of the processing order
-    _lib.check(_lib.lib().etch_mhsa_interp_layer(B, N, S, _ptr(feats_cl), _ptr(idx), _ptr(w), _optptr(order), _ptr(wq), _ptr(wk), _ptr(wv), _ptr(wc),
-                                                 _optptr(bc), _ptr(out), _ptr(sched), _stream()), "etch_mhsa_interp_layer")
+    _lib.call("etch_mhsa_interp_layer", B, N, S, feats_cl, idx, w, order, wq, wk, wv, wc, bc, out, sched)
     return out
 
 
@@ -801,7 +751,7 @@ def token_mean(x):
     _need(x, torch.float32, "x")
     T, A, C = x.shape
     out = torch.empty((T, C), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().etch_token_mean(_c_long(T), A, C, _ptr(x), _ptr(out), _stream()), "etch_token_mean")
+    _lib.call("etch_token_mean", T, A, C, x, out)
     return out
 
 
@@ -809,7 +759,7 @@ def rowdot(x, w, bias):
     _need(x, torch.float32, "x"), _need(w, torch.float32, "w")
     R, K = x.shape
     y = torch.empty((R,), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().etch_rowdot(_c_long(R), K, _ptr(x), _c_long(x.stride(0)), _ptr(w), _c_float(bias), _ptr(y), _stream()), "etch_rowdot")
+    _lib.call("etch_rowdot", R, K, x, x.stride(0), w, float(bias), y)
     return y
 
 
@@ -819,7 +769,7 @@ def so3_mean_dir(w, anchors, want_R=False, want_sv=False):
     d = torch.empty((T, 3), dtype=torch.float32, device=w.device)
     R = torch.empty((T, 3, 3), dtype=torch.float32, device=w.device) if want_R else None
     sv = torch.empty((T, 3), dtype=torch.float32, device=w.device) if want_sv else None
-    _lib.check(_lib.lib().etch_so3_mean_dir(_c_long(T), A, _ptr(w), _ptr(anchors), _ptr(d), _optptr(R), _optptr(sv), _stream()), "etch_so3_mean_dir")
+    _lib.call("etch_so3_mean_dir", T, A, w, anchors, d, R, sv)
     return d, R, sv
 
 
@@ -830,8 +780,7 @@ def pt_attention(p, qkv, c, idx, params, ns):
     out = torch.empty((n, c), dtype=torch.float32, device=p.device)
     arr = (ctypes.c_void_p * 16)(*[(0 if t is None else t.data_ptr()) for t in params])
     base = qkv.data_ptr()
-    _lib.check(_lib.lib().etch_pt_attention(n, c, ns, _ptr(p), _vp(base), _vp(base + 4 * c), _vp(base + 8 * c), _c_long(qkv.stride(0)),
-                                            _ptr(idx), arr, _ptr(out), _c_long(c), _stream()), "etch_pt_attention")
+    _lib.call("etch_pt_attention", n, c, ns, p, base, base + 4 * c, base + 8 * c, qkv.stride(0), idx, arr, out, c)
     return out
 
 
@@ -845,8 +794,7 @@ def pt_attention_mfma(p, qkv, c, idx, params, ns, w2):
     out = torch.empty((n, c), dtype=torch.float32, device=p.device)
     arr = (ctypes.c_void_p * 16)(*[(0 if t is None else t.data_ptr()) for t in params])
     base = qkv.data_ptr()
-    _lib.check(_lib.lib().etch_pt_attention_mfma(n, c, ns, _ptr(p), _vp(base), _vp(base + 4 * c), _vp(base + 8 * c), _c_long(qkv.stride(0)),
-                                                 _ptr(idx), arr, _ptr(w2), _ptr(out), _c_long(c), _stream()), "etch_pt_attention_mfma")
+    _lib.call("etch_pt_attention_mfma", n, c, ns, p, base, base + 4 * c, base + 8 * c, qkv.stride(0), idx, arr, w2, out, c)
     return out
 
 
@@ -861,8 +809,7 @@ def pt_block_k1(x, w1, s1, t1, wqkv, bqkv):
     n, c = x.shape
     assert x.stride(1) == 1 and w1.shape == (c, c) and wqkv.shape == (3 * c, c)
     qkv = torch.empty((n, 3 * c), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().etch_pt_block_k1(n, c, _ptr(x), _c_long(x.stride(0)), _ptr(w1), _ptr(s1), _ptr(t1), _ptr(wqkv), _ptr(bqkv), _ptr(qkv),
-                                           _c_long(3 * c), _stream()), "etch_pt_block_k1")
+    _lib.call("etch_pt_block_k1", n, c, x, x.stride(0), w1, s1, t1, wqkv, bqkv, qkv, 3 * c)
     return qkv
 
 
@@ -881,9 +828,7 @@ def pt_block_k2(p, qkv, c, idx, params, ns, w2, w3, s3, t3, x_res, next_k1=None)
     qn = torch.empty((n, 3 * c), dtype=torch.float32, device=p.device) if next_k1 is not None else None
     base = qkv.data_ptr()
     assert x_res.stride(1) == 1
-    _lib.check(_lib.lib().etch_pt_block_k2(n, c, ns, _ptr(p), _vp(base), _vp(base + 4 * c), _vp(base + 8 * c), _c_long(qkv.stride(0)), _ptr(idx), arr,
-                                           _ptr(w2), tarr, _c_long(x_res.stride(0)), _ptr(out), _c_long(c), _optptr(qn), _c_long(3 * c), _stream()),
-               "etch_pt_block_k2")
+    _lib.call("etch_pt_block_k2", n, c, ns, p, base, base + 4 * c, base + 8 * c, qkv.stride(0), idx, arr, w2, tarr, x_res.stride(0), out, c, qn, 3 * c)
     return out, qn
 
 
@@ -892,15 +837,13 @@ def pt_attention_split(p, qkv, c, idx, params, ns, w2, b2, s3, t3, w5, b5):
     n = p.shape[0]
     arr = (ctypes.c_void_p * 16)(*[(0 if t is None else t.data_ptr()) for t in params])
     base = qkv.data_ptr()
-    ldq = _c_long(qkv.stride(0))
+    ldq = qkv.stride(0)
     w_in = torch.empty((n * ns, c), dtype=torch.float32, device=p.device)
-    _lib.check(_lib.lib().etch_pt_attn_prep(n, c, ns, _ptr(p), _vp(base), _vp(base + 4 * c), ldq, _ptr(idx), arr, _ptr(w_in), _stream()),
-               "etch_pt_attn_prep")
+    _lib.call("etch_pt_attn_prep", n, c, ns, p, base, base + 4 * c, ldq, idx, arr, w_in)
     hid = linear(w_in, w2, bias=b2, scale=s3, shift=t3, act="relu")
     logits = linear(hid, w5, bias=b5)
     out = torch.empty((n, c), dtype=torch.float32, device=p.device)
-    _lib.check(_lib.lib().etch_pt_attn_aggregate(n, c, ns, _ptr(p), _vp(base + 8 * c), ldq, _ptr(idx), _ptr(logits), arr, _ptr(out), _c_long(c),
-                                                 _stream()), "etch_pt_attn_aggregate")
+    _lib.call("etch_pt_attn_aggregate", n, c, ns, p, base + 8 * c, ldq, idx, logits, arr, out, c)
     return out
 
 
@@ -910,8 +853,7 @@ def pt_group(p, new_p, x, idx, pad_to=1):
     c = x.shape[1]
     ld = -(-(3 + c) // pad_to) * pad_to
     out = torch.empty((m * ns, ld), dtype=torch.float32, device=p.device)
-    _lib.check(_lib.lib().etch_pt_group(m, ns, c, _ptr(p), _ptr(new_p), _ptr(x), _c_long(x.stride(0)), _ptr(idx), _ptr(out), _c_long(ld), _stream()),
-               "etch_pt_group")
+    _lib.call("etch_pt_group", m, ns, c, p, new_p, x, x.stride(0), idx, out, ld)
     return out
 
 
@@ -920,43 +862,42 @@ def pt_down_gather_max(ux, p, new_p, idx, wp, scale, shift):
     m, ns = idx.shape
     co = ux.shape[1]
     out = torch.empty((m, co), dtype=torch.float32, device=ux.device)
-    _lib.check(_lib.lib().etch_pt_down_gather_max(m, ns, co, _ptr(ux), _c_long(ux.stride(0)), _ptr(p), _ptr(new_p), _ptr(idx), _ptr(wp), _ptr(scale),
-                                                  _ptr(shift), _ptr(out), _stream()), "etch_pt_down_gather_max")
+    _lib.call("etch_pt_down_gather_max", m, ns, co, ux, ux.stride(0), p, new_p, idx, wp, scale, shift, out)
     return out
 
 
 def gather_rows(x, idx):
     m, c = idx.shape[0], x.shape[1]
     out = torch.empty((m, c), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().etch_gather_rows(m, c, _ptr(x), _c_long(x.stride(0)), _ptr(idx), _ptr(out), _stream()), "etch_gather_rows")
+    _lib.call("etch_gather_rows", m, c, x, x.stride(0), idx, out)
     return out
 
 
 def rows_maxpool(x, ns):
     m, c = x.shape[0] // ns, x.shape[1]
     out = torch.empty((m, c), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().etch_rows_maxpool(m, ns, c, _ptr(x), _ptr(out), _stream()), "etch_rows_maxpool")
+    _lib.call("etch_rows_maxpool", m, ns, c, x, out)
     return out
 
 
 def pt_interp_add(a, f, idx, dist):
     n, c = a.shape
     out = torch.empty_like(a)
-    _lib.check(_lib.lib().etch_pt_interp_add(n, c, _ptr(a), _ptr(f), _ptr(idx), _ptr(dist), _ptr(out), _stream()), "etch_pt_interp_add")
+    _lib.call("etch_pt_interp_add", n, c, a, f, idx, dist, out)
     return out
 
 
 def seg_mean(x, offset, nseg):
     c = x.shape[1]
     out = torch.empty((nseg, c), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().etch_seg_mean(nseg, c, _ptr(x), _ptr(offset), _ptr(out), _stream()), "etch_seg_mean")
+    _lib.call("etch_seg_mean", nseg, c, x, offset, out)
     return out
 
 
 def concat_bcast(x, g, offset, nseg):
     n, c = x.shape
     out = torch.empty((n, 2 * c), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().etch_concat_bcast(n, c, nseg, _ptr(x), _ptr(g), _ptr(offset), _ptr(out), _stream()), "etch_concat_bcast")
+    _lib.call("etch_concat_bcast", n, c, nseg, x, g, offset, out)
     return out
 
 
@@ -964,8 +905,7 @@ def grouped_dot(h, w, bias, G, J, out=None):
     R = h.shape[0]
     if out is None:
         out = torch.empty((R, G), dtype=torch.float32, device=h.device)
-    _lib.check(_lib.lib().etch_grouped_dot(_c_long(R), G, J, _ptr(h), _c_long(h.stride(0)), _ptr(w), _ptr(bias), _ptr(out), _c_long(out.stride(0)),
-                                           _stream()), "etch_grouped_dot")
+    _lib.call("etch_grouped_dot", R, G, J, h, h.stride(0), w, bias, out, out.stride(0))
     return out
 
 
@@ -1021,27 +961,23 @@ def linear_relu_dot(x, w, b1, w2, b2, G, wp=None, out=None):
     if out is None:
         out = torch.empty((R, G), dtype=torch.float32, device=x.device)
     if wp is not None and wp.dtype == torch.float16 and (b1.data_ptr() | w2.data_ptr()) % 16 == 0:
-        _lib.check(_lib.lib().etch_linear_relu_dot_f16(_c_long(R), int(K), int(G), int(J), _ptr(x), _c_long(x.stride(0) if R > 1 else K), _ptr(wp), _ptr(wp.wsc),
-                                                       _ptr(b1), _ptr(w2), _ptr(b2), _ptr(out), _c_long(out.stride(0) if R > 1 else G), _stream()),
-                   "etch_linear_relu_dot_f16")
+        _lib.call("etch_linear_relu_dot_f16", R, int(K), int(G), int(J), x, x.stride(0) if R > 1 else K, wp, wp.wsc, b1, w2, b2, out,
+                  out.stride(0) if R > 1 else G)
         return out
     if wp is not None and wp.dtype == torch.float16:
         wp = None                                  # (a bias / w2 view off the 16-byte grid: the fp32 kernel below)
     if wp is not None and wp.dtype == torch.int16:
-        _lib.check(_lib.lib().etch_linear_relu_dot_split(_c_long(R), int(K), int(G), int(J), _ptr(x), _c_long(x.stride(0) if R > 1 else K), _ptr(wp),
-                                                         _ptr(b1), _ptr(w2), _ptr(b2), _ptr(out), _c_long(out.stride(0) if R > 1 else G), _stream()),
-                   "etch_linear_relu_dot_split")
+        _lib.call("etch_linear_relu_dot_split", R, int(K), int(G), int(J), x, x.stride(0) if R > 1 else K, wp, b1, w2, b2, out, out.stride(0) if R > 1 else G)
         return out
-    _lib.check(_lib.lib().etch_linear_relu_dot(_c_long(R), int(K), int(G), int(J), _ptr(x), _c_long(x.stride(0) if R > 1 else K), _ptr(w),
-                                               _c_long(w.stride(0)), _optptr(wp), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(out),
-                                               _c_long(out.stride(0) if R > 1 else G), _stream()), "etch_linear_relu_dot")
+    _lib.call("etch_linear_relu_dot", R, int(K), int(G), int(J), x, x.stride(0) if R > 1 else K, w, w.stride(0), wp, b1, w2, b2, out,
+              out.stride(0) if R > 1 else G)
     return out
 
 
 def softmax_dot(logits, v):
     R, G = logits.shape
     out = torch.empty((R,), dtype=torch.float32, device=logits.device)
-    _lib.check(_lib.lib().etch_softmax_dot(_c_long(R), G, _ptr(logits), _ptr(v), _ptr(out), _stream()), "etch_softmax_dot")
+    _lib.call("etch_softmax_dot", R, G, logits, v, out)
     return out
 
 
@@ -1052,7 +988,7 @@ def argmax_rows(logits):
     G = logits.shape[-1]
     R = logits.numel() // G
     out = torch.empty(logits.shape[:-1], dtype=torch.int64, device=logits.device)
-    _lib.check(_lib.lib().etch_argmax_rows(_c_long(R), G, _ptr(logits), _ptr(out), _stream()), "etch_argmax_rows")
+    _lib.call("etch_argmax_rows", R, G, logits, out)
     return out
 
 
@@ -1062,8 +998,7 @@ def get_markers(points, labels, conf, num_markers):
     markers = torch.empty((B, num_markers, 3), dtype=torch.float32, device=points.device)
     valid_f = torch.empty((B, num_markers), dtype=torch.float32, device=points.device)
     valid_b = torch.empty((B, num_markers), dtype=torch.bool, device=points.device)
-    _lib.check(_lib.lib().etch_get_markers(B, K, num_markers, _ptr(points), _ptr(labels), _ptr(conf), _ptr(markers), _ptr(valid_f),
-                                           _ptr(valid_b), _stream()), "etch_get_markers")
+    _lib.call("etch_get_markers", B, K, num_markers, points, labels, conf, markers, valid_f, valid_b)
     return markers, valid_f, valid_b
 
 
@@ -1191,8 +1126,7 @@ def pose_prior_eval(pose, pose_prior):
     val = torch.empty((B,), dtype=torch.float64, device=pose.device)
     comp = torch.empty((B,), dtype=torch.int32, device=pose.device)
     grad = torch.empty((B, pose_prior.D), dtype=torch.float64, device=pose.device)
-    _lib.check(_lib.lib().etch_pose_prior_eval(B, pose_prior._tables, pose_prior.G, pose_prior.D, _ptr(pose), _ptr(val), _ptr(comp), _ptr(grad),
-                                               _stream()), "etch_pose_prior_eval")
+    _lib.call("etch_pose_prior_eval", B, pose_prior._tables, pose_prior.G, pose_prior.D, pose, val, comp, grad)
     return val, comp, grad
 
 
@@ -1234,26 +1168,20 @@ def smpl_lm_fit(consts, markers, valid_f, it0, step0, damp0, it1, step1, damp1, 
         G = 1           # the workgroups of a scan wait for each other: on a small part / CU partition one persistent workgroup per scan (same results up to summation order)
     ws = None
     if G > 1:
-        nbytes = _lib.lib().etch_smpl_lm_split_workspace_bytes(B, int(nj), int(nb), G)
+        nbytes = _lib.call("etch_smpl_lm_split_workspace_bytes", B, int(nj), int(nb), G)
         ws = torch.empty((nbytes // 8 + 1,), dtype=torch.float64, device=markers.device)
     if pose_prior is not None:
         mean, weight = prior if prior is not None else (None, None)
         pp = pose_prior
-        _lib.check(_lib.lib().etch_smpl_lm_fit_pose_prior(B, M, int(nj), int(nb), arr, _ptr(markers), _ptr(valid_f), int(it0), _c_float(step0),
-                                                          _c_float(damp0), int(it1), _c_float(step1), _c_float(damp1), _ptr(x), _ptr(x0), _optptr(tr),
-                                                          _optptr(phase_ticks), G, _optptr(ws), _optptr(x_init), _optptr(mean), _optptr(weight),
-                                                          pp._tables, pp.G, pp.D, pp.n_ang, _c_float(pp.w_gmm), _c_float(pp.w_ang), _stream()),
-                   "etch_smpl_lm_fit_pose_prior")
+        _lib.call("etch_smpl_lm_fit_pose_prior", B, M, int(nj), int(nb), arr, markers, valid_f, int(it0), float(step0), float(damp0), int(it1), float(step1),
+                  float(damp1), x, x0, tr, phase_ticks, G, ws, x_init, mean, weight, pp._tables, pp.G, pp.D, pp.n_ang, float(pp.w_gmm), float(pp.w_ang))
     elif x_init is None and prior is None:
-        _lib.check(_lib.lib().etch_smpl_lm_fit_split(B, M, int(nj), int(nb), arr, _ptr(markers), _ptr(valid_f), int(it0), _c_float(step0), _c_float(damp0),
-                                                     int(it1), _c_float(step1), _c_float(damp1), _ptr(x), _ptr(x0), _optptr(tr), _optptr(phase_ticks),
-                                                     G, _optptr(ws), _stream()), "etch_smpl_lm_fit_split")
+        _lib.call("etch_smpl_lm_fit_split", B, M, int(nj), int(nb), arr, markers, valid_f, int(it0), float(step0), float(damp0), int(it1), float(step1),
+                  float(damp1), x, x0, tr, phase_ticks, G, ws)
     else:
         mean, weight = prior if prior is not None else (None, None)
-        _lib.check(_lib.lib().etch_smpl_lm_fit_prior(B, M, int(nj), int(nb), arr, _ptr(markers), _ptr(valid_f), int(it0), _c_float(step0), _c_float(damp0),
-                                                     int(it1), _c_float(step1), _c_float(damp1), _ptr(x), _ptr(x0), _optptr(tr), _optptr(phase_ticks),
-                                                     G, _optptr(ws), _optptr(x_init), _optptr(mean), _optptr(weight), _stream()),
-                   "etch_smpl_lm_fit_prior")
+        _lib.call("etch_smpl_lm_fit_prior", B, M, int(nj), int(nb), arr, markers, valid_f, int(it0), float(step0), float(damp0), int(it1), float(step1),
+                  float(damp1), x, x0, tr, phase_ticks, G, ws, x_init, mean, weight)
     x._etch_split_ws = ws       # the split fit's workspace carries the per-scan give-up flags (smpl_lm_split_failed); None for one workgroup per scan
     return x, x0, tr
 
@@ -1265,7 +1193,7 @@ def smpl_lm_split_failed(x):
     if ws is None:
         return 0
     n = ctypes.c_int(0)
-    _lib.check(_lib.lib().etch_smpl_lm_split_failed(int(x.shape[0]), _ptr(ws), ctypes.byref(n), _stream()), "etch_smpl_lm_split_failed")
+    _lib.call("etch_smpl_lm_split_failed", int(x.shape[0]), ws, ctypes.byref(n))
     return int(n.value)
 
 
@@ -1287,15 +1215,12 @@ def smpl_adam_fit(consts, markers, valid_f, it0, it1, lr=1e-2, beta1=0.9, beta2=
     tr = torch.zeros((B, it0 + it1), dtype=torch.float32, device=markers.device) if want_trace else None
     if pose_prior is not None or mean_shape_w != 0.0:
         pp = pose_prior
-        _lib.check(_lib.lib().etch_smpl_adam_fit_prior(B, M, int(nj), int(nb), arr, _ptr(markers), _ptr(valid_f), int(it0), int(it1), _c_float(lr),
-                                                       _c_float(beta1), _c_float(beta2), _c_float(eps), _ptr(x), _ptr(xl), _optptr(tr),
-                                                       pp._tables if pp is not None else None, pp.G if pp is not None else 0,
-                                                       pp.D if pp is not None else 0, _c_float(pose_prior_w), _c_float(mean_shape_w), _stream()),
-                   "etch_smpl_adam_fit_prior")
+        _lib.call("etch_smpl_adam_fit_prior", B, M, int(nj), int(nb), arr, markers, valid_f, int(it0), int(it1), float(lr), float(beta1), float(beta2),
+                  float(eps), x, xl, tr, pp._tables if pp is not None else None, pp.G if pp is not None else 0, pp.D if pp is not None else 0,
+                  float(pose_prior_w), float(mean_shape_w))
         return x, xl, tr
-    _lib.check(_lib.lib().etch_smpl_adam_fit(B, M, int(nj), int(nb), arr, _ptr(markers), _ptr(valid_f), int(it0), int(it1), _c_float(lr),
-                                             _c_float(beta1), _c_float(beta2), _c_float(eps), _ptr(x), _ptr(xl), _optptr(tr), _stream()),
-               "etch_smpl_adam_fit")
+    _lib.call("etch_smpl_adam_fit", B, M, int(nj), int(nb), arr, markers, valid_f, int(it0), int(it1), float(lr), float(beta1), float(beta2), float(eps), x, xl,
+              tr)
     return x, xl, tr
 
 
@@ -1303,7 +1228,7 @@ def marker_status(markers, valid_f):
     """(B,) int32: bit 0 = a valid marker is non-finite (the fit of that scan is NaN, as in the reference), bit 1 = no valid marker."""
     B, M = valid_f.shape
     st = torch.empty((B,), dtype=torch.int32, device=markers.device)
-    _lib.check(_lib.lib().etch_marker_status(B, M, _ptr(markers), _ptr(valid_f), _ptr(st), _stream()), "etch_marker_status")
+    _lib.call("etch_marker_status", B, M, markers, valid_f, st)
     return st
 
 
@@ -1316,8 +1241,7 @@ def smpl_lm_linearize(consts, x, markers, valid_f, nb_active, nj=24, nb=10, want
     r = torch.empty((B, 3 * M), dtype=torch.float32, device=x.device)
     J = torch.empty((B, 3 * M, dof), dtype=torch.float32, device=x.device)
     N = torch.empty((B, dof + 1, dof + 1), dtype=torch.float64, device=x.device) if want_normal else None
-    _lib.check(_lib.lib().etch_smpl_lm_linearize(B, M, int(nj), int(nb), int(nb_active), arr, _ptr(x), _ptr(markers), _ptr(valid_f), _ptr(r),
-                                                 _ptr(J), _optptr(N), _stream()), "etch_smpl_lm_linearize")
+    _lib.call("etch_smpl_lm_linearize", B, M, int(nj), int(nb), int(nb_active), arr, x, markers, valid_f, r, J, N)
     return (r, J, N) if want_normal else (r, J)
 
 
@@ -1327,7 +1251,7 @@ def rodrigues(theta):
     n = theta.shape[0]
     R = torch.empty((n, 3, 3), dtype=torch.float64, device=theta.device)
     dR = torch.empty((n, 3, 3, 3), dtype=torch.float32, device=theta.device)
-    _lib.check(_lib.lib().etch_rodrigues(n, _ptr(theta), _ptr(R), _ptr(dR), _stream()), "etch_rodrigues")
+    _lib.call("etch_rodrigues", n, theta, R, dR)
     return R, dR
 
 
@@ -1337,7 +1261,7 @@ def smpl_lbs(consts, x, V, n_extra, nj=24, nb=10):
     arr = (ctypes.c_void_p * 8)(*[t.data_ptr() for t in consts])
     verts = torch.empty((B, V, 3), dtype=torch.float32, device=x.device)
     joints = torch.empty((B, nj + n_extra, 3), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().etch_smpl_lbs(B, V, int(nj), int(nb), n_extra, arr, _ptr(x), _ptr(verts), _ptr(joints), _stream()), "etch_smpl_lbs")
+    _lib.call("etch_smpl_lbs", B, V, int(nj), int(nb), n_extra, arr, x, verts, joints)
     return verts, joints
 
 
@@ -1345,8 +1269,7 @@ def inner_points(points, direction, magnitude, scale):
     _need(points, torch.float32, "points"), _need(direction, torch.float32, "direction"), _need(magnitude, torch.float32, "magnitude")
     out = torch.empty_like(points)
     n = points.numel() // 3
-    _lib.check(_lib.lib().etch_inner_points(_c_long(n), _ptr(points), _ptr(direction), _ptr(magnitude), _c_float(scale), _ptr(out), _stream()),
-               "etch_inner_points")
+    _lib.call("etch_inner_points", n, points, direction, magnitude, float(scale), out)
     return out
 
 
@@ -1374,8 +1297,7 @@ def nn_bidir(x, y, x_lengths=None, y_lengths=None):
     dxy = torch.empty((B, N), dtype=torch.float32, device=x.device)
     iyx = torch.empty((B, V), dtype=torch.int32, device=x.device)
     dyx = torch.empty((B, V), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().etch_nn_bidir(B, N, V, _ptr(x), _ptr(y), _optptr(xl), _optptr(yl), _ptr(ws), _ptr(ixy), _ptr(dxy), _ptr(iyx), _ptr(dyx),
-                                        _stream()), "etch_nn_bidir")
+    _lib.call("etch_nn_bidir", B, N, V, x, y, xl, yl, ws, ixy, dxy, iyx, dyx)
     return ixy, dxy, iyx, dyx
 
 
@@ -1397,9 +1319,7 @@ def chamfer_grad(x, y, idx_xy, idx_yx, w_xy=None, w_yx=None, x_lengths=None, y_l
     ws = torch.empty((max(3 * B * (N + V), 1),), dtype=torch.int64, device=x.device)
     gx = torch.empty_like(x) if want_x else None
     gy = torch.empty_like(y) if want_y else None
-    _lib.check(_lib.lib().etch_chamfer_grad(B, N, V, _ptr(x), _ptr(y), _optptr(xl), _optptr(yl), _ptr(_need(idx_xy, torch.int32, "idx_xy")),
-                                            _ptr(_need(idx_yx, torch.int32, "idx_yx")), _optptr(w_xy), _optptr(w_yx), _ptr(ws), _optptr(gx),
-                                            _optptr(gy), _stream()), "etch_chamfer_grad")
+    _lib.call("etch_chamfer_grad", B, N, V, x, y, xl, yl, _need(idx_xy, torch.int32, "idx_xy"), _need(idx_yx, torch.int32, "idx_yx"), w_xy, w_yx, ws, gx, gy)
     return gx, gy
 
 
@@ -1411,8 +1331,7 @@ def _check_body(consts, nj, nb, n_extra):
 
 def _refine_workspace(B, N, V, nj, nb, n_extra, device):
     n = ctypes.c_longlong(0)
-    _lib.check(_lib.lib().etch_smpl_chamfer_refine_workspace(B, N, V, int(nj), int(nb), int(n_extra), ctypes.byref(n)),
-               "etch_smpl_chamfer_refine_workspace")
+    _lib.call("etch_smpl_chamfer_refine_workspace", B, N, V, int(nj), int(nb), int(n_extra), ctypes.byref(n))
     return torch.empty((max(int(n.value), 8),), dtype=torch.uint8, device=device)
 
 
@@ -1427,8 +1346,7 @@ def smpl_lbs_vjp(consts, params, g, nj=24, nb=10, n_extra=21):
     arr = (ctypes.c_void_p * 8)(*[t.data_ptr() for t in consts])
     ws = _refine_workspace(B, 0, V, nj, nb, n_extra, g.device)
     grad = torch.empty_like(params)
-    _lib.check(_lib.lib().etch_smpl_lbs_vjp(B, V, int(nj), int(nb), int(n_extra), arr, _ptr(params), _ptr(g), _ptr(ws), _ptr(grad), _stream()),
-               "etch_smpl_lbs_vjp")
+    _lib.call("etch_smpl_lbs_vjp", B, V, int(nj), int(nb), int(n_extra), arr, params, g, ws, grad)
     return grad
 
 
@@ -1456,10 +1374,8 @@ def smpl_chamfer_refine(consts, scan, params, V, scan_lengths=None, prior=None, 
     joints = torch.empty((B, nj + n_extra, 3), dtype=torch.float32, device=scan.device)
     loss = torch.empty((B,), dtype=torch.float32, device=scan.device)
     tr = torch.empty((B, iters), dtype=torch.float32, device=scan.device) if want_trace else None
-    _lib.check(_lib.lib().etch_smpl_chamfer_refine(B, N, int(V), int(nj), int(nb), int(n_extra), arr, _ptr(scan), _optptr(sl), parr, G, int(bidir),
-                                                   int(iters), _c_float(lr), _c_float(beta1), _c_float(beta2), _c_float(eps), _ptr(params),
-                                                   _ptr(verts), _ptr(joints), _optptr(tr), _ptr(loss), _ptr(ws), _stream()),
-               "etch_smpl_chamfer_refine")
+    _lib.call("etch_smpl_chamfer_refine", B, N, int(V), int(nj), int(nb), int(n_extra), arr, scan, sl, parr, G, int(bidir), int(iters), float(lr), float(beta1),
+              float(beta2), float(eps), params, verts, joints, tr, loss, ws)
     return verts, joints, loss, tr
 
 
@@ -1476,9 +1392,9 @@ def _check_mesh(verts, faces):
     return verts.shape[0], faces.shape[0]
 
 
-def _mesh_workspace(fn, n, F, device):
+def _mesh_workspace(query, n, F, device):
     b = ctypes.c_longlong(0)
-    _lib.check(fn(int(n), int(F), ctypes.byref(b)), "workspace query")
+    _lib.call(query, int(n), int(F), ctypes.byref(b))
     return torch.empty((max(int(b.value), 8),), dtype=torch.uint8, device=device)
 
 
@@ -1496,13 +1412,12 @@ def ray_first_hit(origins, dirs, verts, faces, excl_face=None, t_max=None):
     if t_max is not None and (_need(t_max, torch.float64, "t_max").shape != (R,)):
         raise _lib.EtchHipError(f"t_max must be ({R},)")
     dev = origins.device
-    ws = _mesh_workspace(_lib.lib().etch_ray_first_hit_workspace, R, F, dev)
+    ws = _mesh_workspace("etch_ray_first_hit_workspace", R, F, dev)
     face = torch.empty((R,), dtype=torch.int32, device=dev)
     t = torch.empty((R,), dtype=torch.float64, device=dev)
     bary = torch.empty((R, 3), dtype=torch.float64, device=dev)
     loc = torch.empty((R, 3), dtype=torch.float64, device=dev)
-    _lib.check(_lib.lib().etch_ray_first_hit(R, F, _ptr(origins), _ptr(dirs), _ptr(verts), _ptr(faces), _optptr(excl_face), _optptr(t_max), _ptr(ws),
-                                             _ptr(face), _ptr(t), _ptr(bary), _ptr(loc), _stream()), "etch_ray_first_hit")
+    _lib.call("etch_ray_first_hit", R, F, origins, dirs, verts, faces, excl_face, t_max, ws, face, t, bary, loc)
     return face, t, bary, loc
 
 
@@ -1515,13 +1430,12 @@ def closest_point_on_mesh(points, verts, faces):
     P = points.shape[0]
     _, F = _check_mesh(verts, faces)
     dev = points.device
-    ws = _mesh_workspace(_lib.lib().etch_closest_point_on_mesh_workspace, P, F, dev)
+    ws = _mesh_workspace("etch_closest_point_on_mesh_workspace", P, F, dev)
     face = torch.empty((P,), dtype=torch.int32, device=dev)
     bary = torch.empty((P, 3), dtype=torch.float64, device=dev)
     closest = torch.empty((P, 3), dtype=torch.float64, device=dev)
     d2 = torch.empty((P,), dtype=torch.float64, device=dev)
-    _lib.check(_lib.lib().etch_closest_point_on_mesh(P, F, _ptr(points), _ptr(verts), _ptr(faces), _ptr(ws), _ptr(face), _ptr(bary), _ptr(closest),
-                                                     _ptr(d2), _stream()), "etch_closest_point_on_mesh")
+    _lib.call("etch_closest_point_on_mesh", P, F, points, verts, faces, ws, face, bary, closest, d2)
     return face, bary, closest, d2
 
 
@@ -1544,8 +1458,7 @@ def vertex_normals(verts, faces):
     idx_d = torch.from_numpy(idx).to(verts.device)
     ws = torch.empty((max(6 * F, 1),), dtype=torch.float64, device=verts.device)
     out = torch.empty((V, 3), dtype=torch.float64, device=verts.device)
-    _lib.check(_lib.lib().etch_vertex_normals(V, F, _ptr(verts), _ptr(faces), _ptr(ptr_d), _ptr(idx_d), _ptr(ws), _ptr(out), _stream()),
-               "etch_vertex_normals")
+    _lib.call("etch_vertex_normals", V, F, verts, faces, ptr_d, idx_d, ws, out)
     return out
 
 
@@ -1558,7 +1471,7 @@ def remove_close(points, radius):
     r = float(radius)
     deg = torch.empty((C,), dtype=torch.int32, device=points.device)
     rem = torch.empty((C,), dtype=torch.int32, device=points.device)
-    _lib.check(_lib.lib().etch_remove_close(C, _ptr(points), ctypes.c_double(r * r), _ptr(deg), _ptr(rem), _stream()), "etch_remove_close")
+    _lib.call("etch_remove_close", C, points, r * r, deg, rem)
     return deg, rem.bool()
 
 
@@ -1594,7 +1507,7 @@ def geodesic_heat(verts, topo, sources, t_coef=1.0, intrinsic_delaunay=True, wan
         raise _lib.EtchHipError(f"source indices must lie in [0, {V})")
     dev = verts.device
     nb = ctypes.c_longlong(0)
-    _lib.check(_lib.lib().etch_geodesic_workspace(B, V, F, E, S, ctypes.byref(nb)), "etch_geodesic_workspace")
+    _lib.call("etch_geodesic_workspace", B, V, F, E, S, ctypes.byref(nb))
     ws = torch.empty((max(int(nb.value), 8),), dtype=torch.uint8, device=dev)
     dist = torch.empty((B, S, V), dtype=torch.float64, device=dev)
     dmin = torch.empty((B, V), dtype=torch.float64, device=dev) if want_min else None
@@ -1605,12 +1518,9 @@ def geodesic_heat(verts, topo, sources, t_coef=1.0, intrinsic_delaunay=True, wan
     if want_mesh:
         mesh = {"ev": torch.empty((B, E, 2), dtype=torch.int32, device=dev), "el": torch.empty((B, E), dtype=torch.float64, device=dev),
                 "ecot": torch.empty((B, E, 2), dtype=torch.float64, device=dev), "area": torch.empty((B, F), dtype=torch.float64, device=dev)}
-    _lib.check(_lib.lib().etch_geodesic_heat(B, V, F, E, S, _ptr(verts), _ptr(fv), _ptr(fe), _ptr(fs), _ptr(ef), _ptr(ev), _ptr(sources),
-                                             ctypes.c_double(t_coef), int(bool(intrinsic_delaunay)), ctypes.c_double(mollify_eps),
-                                             ctypes.c_double(delaunay_tol), int(max_rounds), ctypes.c_double(heat_tol), ctypes.c_double(heat_omega), int(heat_cap),
-                                             ctypes.c_double(cg_rtol), int(cg_cap), _ptr(ws), _ptr(dist), _optptr(dmin), _optptr(label), _ptr(iters),
-                                             flips, _optptr(mesh.get("ev")), _optptr(mesh.get("el")), _optptr(mesh.get("ecot")),
-                                             _optptr(mesh.get("area")), _stream()), "etch_geodesic_heat")
+    _lib.call("etch_geodesic_heat", B, V, F, E, S, verts, fv, fe, fs, ef, ev, sources, t_coef, int(bool(intrinsic_delaunay)), mollify_eps, delaunay_tol,
+              int(max_rounds), heat_tol, heat_omega, int(heat_cap), cg_rtol, int(cg_cap), ws, dist, dmin, label, iters, flips, mesh.get("ev"), mesh.get("el"),
+              mesh.get("ecot"), mesh.get("area"))
     it = iters.cpu()
     if bool((it < 0).any()):
         bad = torch.nonzero((it < 0).any(2))[:4].tolist()
@@ -1661,36 +1571,34 @@ def train_losses(direction, magnitude, confidences, part_labels, t_vectors, t_co
         raise _lib.EtchHipError("train_losses: empty targets")
     M = part_labels.shape[2] if part_labels is not None else 0
     dev = first.device
-    key = (dev.index, _stream().value)
+    key = (dev.index, _lib.stream())
     ws = _TRAIN_LOSS_WS.get(key)
     if ws is None:
-        ws = _TRAIN_LOSS_WS[key] = torch.empty((_lib.lib().etch_train_losses_workspace_doubles(),), dtype=torch.float64, device=dev)
+        ws = _TRAIN_LOSS_WS[key] = torch.empty((_lib.call("etch_train_losses_workspace_doubles"),), dtype=torch.float64, device=dev)
     losses = torch.empty((5,), dtype=torch.float32, device=dev)
     if status is None:
         status = torch.zeros((1,), dtype=torch.int32, device=dev)
     grads = [torch.empty_like(h) if h is not None else None for h in heads]
-    w = [ctypes.c_float(float(x)) for x in weights]
+    w = [float(x) for x in weights]
     used_t = [t_vectors if (direction is not None or magnitude is not None) else None, t_confidences if confidences is not None else None,
               t_labels if part_labels is not None else None]
-    _lib.check(_lib.lib().etch_train_losses(int(B), int(K), int(N), int(M), *[_optptr(h) for h in heads], *[_optptr(t) for t in used_t], _ptr(index),
-                                            w[0], w[1], w[2], w[3], ctypes.c_float(float(scale_magnitude)), _ptr(ws), _ptr(counter), _ptr(losses),
-                                            _ptr(status), *[_optptr(g) for g in grads], _stream()), "etch_train_losses")
+    _lib.call("etch_train_losses", int(B), int(K), int(N), int(M), *heads, *used_t, index, w[0], w[1], w[2], w[3],
+              float(scale_magnitude), ws, counter, losses, status, *grads)
     return losses, status, grads
 
 
 def guarded_adam_chunk():
-    return int(_lib.lib().etch_guarded_adam_chunk())
+    return _lib.call("etch_guarded_adam_chunk")
 
 
 def guarded_adam_step(T, C, chunk_tensor, first_chunk, numel, pmv, grads, status, steps, chunkflags, lr, betas, eps, counters):
     """etch_guarded_adam_step over tables built by etch_amd.optim.GuardedAdam (all device tensors; status may be None)."""
-    _lib.check(_lib.lib().etch_guarded_adam_step(int(T), int(C), _ptr(chunk_tensor), _ptr(first_chunk), _ptr(numel), _ptr(pmv), _ptr(grads), _optptr(status),
-                                                 _ptr(steps), _ptr(chunkflags), ctypes.c_double(lr), ctypes.c_double(betas[0]), ctypes.c_double(betas[1]),
-                                                 ctypes.c_double(eps), _ptr(counters), _stream()), "etch_guarded_adam_step")
+    _lib.call("etch_guarded_adam_step", int(T), int(C), chunk_tensor, first_chunk, numel, pmv, grads, status, steps, chunkflags, lr, betas[0], betas[1], eps,
+              counters)
 
 
 def grad_tail_floats():
-    return int(_lib.lib().etch_grad_tail_floats())
+    return _lib.call("etch_grad_tail_floats")
 
 
 def grad_pack(T, C, chunk_tensor, first_chunk, numel, grads, offsets, flat, scale, mode, losses=None, status=None, tail_offset=-1, *, layout):
@@ -1719,9 +1627,8 @@ def grad_pack(T, C, chunk_tensor, first_chunk, numel, grads, offsets, flat, scal
                 raise _lib.EtchHipError("grad_pack: losses must hold 5 values")
         if status is not None:
             _need(status, torch.int32, "status")
-    _lib.check(_lib.lib().etch_grad_pack(int(T), int(C), _ptr(chunk_tensor), _ptr(first_chunk), _ptr(numel), _ptr(grads), _ptr(offsets), _ptr(flat),
-                                         ctypes.c_float(float(scale)), int(mode), _optptr(losses), _optptr(status), ctypes.c_longlong(int(tail_offset)),
-                                         _stream()), "etch_grad_pack")
+    _lib.call("etch_grad_pack", int(T), int(C), chunk_tensor, first_chunk, numel, grads, offsets, flat, float(scale), int(mode), losses, status,
+              int(tail_offset))
 
 
 def grad_unpack_tail(tail, losses=None, status=None):
@@ -1735,7 +1642,7 @@ def grad_unpack_tail(tail, losses=None, status=None):
     if status is None:
         status = torch.zeros((1,), dtype=torch.int32, device=tail.device)
     _need(losses, torch.float32, "losses"), _need(status, torch.int32, "status")
-    _lib.check(_lib.lib().etch_grad_unpack_tail(_ptr(tail), _ptr(losses), _ptr(status), _stream()), "etch_grad_unpack_tail")
+    _lib.call("etch_grad_unpack_tail", tail, losses, status)
     return losses, status
 
 
@@ -1745,7 +1652,7 @@ def bbox_center(verts, vert_offsets):
     _need(verts, torch.float64, "verts"), _need(vert_offsets, torch.int32, "vert_offsets")
     B = vert_offsets.numel() - 1
     center = torch.empty((B, 3), dtype=torch.float64, device=verts.device)
-    _lib.check(_lib.lib().etch_bbox_center(int(B), _ptr(verts), _ptr(vert_offsets), _ptr(center), _stream()), "etch_bbox_center")
+    _lib.call("etch_bbox_center", int(B), verts, vert_offsets, center)
     return center
 
 
@@ -1761,12 +1668,11 @@ def sample_surface(verts, faces, vert_offsets, face_offsets, keys, num_points, t
         raise _lib.EtchHipError("sample_surface: offsets must be (B+1), faces (total_faces,3) and num_points >= 0")
     if center is not None and _need(center, torch.float64, "center").shape != (B, 3):
         raise _lib.EtchHipError(f"center must be ({B},3)")
-    ws = _mesh_workspace(_lib.lib().etch_sample_surface_workspace, B, total_faces, dev)
+    ws = _mesh_workspace("etch_sample_surface_workspace", B, total_faces, dev)
     p32 = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
     p64 = torch.empty((B, N, 3), dtype=torch.float64, device=dev) if want_fp64 else None
     face = torch.empty((B, N), dtype=torch.int32, device=dev)
     status = torch.empty((B,), dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().etch_sample_surface(int(B), N, int(total_faces), int(max_faces), _ptr(verts), _ptr(faces), _ptr(vert_offsets), _ptr(face_offsets),
-                                              _ptr(keys), _optptr(center), _ptr(ws), _ptr(p32), _optptr(p64), _ptr(face), _ptr(status), _stream()),
-               "etch_sample_surface")
+    _lib.call("etch_sample_surface", int(B), N, int(total_faces), int(max_faces), verts, faces, vert_offsets, face_offsets, keys, center, ws, p32, p64, face,
+              status)
     return p32, p64, face, status

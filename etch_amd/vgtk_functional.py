@@ -5,7 +5,6 @@ the way the reference spells `vgtk.so3conv.functional`.
 These are the UN-FUSED forms: they materialise the tensors the reference materialises (the [b,p,60,24,nn] kernel weights are 921 MB
 per 5 000-point scan at the first conv).  The model itself never calls them -- `InterSO3Conv` / `IntraSO3Conv` run the fused
 kernels -- they serve callers of the operator API and cross-check the fused kernels in tests/test_gpu_functional.py."""
-import ctypes
 import math
 
 import torch
@@ -13,7 +12,7 @@ import torch
 from . import _lib
 from . import constants as K
 from . import ops
-from .ops import _c_float, _need, _ptr, _stream
+from .ops import _need
 
 
 def batched_index_select(input, dim, index):
@@ -33,7 +32,7 @@ def index_points(points, idx):
     B, N, C = points.shape
     S = idx.numel() // B
     out = torch.empty((B, S, C), dtype=torch.float32, device=points.device)
-    _lib.check(_lib.lib().etch_index_points(B, N, ctypes.c_long(S), C, _ptr(points), _ptr(idx), _ptr(out), _stream()), "etch_index_points")
+    _lib.call("etch_index_points", B, N, S, C, points, idx, out)
     return out.view(*idx.shape, C)
 
 
@@ -44,7 +43,7 @@ def square_distance(src, dst):
     B, N, C = src.shape
     M = dst.shape[1]
     out = torch.empty((B, N, M), dtype=torch.float32, device=src.device)
-    _lib.check(_lib.lib().etch_square_distance(B, N, M, C, _ptr(src), _ptr(dst), _ptr(out), _stream()), "etch_square_distance")
+    _lib.call("etch_square_distance", B, N, M, C, src, dst, out)
     return out
 
 
@@ -106,8 +105,7 @@ def inter_so3conv_grouping_anchor(grouped_xyz, anchors, kernels, sigma, interpol
     # rotated kernel points exactly as functional.py:296 (host matmul, then uploaded), laid out [na, ks, 3]
     rk = torch.matmul(anchors.detach().cpu(), kernels.detach().cpu().transpose(0, 1)).permute(0, 2, 1).contiguous().to(grouped_xyz.device)
     w = torch.empty((b, p, na, ks, nn), dtype=torch.float32, device=grouped_xyz.device)
-    _lib.check(_lib.lib().etch_inter_kernel_weights(b, p, nn, na, ks, _ptr(grouped_xyz), _ptr(rk), _c_float(sigma), _ptr(w), _stream()),
-               "etch_inter_kernel_weights")
+    _lib.call("etch_inter_kernel_weights", b, p, nn, na, ks, grouped_xyz, rk, float(sigma), w)
     return w
 
 
@@ -120,8 +118,7 @@ def inter_so3conv_feat_grouping(inter_idx, inter_w, feats):
     _, c, q, na = feats.shape
     ks = inter_w.shape[3]
     out = torch.empty((b, c, ks, p, na), dtype=torch.float32, device=feats.device)
-    _lib.check(_lib.lib().etch_inter_feat_grouping(b, c, q, p, nn, na, ks, _ptr(idx), _ptr(inter_w), _ptr(feats), _ptr(out), _stream()),
-               "etch_inter_feat_grouping")
+    _lib.call("etch_inter_feat_grouping", b, c, q, p, nn, na, ks, idx, inter_w, feats, out)
     return out
 
 
@@ -147,7 +144,7 @@ def intra_so3conv_grouping(intra_idx, feature):
     nb, c, nq, na = feature.shape
     pnn = ii.shape[1]
     out = torch.empty((nb, c, pnn, nq, na), dtype=torch.float32, device=feature.device)
-    _lib.check(_lib.lib().etch_intra_grouping(nb, c, nq, na, pnn, _ptr(ii), _ptr(feature), _ptr(out), _stream()), "etch_intra_grouping")
+    _lib.call("etch_intra_grouping", nb, c, nq, na, pnn, ii, feature, out)
     return out
 
 

@@ -2,7 +2,6 @@ import sys, time
 sys.path.insert(0, '/root/repo')
 import numpy as np, torch
 from etch_amd import ops, _lib
-import ctypes
 dev = torch.device("cuda")
 def scan(seed, n): return (np.random.default_rng(seed).standard_normal((n, 3)) * np.array([0.14, 0.31, 0.085])).astype(np.float32)
 B = 32
@@ -13,9 +12,7 @@ for ns, ms, k in ((5000, 5000, 8), (5000, 5000, 16), (5000, 1250, 16), (1250, 50
     noff = torch.tensor([ms * (i + 1) for i in range(B)], dtype=torch.int32, device=dev)
     idx = torch.empty((B * ms, k), dtype=torch.int32, device=dev); d = torch.empty((B * ms, k), dtype=torch.float32, device=dev)
     def run():
-        _lib.check(_lib.lib().etch_knnquery(B, ms, B * ms, k, ctypes.c_void_p(xyz.data_ptr()), ctypes.c_void_p(q.data_ptr()), ctypes.c_void_p(off.data_ptr()),
-                                            ctypes.c_void_p(noff.data_ptr()), ctypes.c_void_p(idx.data_ptr()), ctypes.c_void_p(d.data_ptr()), 0,
-                                            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "knn")
+        _lib.call("etch_knnquery", B, ms, B * ms, k, xyz, q, off, noff, idx, d, 0)
     run(); torch.cuda.synchronize()
     s = torch.cuda.Event(enable_timing=True); e = torch.cuda.Event(enable_timing=True)
     s.record()

@@ -71,6 +71,33 @@ def test_ball_query_known_answers():
     assert f(3) == [[[1, 2, 4], [0] * 3]]
 
 
+def test_ball_query_under_a_recording_hook():
+    """What bench.py's profile pass relies on: with a hook installed the call arrives as (symbol, args in header order without any tensor, fn),
+    fn(*args) performs it, and the result is the one of the same call without a hook."""
+    from etch_amd import _lib, ops
+    x = scan(2100, 64).T[None]
+    q = np.ascontiguousarray(x[:, :, :16])
+    dq, dx = dev(q), dev(x)
+    plain = ops.ball_query(dq, dx, 0.2, 8)
+    rec = []
+
+    def hook(name, args, fn):
+        rec.append((name, args))
+        return fn(*args)
+
+    lib = _lib.lib()
+    lib.profiler = hook
+    try:
+        hooked = ops.ball_query(dq, dx, 0.2, 8)
+    finally:
+        lib.profiler = None
+    (name, args), = rec
+    assert name == "etch_ball_query"
+    assert not any(isinstance(a, torch.Tensor) for a in args)
+    assert [a.value if hasattr(a, "value") else a for a in args][:3] == [1, 64, 16]
+    assert torch.equal(hooked, plain)
+
+
 def test_gather_points():
     from etch_amd import ops
     rng = np.random.default_rng(0)

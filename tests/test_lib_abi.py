@@ -67,3 +67,146 @@ def test_reference_launcher_symbols_and_prototypes():
         mine = re.search(r"void\s+" + name + r"\s*\([^)]*\)\s*;", hdr).group(0)
         assert _norm(mine) == _norm(proto), (mine, proto)
     assert "etch_knnquery_dev" in _lib.declared_symbols()
+
+
+# ---- the header is the one description of the C ABI: parse, symbol sets, includes, the call helper ----------------------------------------
+NAME_PATTERNS = (r"\bint\s+etch_\w+\(", r"\bvoid\s+\w+_launcher\(",
+                 r"\blong\s+etch_\w+\(")           # the one size that does not fit an int: etch_smpl_lm_split_workspace_bytes
+
+
+def _header_text(experiments):
+    import re
+    txt = open(_lib.HEADER).read()
+    if not experiments:
+        txt = re.sub(r"#ifdef ETCH_BUILD_EXPERIMENTS.*?#endif", "", txt, flags=re.S)
+    return re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+
+
+def test_parse_finds_every_prototype_and_maps_every_type():
+    import ctypes
+    import re
+
+    import pytest
+    counts = {}
+    for experiments in (False, True):
+        protos = _lib.prototypes(experiments=experiments)
+        txt = _header_text(experiments)
+        counts[experiments] = len(protos)
+        assert len(protos) == sum(len(re.findall(p, txt)) for p in NAME_PATTERNS)
+        assert len(re.findall(NAME_PATTERNS[2], txt)) == 1
+        known = set(_lib.CTYPES.values())
+        for name, (ret, params) in protos.items():
+            assert ret in (None, ctypes.c_int, ctypes.c_long), name
+            assert (ret is None) == name.endswith("_launcher"), name
+            for ctype, pname in params:
+                assert ctype in known and ctype is not None and pname.isidentifier(), (name, pname)
+        assert sorted(n for n in protos if n.startswith("etch_")) == _lib.declared_symbols(experiments)
+        assert sorted(n for n in protos if n.endswith("_launcher")) == _lib.declared_launchers()
+    assert counts[True] > counts[False] >= 150
+    ret, params = _lib.prototypes()["etch_linear"]
+    assert ret is ctypes.c_int and len(params) == 21 and params[4] == (ctypes.c_long, "ldx") and params[-1] == (ctypes.c_void_p, "stream")
+    assert _lib.prototypes()["etch_smpl_lm_split_workspace_bytes"][0] is ctypes.c_long
+    assert _lib.prototypes()["etch_pt_attention"][1][9] == (ctypes.c_void_p, "params")          # const float* const*
+    with pytest.raises(_lib.EtchHipError, match="`x` of etch_f.*`short`"):
+        _lib.prototypes(text="int etch_f(int a, short x, void* stream);")
+
+
+def _exported(path):
+    """The etch_* / *_launcher functions `path` exports, by llvm-nm of the toolchain hipcc comes from, else nm -D."""
+    import re
+    import shutil
+    import subprocess
+    cc = shutil.which(B.hipcc()) or B.hipcc()
+    root = os.path.dirname(os.path.dirname(os.path.realpath(cc)))
+    tools = [os.path.join(root, *d, "llvm-nm") for d in (("lib", "llvm", "bin"), ("llvm", "bin"), ("bin",))] + [shutil.which("llvm-nm"), shutil.which("nm")]
+    nm = next(t for t in tools if t and os.path.exists(t))
+    out = subprocess.run([nm, "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    return {m.group(1) for m in re.finditer(r"\sT\s+(etch_\w+|\w+_launcher)\s*$", out, flags=re.M)}
+
+
+def test_header_and_libraries_agree_on_the_symbol_set():
+    for path, experiments in ((B.build(), False), (B.build_experiments(), True)):
+        assert _exported(path) == set(_lib.prototypes(experiments=experiments)), path
+
+
+def test_every_kernel_source_includes_the_header():
+    import re
+    names = set(_lib.prototypes(experiments=True))
+    csrc = os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "csrc")
+    exporting = 0
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith(".hip"):
+            continue
+        txt = open(os.path.join(csrc, f)).read()
+        if any(n in names for n in re.findall(r"\b(?:int|long|void)\s+(\w+)\s*\([^;{}]*\)\s*\{", txt)):
+            exporting += 1
+            assert re.search(r'^#include "etch_hip.h"', txt, flags=re.M), f
+    assert exporting >= 20
+
+
+def test_no_hand_written_prototypes_or_pointer_helpers_in_the_package():
+    import re
+    root = os.path.dirname(os.path.abspath(_lib.__file__))
+    for dp, _, fs in os.walk(root):
+        for f in fs:
+            if not f.endswith(".py"):
+                continue
+            txt = open(os.path.join(dp, f)).read()
+            if f != "_lib.py":
+                assert not re.search(r"\.(restype|argtypes)\b", txt), f
+            assert not re.search(r"(?<!def )\b(_ptr|_optptr|_c_float|_c_long)\(|\bdef _check\(status", txt), f     # (ops._ptr stays for direct callers only)
+
+
+class _Entered(Exception):
+    pass
+
+
+def test_call_helper_rejects_bad_calls_before_the_c_function():
+    import pytest
+    B.build()
+    name = "etch_fps_split_workspace_bytes"
+    assert _lib.call(name, 3, 4) == 1600                      # index_ops.hip: 64 + nseg * 2 * G * 64
+    lib = _lib.lib()
+    entered = []
+
+    def hook(sym, args, fn):
+        entered.append((sym, args))
+        return fn(*args)
+
+    lib.profiler = hook
+    try:
+        for bad in ((3,), (3, 4, 5)):
+            with pytest.raises(_lib.EtchHipError, match=name + " takes 2 arguments"):
+                _lib.call(name, *bad)
+        assert entered == []                                  # a wrong count never reaches the hook, let alone the C function
+        with pytest.raises(_lib.EtchHipError, match=name + ".*argument 1"):
+            _lib.call(name, 3.0, 4)                           # ctypes converts every argument before it enters the function
+        assert entered == [(name, (3.0, 4))]
+    finally:
+        lib.profiler = None
+    with pytest.raises(_lib.EtchHipError, match=name + ".*argument 1"):
+        _lib.call(name, 3.0, 4)
+    with pytest.raises(_lib.EtchHipError, match="not declared"):
+        _lib.call("etch_no_such_function", 1)
+    with pytest.raises(_lib.EtchHipError, match="etch_smpl_lm_split_workspace_bytes failed: unsupported size") as e:
+        _lib.call("etch_smpl_lm_split_workspace_bytes", 1, 3, 3, 2)      # no such body model: a host-only function's negative value is its error
+    assert e.value.status == -2
+
+
+def test_profiler_hook_sees_the_call():
+    B.build()
+    lib = _lib.lib()
+    seen = []
+
+    def hook(sym, args, fn):
+        seen.append((sym, args, fn))
+        return fn(*args)
+
+    lib.profiler = hook
+    try:
+        assert _lib.call("etch_fps_split_workspace_bytes", 3, 4) == 1600
+    finally:
+        lib.profiler = None
+    (sym, args, fn), = seen
+    assert (sym, args) == ("etch_fps_split_workspace_bytes", (3, 4)) and fn(*args) == 1600
+    assert lib.etch_fps_split_workspace_bytes(3, 4) == 1600                  # plain attribute access stays
