@@ -30,6 +30,7 @@ struct GemmArgs {
 #define G_BM 64
 #define G_BN 64
 #define G_BK 32
+#define G_KC 256  // K per fmaf chain of an accumulator (a multiple of G_BK): longer sums are closed chain by chain, see gemm_nt_kernel
 #define G_LD 40   // padded LDS row (floats): 160 B keeps 16-B alignment and makes the ds_read_b128 fragment reads conflict-free (36 was 2-way)
 
 template <bool VEC>
@@ -49,7 +50,7 @@ __device__ __forceinline__ float4 ld4_guard(const float* row, int k, int K, bool
 // STATS (the strided skip conv of etch_linear_stats): blockIdx.z = sample, R = the rows of ONE sample (a tile never straddles two samples), every lane adds
 // the values it stores and their squares in fp64 and the workgroup writes one [2][O] partial per 64-row tile (a.stat: [sample][tile][2][O]), lane groups and
 // waves summed in a fixed order through LDS.  Y is bitwise what the plain kernel writes for the same rows: a row's MFMA chain does not depend on its tile.
-template <bool VECX, bool VECW, int BN, int BM = 64, int WAVES = 4, bool STATS = false>   // block tile BM rows x BN outputs, WAVES waves (2 along M)
+template <bool VECX, bool VECW, int BN, int BM = 64, int WAVES = 4, bool STATS = false, bool LONGK = false>   // block tile BM rows x BN outputs, WAVES waves (2 along M)
 __global__ void __launch_bounds__(WAVES * 64) gemm_nt_kernel(GemmArgs a) {
     constexpr int THREADS = WAVES * 64;
     constexpr int NWN = WAVES / 2;             // waves along the output dimension
@@ -105,7 +106,22 @@ __global__ void __launch_bounds__(WAVES * 64) gemm_nt_kernel(GemmArgs a) {
     for (int h = 0; h < XL; ++h) xv[h] = ld4_guard<VECX>(xrow[h], sc4, a.K, xok[h]);
 #pragma unroll
     for (int h = 0; h < WL; ++h) wv[h] = ld4_guard<VECW>(wrow[h], sc4, a.K, wok[h]);
+    // An accumulator is one fmaf chain along K, and its rounding error grows with the chain's length: at K = 1024 (TransitionUp's head Linear) the
+    // output was 3.5 x further from fp64 than a blocked fp32 sum (tests/test_gpu_pt_fp64.py).  LONGK (K > G_KC, launch_tiled): every G_KC of K the
+    // chain is closed into a second accumulator.  Shorter sums run the kernel without it: their bits and their registers (16 more VGPRs cost a
+    // wave of occupancy) are what they were.
+    f32x4 done[LONGK ? MI : 1][LONGK ? NJ : 1];
+#pragma unroll
+    for (int i = 0; i < (LONGK ? MI : 1); ++i)
+#pragma unroll
+        for (int j = 0; j < (LONGK ? NJ : 1); ++j) done[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
     for (int k0 = 0; k0 < a.K; k0 += G_BK) {
+        if (LONGK && k0 != 0 && k0 % G_KC == 0) {
+#pragma unroll
+            for (int i = 0; i < MI; ++i)
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) { done[i][j] += acc[i][j]; acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+        }
         __syncthreads();   // previous tile fully consumed
 #pragma unroll
         for (int h = 0; h < XL; ++h) *reinterpret_cast<float4*>(&Xs[(srow + RPP * h) * G_LD + sc4]) = xv[h];
@@ -133,6 +149,12 @@ __global__ void __launch_bounds__(WAVES * 64) gemm_nt_kernel(GemmArgs a) {
             G_STEP(x) G_STEP(y) G_STEP(z) G_STEP(w)
 #undef G_STEP
         }
+    }
+    if constexpr (LONGK) {
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) acc[i][j] += done[i][j];
     }
     // epilogue: D[row = fg*4 + reg][col = fr]
     double st_s[NJ], st_q[NJ];
@@ -192,6 +214,13 @@ __global__ void __launch_bounds__(WAVES * 64) gemm_nt_kernel(GemmArgs a) {
 template <int BN, int BM = 64, int WAVES = 4>
 static void launch_tiled(const GemmArgs& a, bool vx, bool vw, hipStream_t st) {
     dim3 grid((a.R + BM - 1) / BM, (a.O + BN - 1) / BN);
+    if (a.K > G_KC) {      // long sums: accumulation chains closed every G_KC
+        if (vx && vw) hipLaunchKernelGGL((gemm_nt_kernel<true, true, BN, BM, WAVES, false, true>), grid, dim3(WAVES * 64), 0, st, a);
+        else if (vx) hipLaunchKernelGGL((gemm_nt_kernel<true, false, BN, BM, WAVES, false, true>), grid, dim3(WAVES * 64), 0, st, a);
+        else if (vw) hipLaunchKernelGGL((gemm_nt_kernel<false, true, BN, BM, WAVES, false, true>), grid, dim3(WAVES * 64), 0, st, a);
+        else hipLaunchKernelGGL((gemm_nt_kernel<false, false, BN, BM, WAVES, false, true>), grid, dim3(WAVES * 64), 0, st, a);
+        return;
+    }
     if (vx && vw) hipLaunchKernelGGL((gemm_nt_kernel<true, true, BN, BM, WAVES>), grid, dim3(WAVES * 64), 0, st, a);
     else if (vx) hipLaunchKernelGGL((gemm_nt_kernel<true, false, BN, BM, WAVES>), grid, dim3(WAVES * 64), 0, st, a);
     else if (vw) hipLaunchKernelGGL((gemm_nt_kernel<false, true, BN, BM, WAVES>), grid, dim3(WAVES * 64), 0, st, a);
