@@ -1,4 +1,5 @@
-// Body-model kinematics shared by the LM / LBS kernels (smpl_fit.hip) and the chamfer refinement (chamfer_fit.hip):
+// Body-model kinematics shared by the LM / LBS kernels (smpl_fit.hip), the chamfer refinement (chamfer_fit.hip) and the skinning frames
+// of the registration (register.hip):
 // batch_rodrigues with its derivative, the joint-angle lookup of the LM variable vector and forward kinematics, in fp64.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -48,4 +49,25 @@ __device__ inline void fk_chain(int nj, const int* parents, const double* R, con
         const double d[3] = {Jj[j * 3] - Jj[p * 3], Jj[j * 3 + 1] - Jj[p * 3 + 1], Jj[j * 3 + 2] - Jj[p * 3 + 2]};
         for (int a = 0; a < 3; ++a) tw[j * 3 + a] = Rp[a * 3] * d[0] + Rp[a * 3 + 1] * d[1] + Rp[a * 3 + 2] * d[2] + tw[p * 3 + a];
     }
+}
+
+// The pose set-up of a full-mesh kernel, by one workgroup (>= nj threads, every thread calls it): xs (the variable vector, already in LDS
+// and synchronised) -> joint rotations R, shaped rest joints Jj, the world chain (Rw, tw).  All arrays are LDS.  R and Jj are synchronised
+// on return; Rw and tw are thread 0's until the caller's next __syncthreads().
+__device__ inline void smpl_block_chain(int nj, int nb, const float* J0, const float* Jd, const int* parents, const double* xs, double* R, double* Jj,
+                                        double* Rw, double* tw) {
+    const int tid = threadIdx.x, npose = 3 * (nj - 1);
+    if (tid < nj) {
+        double th[3];
+        joint_theta(xs, tid, npose, nb, th);
+        float dummy[3][9];
+        rodrigues_d(th, R + tid * 9, dummy, false);
+        for (int c = 0; c < 3; ++c) {
+            double v = J0[tid * 3 + c];
+            for (int l = 0; l < nb; ++l) v += (double)Jd[(tid * 3 + c) * nb + l] * xs[npose + l];
+            Jj[tid * 3 + c] = v;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) fk_chain(nj, parents, R, Jj, Rw, tw);
 }

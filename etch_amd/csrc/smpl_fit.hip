@@ -1297,19 +1297,7 @@ __global__ void __launch_bounds__(256) smpl_lbs_kernel(LbsConsts C, int NJ, int 
     if (tid < DOF) xs[tid] = (double)x[(size_t)b * DOF + tid];
     if (tid < NJ) parents[tid] = C.parents[tid];
     __syncthreads();
-    if (tid < NJ) {
-        double th[3];
-        joint_theta(xs, tid, NPOSE, NB, th);
-        float dummy[3][9];
-        rodrigues_d(th, R + tid * 9, dummy, false);
-        for (int c = 0; c < 3; ++c) {
-            double v = C.J0[tid * 3 + c];
-            for (int l = 0; l < NB; ++l) v += (double)C.Jd[(tid * 3 + c) * NB + l] * xs[NPOSE + l];
-            Jj[tid * 3 + c] = v;
-        }
-    }
-    __syncthreads();
-    if (tid == 0) fk_chain(NJ, parents, R, Jj, Rw, tw);
+    smpl_block_chain(NJ, NB, C.J0, C.Jd, parents, xs, R, Jj, Rw, tw);
     for (int e = tid; e < NPF; e += 256) { const int k = 1 + e / 9, q = e % 9; pf[e] = (float)(R[k * 9 + q] - ((q % 4 == 0) ? 1.0 : 0.0)); }
     __syncthreads();
     if (tid < NJ) {                            // A_j = [Rw_j | tw_j - Rw_j J_j]

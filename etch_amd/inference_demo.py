@@ -114,18 +114,27 @@ def parse_args(argv=None):
     return add_flags(parser).parse_args(argv)
 
 
-def _refine_and_save(args, model, points, centered_mesh, original_center, scan_name, export=Mesh.export):
-    """--chamfer_refine: the marker fit, then fit_cham against the centred scan's vertices (the script's `vertices_scan`).  The OBJ is the
-    refined mesh moved back by the scan centre; the .npz holds the refined parameters, `scale`, and the joints in the centred scan's
-    frame ((joints + trans) * scale, the frame the LM joints of an unrefined run are written in)."""
+def fit_and_refine(args, model, points, centered_mesh):
+    """The marker fit of points (N,3), then with --chamfer_refine fit_cham against the centred scan's vertices (the script's `vertices_scan`).
+    -> the fit's meshes, the body model, the refined vertices (None without --chamfer_refine) and the parameters as fit_cham's dict (without
+    --chamfer_refine its `init`, the marker fit's)."""
     from .models.chamfer_refine import fit_cham, init_from_fit
     from .models.fit_SMPL import _resolve_body_model
 
     points_tensor = torch.from_numpy(points).float().unsqueeze(0).to(args.device)
     meshes, _, _, _, dev = predict_smpl_batch(args, model, points_tensor, args.gender, return_trace=True)
     bm = _resolve_body_model(args, args.gender)
-    scan = torch.from_numpy(np.asarray(centered_mesh.vertices, np.float32)).unsqueeze(0).to(args.device)
-    verts, prm = fit_cham(bm, scan, init_from_fit(dev), prior=None, bidir=args.chamfer_refine, iterations=args.refine_iters)
+    verts, prm = None, init_from_fit(dev)
+    if args.chamfer_refine != "none":
+        scan = torch.from_numpy(np.asarray(centered_mesh.vertices, np.float32)).unsqueeze(0).to(args.device)
+        verts, prm = fit_cham(bm, scan, prm, prior=None, bidir=args.chamfer_refine, iterations=args.refine_iters)
+    return meshes, bm, verts, prm
+
+
+def _refine_and_save(args, model, points, centered_mesh, original_center, scan_name, export=Mesh.export):
+    """--chamfer_refine: the OBJ is the refined mesh moved back by the scan centre; the .npz holds the refined parameters, `scale`, and the
+    joints in the centred scan's frame ((joints + trans) * scale, the frame the LM joints of an unrefined run are written in)."""
+    meshes, _, verts, prm = fit_and_refine(args, model, points, centered_mesh)
     final = Mesh(verts[0] + original_center, meshes[0].faces)
     export(final, os.path.join(args.output_folder, f"{scan_name}_pred_smpl.obj"))
     pose = prm["pose"][0].cpu().numpy()
@@ -160,8 +169,10 @@ def _ingest_device(args):
     return points, Mesh(scan_mesh.vertices - center, scan_mesh.faces), center
 
 
-def main(argv=None):
-    args = parse_args(argv)
+def prepare(args):
+    """What a single-scan command does between parsing its flags and the fit: the device, the markerset, the body model, the pose prior and
+    the output folder into args; the network; the scan read, centred and sampled (--ingest).  -> model, the OBJ writer, points (N,3) float32
+    numpy, the centred mesh, the centre, the scan's name."""
     if not torch.cuda.is_available():
         raise RuntimeError("etch_amd needs an AMD GPU (gfx950); there is no CPU path")
     args.cuda = True
@@ -186,6 +197,12 @@ def main(argv=None):
         centered_mesh, original_center = preprocess_scan(args.scan_path)
         points = sample_points_from_mesh(centered_mesh, args.num_point, args.seed)
     scan_name = os.path.splitext(os.path.basename(args.scan_path))[0]
+    return model, export, points, centered_mesh, original_center, scan_name
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    model, export, points, centered_mesh, original_center, scan_name = prepare(args)
     if args.chamfer_refine != "none":
         _refine_and_save(args, model, points, centered_mesh, original_center, scan_name, export)
         print(f"Predicted SMPL mesh and smpl info saved under {args.output_folder}")

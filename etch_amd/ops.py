@@ -1379,6 +1379,122 @@ def smpl_chamfer_refine(consts, scan, params, V, scan_lengths=None, prior=None, 
     return verts, joints, loss, tr
 
 
+# ------------------------------------------------------------------ SMPL+D registration and re-posing (csrc/register.hip)
+def smpl_skin_frames(consts, params, nj=24, nb=10):
+    """params (B, 3 nj + nb + 4) = pose (global orient first) | beta | trans | scale -> base (B,V,3), R (B,V,9), A (B,nj,12) with
+    verts(D) = base + R D.  consts: the LBS tables of _DeviceBody.lbs_consts."""
+    _need(params, torch.float32, "params")
+    _check_body(consts, nj, nb, consts[7].numel() if len(consts) == 8 else -1)
+    if params.dim() != 2 or params.shape[1] != 3 * nj + nb + 4:
+        raise _lib.EtchHipError(f"params must be (B, {3 * nj + nb + 4}), got {tuple(params.shape)}")
+    B, V = params.shape[0], consts[0].shape[0]
+    arr = (ctypes.c_void_p * 7)(*[t.data_ptr() for t in consts[:7]])
+    base = torch.empty((B, V, 3), dtype=torch.float32, device=params.device)
+    R = torch.empty((B, V, 9), dtype=torch.float32, device=params.device)
+    A = torch.empty((B, nj, 12), dtype=torch.float32, device=params.device)
+    _lib.call("etch_smpl_skin_frames", B, V, int(nj), int(nb), arr, params, base, R, A)
+    return base, R, A
+
+
+def _check_frames(base, R, D, what):
+    _need(base, torch.float32, "base"), _need(R, torch.float32, "R")
+    if base.dim() != 3 or base.shape[2] != 3 or base.shape[1] == 0 or tuple(R.shape) != (base.shape[0], base.shape[1], 9):
+        raise _lib.EtchHipError(f"{what}: base (B,V,3) and R (B,V,9), got {tuple(base.shape)} and {tuple(R.shape)}")
+    if D is not None:
+        _need(D, torch.float32, "D")
+        if D.shape != base.shape:
+            raise _lib.EtchHipError(f"{what}: D must be {tuple(base.shape)} like base, got {tuple(D.shape)}")
+    return base.shape[0], base.shape[1]
+
+
+def smpld_apply(base, R, D):
+    """verts (B,V,3) = base + R D."""
+    B, V = _check_frames(base, R, D, "smpld_apply")
+    verts = torch.empty_like(base)
+    _lib.call("etch_smpld_apply", B, V, base, R, D, verts)
+    return verts
+
+
+def _check_registration(base, R, D, scan, scan_lengths, nbr_ptr, nbr_idx, n_edges, weights, trunc, what):
+    B, V = _check_frames(base, R, D, what)
+    _need(scan, torch.float32, "scan")
+    if scan.dim() != 3 or scan.shape[0] != B or scan.shape[2] != 3 or scan.shape[1] == 0:
+        raise _lib.EtchHipError(f"{what}: scan must be ({B},N,3) with N >= 1, got {tuple(scan.shape)}")
+    N = scan.shape[1]
+    sl = _lengths(scan_lengths, B, N, scan.device, "scan_lengths")
+    _need(nbr_ptr, torch.int32, "nbr_ptr"), _need(nbr_idx, torch.int32, "nbr_idx")
+    if tuple(nbr_ptr.shape) != (V + 1,) or tuple(nbr_idx.shape) != (2 * int(n_edges),) or n_edges < 0:
+        raise _lib.EtchHipError(f"{what}: nbr_ptr must be ({V + 1},) and nbr_idx (2 n_edges,) = ({2 * int(n_edges)},), got {tuple(nbr_ptr.shape)} and "
+                                f"{tuple(nbr_idx.shape)}")
+    if not all(math.isfinite(float(w)) and float(w) >= 0.0 for w in weights):
+        raise _lib.EtchHipError(f"{what}: the weights must be finite and >= 0")
+    if trunc is not None and not (math.isfinite(float(trunc)) and float(trunc) >= 0.0):
+        raise _lib.EtchHipError(f"{what}: trunc must be None or finite and >= 0")
+    n = ctypes.c_longlong(0)
+    _lib.call("etch_smpld_register_workspace", B, N, V, ctypes.byref(n))
+    ws = torch.empty((max(int(n.value), 8),), dtype=torch.uint8, device=scan.device)
+    return B, N, V, sl, ws, -1.0 if trunc is None else float(trunc)
+
+
+def smpld_energy_grad(base, R, D, scan, nbr_ptr, nbr_idx, n_edges, scan_lengths=None, w_s2m=1.0, w_m2s=1.0, lambda_s=1.0, lambda_m=0.0, trunc=None):
+    """One evaluation of the registration energy at the offsets D (B,V,3): -> terms (B,4) = scan -> body, body -> scan, smoothness,
+    magnitude; grad (B,V,3) = d energy / dD with neighbours and masks held fixed; verts (B,V,3) = base + R D; idx_xy (B,N), idx_yx (B,V) int32,
+    the neighbours of nn_bidir(scan, verts).  nbr_ptr (V+1) / nbr_idx (2 n_edges) int32: the neighbour lists of the mesh edges."""
+    B, N, V, sl, ws, tr = _check_registration(base, R, D, scan, scan_lengths, nbr_ptr, nbr_idx, n_edges, (w_s2m, w_m2s, lambda_s, lambda_m), trunc,
+                                              "smpld_energy_grad")
+    dev = scan.device
+    terms = torch.empty((B, 4), dtype=torch.float32, device=dev)
+    grad, verts = torch.empty_like(base), torch.empty_like(base)
+    ixy = torch.empty((B, N), dtype=torch.int32, device=dev)
+    iyx = torch.empty((B, V), dtype=torch.int32, device=dev)
+    _lib.call("etch_smpld_energy_grad", B, N, V, base, R, D, scan, sl, nbr_ptr, nbr_idx, int(n_edges), float(w_s2m), float(w_m2s), float(lambda_s),
+              float(lambda_m), tr, ws, terms, grad, verts, ixy, iyx)
+    return terms, grad, verts, ixy, iyx
+
+
+def smpld_register(base, R, D, scan, nbr_ptr, nbr_idx, n_edges, lambda_s, scan_lengths=None, w_s2m=1.0, w_m2s=1.0, lambda_m=0.0, trunc=None, lr=1e-3,
+                   want_trace=False):
+    """len(lambda_s) Adam steps on D (B,V,3), updated IN PLACE; step i uses the smoothness weight lambda_s[i].  -> verts (B,V,3) and energy
+    (B,4) of the final D, trace (B,iters,4) = the four terms at the iterate before each step, or None."""
+    lam = [float(l) for l in lambda_s]
+    if len(lam) < 1:
+        raise _lib.EtchHipError("smpld_register: lambda_s must hold one smoothness weight per iteration, at least one")
+    if not (math.isfinite(float(lr)) and float(lr) > 0.0):
+        raise _lib.EtchHipError("smpld_register: lr must be finite and > 0")
+    B, N, V, sl, ws, tr = _check_registration(base, R, D, scan, scan_lengths, nbr_ptr, nbr_idx, n_edges, [w_s2m, w_m2s, lambda_m] + lam, trunc,
+                                              "smpld_register")
+    iters = len(lam)
+    dev = scan.device
+    verts = torch.empty_like(base)
+    energy = torch.empty((B, 4), dtype=torch.float32, device=dev)
+    trace = torch.empty((B, iters, 4), dtype=torch.float32, device=dev) if want_trace else None
+    _lib.call("etch_smpld_register", B, N, V, base, R, scan, sl, nbr_ptr, nbr_idx, int(n_edges), iters, (ctypes.c_float * iters)(*lam), float(lambda_m),
+              float(w_s2m), float(w_m2s), tr, float(lr), D, verts, energy, trace, ws)
+    return verts, energy, trace
+
+
+def skin_carry(points, face, bary, faces, W, A, A_new, trans_scale, trans_scale_new):
+    """Carry points (P,3) fp64 bound to a skinned surface (face (P) int32 into faces (F,3) int32, bary (P,3) fp64) from the pose of A (nj,12)
+    to the pose of A_new: (T' T^-1 (x / scale - trans) + trans') scale' with T = sum_j w~_j A_j, w~ = the barycentric mix of W (V,nj);
+    trans_scale / trans_scale_new: (4,) fp32 = trans | scale.  |det T^R| < 1e-10 -> T = identity.  -> (P,3) fp64."""
+    _need(points, torch.float64, "points"), _need(bary, torch.float64, "bary"), _need(face, torch.int32, "face"), _need(faces, torch.int32, "faces")
+    _need(W, torch.float32, "W"), _need(A, torch.float32, "A"), _need(A_new, torch.float32, "A_new")
+    _need(trans_scale, torch.float32, "trans_scale"), _need(trans_scale_new, torch.float32, "trans_scale_new")
+    P = points.shape[0]
+    if points.dim() != 2 or points.shape[1] != 3 or tuple(bary.shape) != (P, 3) or tuple(face.shape) != (P,):
+        raise _lib.EtchHipError(f"skin_carry: points (P,3), face (P,), bary (P,3), got {tuple(points.shape)}, {tuple(face.shape)}, {tuple(bary.shape)}")
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] == 0 or W.dim() != 2:
+        raise _lib.EtchHipError(f"skin_carry: faces (F,3) with F >= 1 and W (V,nj), got {tuple(faces.shape)} and {tuple(W.shape)}")
+    V, nj = W.shape
+    if not 1 <= nj <= 55 or tuple(A.shape) != (nj, 12) or tuple(A_new.shape) != (nj, 12):
+        raise _lib.EtchHipError(f"skin_carry: A and A_new must be ({nj},12) for W {tuple(W.shape)} (nj <= 55), got {tuple(A.shape)} and {tuple(A_new.shape)}")
+    if tuple(trans_scale.shape) != (4,) or tuple(trans_scale_new.shape) != (4,):
+        raise _lib.EtchHipError("skin_carry: trans_scale and trans_scale_new must be (4,) = trans | scale")
+    out = torch.empty_like(points)
+    _lib.call("etch_skin_carry", P, faces.shape[0], V, nj, points, face, bary, faces, W, A, A_new, trans_scale, trans_scale_new, out)
+    return out
+
+
 # ------------------------------------------------------------------ tightness supervision (csrc/raycast.hip)
 def _check_mesh(verts, faces):
     """verts (V,3) fp64, faces (F,3) int32 on the device with every index in [0, V): the kernels read vertices through the face indices."""

@@ -726,6 +726,40 @@ int etch_smpl_chamfer_refine(int B, int N, int V, int nj, int nb, int n_extra, c
                              const void* const* prior, int n_gauss, int bidir, int iters, float lr, float beta1, float beta2, float eps, float* params,
                              float* verts, float* joints, float* loss_trace, float* loss_last, void* workspace, void* stream);
 
+/* ---- SMPL+D registration and re-posing (csrc/register.hip) ------------------------------------------------------------ */
+
+/* Skinning frames of params (B, 3 nj + nb + 4) = pose (global orient first) | beta | trans | scale: with r_v the rest vertex after shape and
+ * pose blend shapes and A_j the joint transforms (rest joint removed, no trans, no scale), base (B,V,3) = (sum_j W_vj A_j [r_v; 1] + trans)
+ * scale, R (B,V,9) = scale sum_j W_vj A_j^R (row-major 3 x 3), A (B,nj,12) (row-major 3 x 4).  consts: the first 7 tables of etch_smpl_lbs. */
+int etch_smpl_skin_frames(int B, int V, int nj, int nb, const void* const* consts, const float* params, float* base, float* R, float* A, void* stream);
+/* verts (B,V,3) = base + R D, D (B,V,3) the per-vertex offsets in the rest pose. */
+int etch_smpld_apply(int B, int V, const float* base, const float* R, const float* D, float* verts, void* stream);
+/* Workspace bytes of etch_smpld_energy_grad and etch_smpld_register. */
+int etch_smpld_register_workspace(int B, int N, int V, long long* bytes);
+/* One evaluation of the registration energy of every scan b (n_b = scan_len[b] or N points x, y = base + R D, a / c / d the neighbours and
+ * distances of etch_nn_bidir(scan, y)):
+ *   w_s2m / n_b sum_i d(x_i, y_a(i)) + w_m2s / V sum_v m_v d(y_v, x_c(v)) + lambda_s / n_edges sum_(u,v) |D_u - D_v|^2 + lambda_m / V sum_v |D_v|^2,
+ * m_v = 1, or with trunc >= 0, [d(y_v, x_c(v)) <= trunc^2] on the fp32 distance (trunc < 0: no mask).  The edges are given as the
+ * neighbour lists nbr_idx[nbr_ptr[v] .. nbr_ptr[v+1]) (nbr_ptr (V+1), every edge in both lists, n_edges of them; shared by the batch).
+ * Outputs: terms (B,4) in the order above, grad (B,V,3) = d energy / dD with neighbours and masks held fixed, verts (B,V,3), idx_xy (B,N),
+ * idx_yx (B,V).  Sums are fp64 in a fixed order; no floating-point atomics. */
+int etch_smpld_energy_grad(int B, int N, int V, const float* base, const float* R, const float* D, const float* scan, const int* scan_len, const int* nbr_ptr,
+                           const int* nbr_idx, int n_edges, float w_s2m, float w_m2s, float lambda_s, float lambda_m, float trunc, void* workspace, float* terms,
+                           float* grad, float* verts, int* idx_xy, int* idx_yx, void* stream);
+/* `iters` torch.optim.Adam steps (betas 0.9 / 0.999, eps 1e-8, constant lr, fp32 moments from zero) on D (B,V,3, updated in place) of the
+ * energy above; step i uses lambda_s[i] (a HOST array of iters floats, read during the call) and its gradient is taken entirely at the
+ * iterate before it.  Outputs: verts (B,V,3) and energy (B,4) of the final D (evaluated with lambda_s[iters-1]), trace (B,iters,4) = the
+ * terms at the iterate before each step, or NULL.  Everything is queued on `stream` without a host wait (capturable). */
+int etch_smpld_register(int B, int N, int V, const float* base, const float* R, const float* scan, const int* scan_len, const int* nbr_ptr, const int* nbr_idx,
+                        int n_edges, int iters, const float* lambda_s, float lambda_m, float w_s2m, float w_m2s, float trunc, float lr, float* D, float* verts,
+                        float* energy, float* trace, void* workspace, void* stream);
+/* Carry P points (fp64) bound to a skinned surface (face (P) int32 into faces (F,3), bary (P,3)) from one pose to another: w~ = sum_k
+ * bary_k W[faces[f,k]] (W (V,nj)), T = sum_j w~_j A_j, T' = sum_j w~_j A_new_j, out = (T' T^-1 (x / scale - trans) + trans') scale', with
+ * trans_scale / trans_scale_new = 4 device floats each (trans | scale).  |det T^R| < 1e-10: T is the identity.  A point whose face or
+ * vertex index is out of range comes back as NaN. */
+int etch_skin_carry(int P, int F, int V, int nj, const double* points, const int* face, const double* bary, const int* faces, const float* W, const float* A,
+                    const float* A_new, const float* trans_scale, const float* trans_scale_new, double* out, void* stream);
+
 /* ---- tightness supervision: info points and vector targets (scripts/generate_infopoints.py, GT_dataloader.py:95-122) ------------- */
 
 /* Workspace bytes of etch_ray_first_hit (R rays) / etch_closest_point_on_mesh (P points) against F faces. */
