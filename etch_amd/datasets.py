@@ -8,7 +8,8 @@ start method (a forked worker cannot use the parent's HIP context).  A body neve
 label per subdivided vertex) is computed once and cached; `precompute(batch_size)` solves many bodies per call.
 
 The scan points come from our seeded area-weighted sampler with seed + 15: trimesh.sample.sample_surface's distribution, not its points
-(as etch_amd.eval.EvalDataset documents).
+(as etch_amd.eval.EvalDataset documents).  With `view` (an etch_amd.depth.ViewSpec) an item's points are, with the spec's probability,
+what one depth camera sees of the scan; the targets come from the same code, which takes any points on the scan surface.
 """
 import os
 import pickle
@@ -23,9 +24,11 @@ from .infopoints import tightness_vectors
 class GTDataset:
     gender_dict = {0: "female", 1: "male"}                  # GT_dataloader.py:75
 
-    def __init__(self, args, device=None, laplacian="intrinsic_delaunay", verbose=True, reader="python"):
+    def __init__(self, args, device=None, laplacian="intrinsic_delaunay", verbose=True, reader="python", view=None):
         if reader not in ("python", "native"):
             raise ValueError(f"reader must be 'python' or 'native', got {reader!r}")
+        self.view = view                                      # an etch_amd.depth.ViewSpec: items seen by one random depth camera
+        self.epoch = 0
         self.reader = reader                                  # "native": etch_amd.mesh_io.read_obj for an item's two meshes, the same arrays
         self.seed = args.seed
         self.scan_dir = args.scan_dir
@@ -46,6 +49,26 @@ class GTDataset:
 
     def __len__(self):
         return len(self.id_list)
+
+    def set_epoch(self, epoch):
+        """The epoch whose views the items show (with `view`): an item's camera is a function of (seed, epoch, index) alone."""
+        self.epoch = int(epoch)
+
+    def view_camera(self, index, scan=None):
+        """The camera of item `index` in the current epoch, or None where the item keeps its full scan (always None without `view`)."""
+        if self.view is None:
+            return None
+        from .depth import bbox_mid
+        if scan is None:
+            from .inference_demo import load_obj
+            scan = load_obj(self._paths(self.id_list[index])[1])
+        return self.view.camera(self.seed, self.epoch, index, bbox_mid(scan.vertices))
+
+    def _view_points(self, index, scan, camera):
+        """num_point points of what `camera` sees of the scan, float64 in the scan's own frame (no centring, like the full samples)."""
+        from .depth import partial_view_points
+        key = self.view.draw(self.seed, self.epoch, index)[3]
+        return partial_view_points([scan], [camera], self.num_point, [key], center=False, device=self.device).points64[0].cpu().numpy()
 
     def _paths(self, i):
         return (os.path.join(self.infopoints_dir, f"{i}.npz"), os.path.join(self.scan_dir, i, f"{i}.obj"),
@@ -86,7 +109,11 @@ class GTDataset:
         ipd = np.load(ip_path)
         scan = load_obj(scan_path)
         body = load_obj(smpl_path)
-        sample_points = sample_points_from_mesh(scan, self.num_point, seed=self.seed + 15)
+        camera = self.view_camera(index, scan)
+        if camera is not None:
+            sample_points = self._view_points(index, scan, camera)
+        else:
+            sample_points = sample_points_from_mesh(scan, self.num_point, seed=self.seed + 15)
         vectors, _ = tightness_vectors(sample_points, ipd["info_points"], ipd["info_vectors"], body, device=self.device)
         dmin, lab, sv = self.field(i)
         confidences, labels = G.geodesic_targets(sample_points, vectors, dmin, lab, sv, device=self.device)

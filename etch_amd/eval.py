@@ -89,12 +89,28 @@ def _device_batches(dataset, batch_size, prefetch):
             yield [f.result() for f in queue.pop(0)]
 
 
-def _evaluate_dataset_device(args, model, dataset, batch_size, output_folder, prefetch):
+def view_cameras(view, scans):
+    """--view_azimuth: one camera per scan, orbiting the scan's own bounding-box centre.  view = {azimuth, elevation (degrees), distance, fov,
+    size (H, W)}."""
+    import math
+
+    from .depth import Camera, bbox_mid
+    return [Camera.orbit(bbox_mid(s.vertices), view["distance"], math.radians(view["azimuth"]), math.radians(view["elevation"]), view["fov"],
+                         int(view["size"][0]), int(view["size"][1])) for s in scans]
+
+
+def _evaluate_dataset_device(args, model, dataset, batch_size, output_folder, prefetch, view=None):
     from .mesh_io import sample_surface, write_obj
     recs = []
     for items in _device_batches(dataset, batch_size, prefetch):
+        scans = [it["scan"] for it in items]
         # every id under one key, as the reference gives each the sampler seed self.seed + 15 (GT_dataloader_mixed.py:201-203)
-        hitpts, _, _ = sample_surface([it["scan"] for it in items], dataset.num_point, [dataset.seed + 15], center=False, device=args.device)
+        if view is not None:
+            # the points one virtual camera sees of each scan, in the scan's own frame like the full samples: the scores stay comparable
+            from .depth import partial_view_points
+            hitpts = partial_view_points(scans, view_cameras(view, scans), dataset.num_point, [dataset.seed + 15], center=False, device=args.device).points
+        else:
+            hitpts, _, _ = sample_surface(scans, dataset.num_point, [dataset.seed + 15], center=False, device=args.device)
         gtj = [it["gt_joints"] for it in items]
         recs += evaluate_batch(args, model, hitpts, [it["gender"] for it in items], ids=[it["id"] for it in items],
                                gt_vertices=[it["gt_vertices"] for it in items], gt_joints=None if any(j is None for j in gtj) else gtj,
@@ -102,11 +118,14 @@ def _evaluate_dataset_device(args, model, dataset, batch_size, output_folder, pr
     return recs
 
 
-def evaluate_dataset(args, model, dataset, batch_size=8, output_folder=None, ingest=None, prefetch=1):
+def evaluate_dataset(args, model, dataset, batch_size=8, output_folder=None, ingest=None, prefetch=1, view=None):
     """eval.py:76-265: the whole dataset in batches through `evaluate_batch`; v2v_score.txt ends with the reference's summary block.
     Returns (records, average v2v).  ingest (default: the dataset's): "host" = items sampled by the dataset one at a time in this thread;
-    "device" = native reader on worker threads `prefetch` batches ahead (0: none), device sampler per batch, native writer."""
+    "device" = native reader on worker threads `prefetch` batches ahead (0: none), device sampler per batch, native writer.  view (ingest
+    "device" only): every scan is scored from the points one virtual camera sees of it (view_cameras), against the full ground-truth body."""
     ingest = ingest or getattr(dataset, "ingest", "host")
+    if view is not None and ingest != "device":
+        raise ValueError("a virtual view (--view_azimuth) is rendered on the device: it needs ingest='device'")
     if ingest != getattr(dataset, "ingest", "host"):
         raise ValueError(f"ingest={ingest!r} needs a dataset built with the same ingest (it has {getattr(dataset, 'ingest', 'host')!r})")
     output_folder = output_folder or args.output_folder
@@ -115,7 +134,7 @@ def evaluate_dataset(args, model, dataset, batch_size=8, output_folder=None, ing
     if os.path.exists(score):
         os.remove(score)                                   # eval.py:82-84
     if ingest == "device":
-        recs = _evaluate_dataset_device(args, model, dataset, batch_size, output_folder, prefetch)
+        recs = _evaluate_dataset_device(args, model, dataset, batch_size, output_folder, prefetch, view)
     else:
         recs = []
         for s in range(0, len(dataset), batch_size):
@@ -229,9 +248,27 @@ def build_parser():
                         help="device: native OBJ reader one batch ahead on worker threads, GPU surface sampler, native writer; host: the Python "
                              "reader and writer and the numpy sampler, one scan at a time")
     parser.add_argument("--prefetch", type=int, default=1, help="--ingest device: batches read ahead of the GPU (0: none)")
+    parser.add_argument("--view_azimuth", type=float, default=None, metavar="DEG",
+                        help="score every scan from one virtual depth camera at this azimuth around the scan's bounding-box centre (--ingest device)")
+    parser.add_argument("--view_elevation", type=float, default=0.0, metavar="DEG")
+    parser.add_argument("--view_distance", type=float, default=2.5, metavar="M")
+    parser.add_argument("--view_fov", type=float, default=45.0, metavar="DEG")
+    parser.add_argument("--view_size", type=int, nargs=2, default=(512, 512), metavar=("H", "W"))
     from .utils.prior import add_pose_prior_flags
     add_pose_prior_flags(parser)
     return parser
+
+
+def view_from_args(parser, args):
+    """--view_* -> the dict view_cameras takes, or None without --view_azimuth; a parser error for a view the device path cannot render."""
+    if args.view_azimuth is None:
+        return None
+    if args.ingest != "device":
+        parser.error("--view_azimuth renders on the device: it needs --ingest device")
+    if not -90.0 < args.view_elevation < 90.0 or not args.view_distance > 0.0 or not 0.0 < args.view_fov < 180.0 or min(args.view_size) < 1:
+        parser.error("--view_elevation must lie inside (-90, 90), --view_distance be positive, --view_fov inside (0, 180), --view_size at least 1 1")
+    return {"azimuth": args.view_azimuth, "elevation": args.view_elevation, "distance": args.view_distance, "fov": args.view_fov,
+            "size": tuple(args.view_size)}
 
 
 def main(argv=None):
@@ -239,7 +276,9 @@ def main(argv=None):
     from .inference_demo import load_model, resolve_body_model
     from .train import default_stuff
 
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    view = view_from_args(parser, args)
     if not torch.cuda.is_available():
         raise RuntimeError("etch_amd.eval needs a GPU: etch_amd has no CPU path")
     args.cuda = True
@@ -259,7 +298,7 @@ def main(argv=None):
     dataset = EvalDataset(args.scan_dir, args.smpl_dir, args.infopoints_dir, args.activated_ids_path, num_point=args.num_point, seed=args.seed,
                           ingest=args.ingest)
     print(f"Num of data: {len(dataset)}")
-    recs, avg = evaluate_dataset(args, model, dataset, batch_size=args.batch_size, prefetch=args.prefetch)
+    recs, avg = evaluate_dataset(args, model, dataset, batch_size=args.batch_size, prefetch=args.prefetch, view=view)
     print(f"average v2v: {avg} over {len(recs)} samples; outputs under {args.output_folder}")
     return recs, avg
 

@@ -169,10 +169,9 @@ def _ingest_device(args):
     return points, Mesh(scan_mesh.vertices - center, scan_mesh.faces), center
 
 
-def prepare(args):
-    """What a single-scan command does between parsing its flags and the fit: the device, the markerset, the body model, the pose prior and
-    the output folder into args; the network; the scan read, centred and sampled (--ingest).  -> model, the OBJ writer, points (N,3) float32
-    numpy, the centred mesh, the centre, the scan's name."""
+def prepare_common(args):
+    """The part of prepare() that does not touch the scan: the device, the markerset, the body model, the pose prior and the output folder
+    into args -> the network."""
     if not torch.cuda.is_available():
         raise RuntimeError("etch_amd needs an AMD GPU (gfx950); there is no CPU path")
     args.cuda = True
@@ -187,7 +186,13 @@ def prepare(args):
     from .utils.prior import pose_prior_from_args
     args.fit_pose_prior = pose_prior_from_args(args, args.device)
     os.makedirs(args.output_folder, exist_ok=True)
-    model = load_model(args)
+    return load_model(args)
+
+
+def prepare(args):
+    """What a single-scan command does between parsing its flags and the fit: prepare_common; the scan read, centred and sampled (--ingest).
+    -> model, the OBJ writer, points (N,3) float32 numpy, the centred mesh, the centre, the scan's name."""
+    model = prepare_common(args)
     export = Mesh.export
     if getattr(args, "ingest", "host") == "device":
         from .mesh_io import write_obj as export

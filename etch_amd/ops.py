@@ -1792,3 +1792,92 @@ def sample_surface(verts, faces, vert_offsets, face_offsets, keys, num_points, t
     _lib.call("etch_sample_surface", int(B), N, int(total_faces), int(max_faces), verts, faces, vert_offsets, face_offsets, keys, center, ws, p32, p64, face,
               status)
     return p32, p64, face, status
+
+
+# ------------------------------------------------------------------ single-view scans (csrc/depth_render.hip)
+def _check_cameras(cams, what):
+    _need(cams, torch.float64, "cams")
+    if cams.dim() != 2 or cams.shape[1] != 16:
+        raise _lib.EtchHipError(f"{what}: cams must be (NV,16) = fx, fy, cx, cy, R (9), t (3), got {tuple(cams.shape)}")
+    return cams.shape[0]
+
+
+def depth_large_threshold():
+    """Candidate pixels above which etch_render_depth hands a face to its large-face launch."""
+    return int(_lib.call("etch_depth_large_threshold"))
+
+
+def render_depth(verts, faces, vert_offsets, face_offsets, view_mesh, cams, height, width, max_faces, near=0.05, want_bary=False):
+    """etch_render_depth on a packed ragged batch (mesh_io.pack_meshes): verts (sum V,3) fp64, faces (sum F,3) int32 local to their mesh and
+    ALREADY VALIDATED, vert_offsets / face_offsets (B+1) int32, view_mesh (NV) int32 with every entry in [0, B), cams (NV,16) fp64; max_faces
+    is the host's copy of the largest face count.  -> depth (NV,H,W) fp64 (+inf = nothing hit), face (NV,H,W) int32 (-1), bary (NV,H,W,3) or
+    None, dropped (NV) int32, status (NV) int32 (ETCH_DEPTH_STATUS_* bits), large (NV) int32 -- all still on the device."""
+    _need(verts, torch.float64, "verts"), _need(faces, torch.int32, "faces"), _need(view_mesh, torch.int32, "view_mesh")
+    _need(vert_offsets, torch.int32, "vert_offsets"), _need(face_offsets, torch.int32, "face_offsets")
+    NV = _check_cameras(cams, "render_depth")
+    B, H, W, dev = vert_offsets.numel() - 1, int(height), int(width), verts.device
+    if B < 1 or face_offsets.numel() != B + 1 or verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise _lib.EtchHipError("render_depth: offsets must be (B+1) with B >= 1, verts (.,3) and faces (.,3)")
+    if view_mesh.shape != (NV,) or H < 1 or W < 1 or int(max_faces) < 0 or int(max_faces) > faces.shape[0]:
+        raise _lib.EtchHipError(f"render_depth: view_mesh must be ({NV},), the image at least 1 x 1 and 0 <= max_faces <= {faces.shape[0]}")
+    if not (float(near) > 0.0 and math.isfinite(float(near))):
+        raise _lib.EtchHipError(f"render_depth: near must be positive and finite, got {near}")
+    if NV * H * W >= 2 ** 31 - 256:
+        raise _lib.EtchHipError("render_depth: NV * H * W must stay below 2^31: render the views in parts")
+    b = ctypes.c_longlong(0)
+    _lib.call("etch_render_depth_workspace", int(NV), int(max_faces), ctypes.byref(b))
+    ws = torch.empty((max(int(b.value), 8),), dtype=torch.uint8, device=dev)
+    depth = torch.empty((NV, H, W), dtype=torch.float64, device=dev)
+    face = torch.empty((NV, H, W), dtype=torch.int32, device=dev)
+    bary = torch.empty((NV, H, W, 3), dtype=torch.float64, device=dev) if want_bary else None
+    dropped = torch.empty((NV,), dtype=torch.int32, device=dev)
+    status = torch.empty((NV,), dtype=torch.int32, device=dev)
+    large = torch.empty((NV,), dtype=torch.int32, device=dev)
+    if NV:
+        _lib.call("etch_render_depth", int(B), int(NV), H, W, int(max_faces), verts, faces, vert_offsets, face_offsets, view_mesh, cams, float(near), ws,
+                  depth, face, bary, dropped, status, large)
+    return depth, face, bary, dropped, status, large
+
+
+def depth_compact(depth, cams, near=0.05, far=math.inf):
+    """etch_depth_compact: depth (NV,H,W) fp64 (rendered or a caller's), cams (NV,16) fp64; a pixel is valid where near < z < far.  -> count (NV)
+    int32, offsets (NV+1) int32, index (NV*H*W) int32 and points (NV*H*W,3) fp64 whose first offsets[NV] rows are the valid pixels of all
+    views in row-major order (the rest is not written) -- all still on the device."""
+    _need(depth, torch.float64, "depth")
+    NV = _check_cameras(cams, "depth_compact")
+    if depth.dim() != 3 or depth.shape[0] != NV:
+        raise _lib.EtchHipError(f"depth_compact: depth must be ({NV},H,W), got {tuple(depth.shape)}")
+    if not (float(near) >= 0.0 and float(far) > float(near)):
+        raise _lib.EtchHipError(f"depth_compact: needs 0 <= near < far, got {near} and {far}")
+    _, H, W = depth.shape
+    if NV * H * W >= 2 ** 31 - 256:
+        raise _lib.EtchHipError("depth_compact: NV * H * W must stay below 2^31: compact the views in parts")
+    dev = depth.device
+    b = ctypes.c_longlong(0)
+    _lib.call("etch_depth_compact_workspace", int(NV), int(H), int(W), ctypes.byref(b))
+    ws = torch.empty((max(int(b.value), 8),), dtype=torch.uint8, device=dev)
+    count = torch.empty((NV,), dtype=torch.int32, device=dev)
+    offsets = torch.empty((NV + 1,), dtype=torch.int32, device=dev)
+    index = torch.empty((NV * H * W,), dtype=torch.int32, device=dev)
+    points = torch.empty((NV * H * W, 3), dtype=torch.float64, device=dev)
+    _lib.call("etch_depth_compact", int(NV), int(H), int(W), depth, cams, float(near), float(far), ws, count, offsets, index, points)
+    return count, offsets, index, points
+
+
+def depth_pick(offsets, index, points, keys, num_points, center=None):
+    """etch_depth_pick: offsets (NV+1) int32, index (>= offsets[NV]) int32 and points (same rows,3) fp64 of a packed cloud, keys (NV) int64 holding
+    the uint64 bits, center (NV,3) fp64 subtracted from the picked points or None.  -> points (NV,N,3) fp64, their fp32 rounding, pixel (NV,N) int32, status (NV) int32 (ETCH_DEPTH_STATUS_EMPTY where a view
+    has no valid pixel; its rows are zeros) -- all still on the device."""
+    _need(offsets, torch.int32, "offsets"), _need(index, torch.int32, "index"), _need(points, torch.float64, "points"), _need(keys, torch.int64, "keys")
+    NV, N, dev = keys.numel(), int(num_points), points.device
+    if offsets.shape != (NV + 1,) or points.dim() != 2 or points.shape[1] != 3 or index.shape != (points.shape[0],) or N < 0:
+        raise _lib.EtchHipError(f"depth_pick: offsets must be ({NV + 1},), points (M,3), index (M,) and num_points >= 0")
+    if center is not None and _need(center, torch.float64, "center").shape != (NV, 3):
+        raise _lib.EtchHipError(f"center must be ({NV},3)")
+    p64 = torch.zeros((NV, N, 3), dtype=torch.float64, device=dev)
+    p32 = torch.zeros((NV, N, 3), dtype=torch.float32, device=dev)
+    pixel = torch.zeros((NV, N), dtype=torch.int32, device=dev)
+    status = torch.empty((NV,), dtype=torch.int32, device=dev)
+    if NV:
+        _lib.call("etch_depth_pick", int(NV), N, offsets, index, points, keys, center, p64, p32, pixel, status)
+    return p64, p32, pixel, status

@@ -320,7 +320,22 @@ def build_parser():
     parser.add_argument("--gpus", type=int, default=1, help="devices to train on, one process each: --batch_size is split over them (DataParallel)")
     parser.add_argument("--accumulate", type=int, default=1, metavar="K", help="micro-batches per device and step: --batch_size (the global batch) is "
                         "cut into gpus * K micro-batches whose gradients are averaged")
+    parser.add_argument("--partial_views", type=float, default=0.0, metavar="P", help="probability that an item's points are what one random depth camera "
+                        "sees of the scan (etch_amd.depth.ViewSpec); the camera depends on (seed, epoch, item) only")
+    parser.add_argument("--view_elevation", type=float, nargs=2, default=(-10.0, 30.0), metavar=("LO", "HI"), help="degrees")
+    parser.add_argument("--view_distance", type=float, default=2.5, metavar="M")
+    parser.add_argument("--view_fov", type=float, default=45.0, metavar="DEG")
+    parser.add_argument("--view_size", type=int, nargs=2, default=(256, 256), metavar=("H", "W"))
     return parser
+
+
+def view_spec_from_args(args):
+    """--partial_views P and the --view_* flags -> the dataset's ViewSpec, or None for P = 0 (the dataset of a run without the flags)."""
+    if not args.partial_views:
+        return None
+    from .depth import ViewSpec
+    return ViewSpec(probability=args.partial_views, elevation_range=tuple(args.view_elevation), distance=args.view_distance, fov_deg=args.view_fov,
+                    size=tuple(args.view_size))
 
 
 def make_model(args):
@@ -374,6 +389,10 @@ def main(argv=None):
         parser.error(f"--gpus {args.gpus}: at most {P.MAX_RANKS} ranks")
     if args.reference_step and args.gpus * args.accumulate > 1:
         parser.error("--reference_step is the reference's literal single-device step: it takes --gpus 1 --accumulate 1")
+    try:
+        view = view_spec_from_args(args)
+    except ValueError as e:
+        parser.error(f"--partial_views: {e}")
     args.pred_items = [s.strip() for s in args.pred_items.split(",") if s.strip()]
     if not args.pred_items or any(s not in PRED_ITEMS for s in args.pred_items):
         raise ValueError(f"--pred_items must be a comma list out of {PRED_ITEMS}")
@@ -430,7 +449,7 @@ def main(argv=None):
         backend = torch.distributed.get_backend() if torch.distributed.is_initialized() else "none"
         say(f"======== Flat gradient path: {args.gpus * args.accumulate} contribution(s) per step, all-reduce backend {backend}, world {world} ========")
 
-    dataset = GTDataset(args, device=args.device, verbose=rank == 0)
+    dataset = GTDataset(args, device=args.device, verbose=rank == 0, view=view)
     loader_generator = torch.Generator().manual_seed(args.seed)
     args.aug_generator = torch.Generator().manual_seed(args.seed + 100)
     if flat:
@@ -457,6 +476,7 @@ def main(argv=None):
         if args.max_steps is not None and args.steps_done >= args.max_steps:
             break
         say(f"====== Epoch {epoch} start! ====== \n")
+        dataset.set_epoch(epoch)
         average_epoch_losses = train(args, model, optimizer, train_loader)
         say(f"===== Average losses of Epoch {epoch} are: " + "".join(f"{k}: {v:.05f}, " for k, v in average_epoch_losses.items()) + "======\n")
         for key in average_epoch_losses.keys():

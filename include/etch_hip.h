@@ -883,6 +883,44 @@ int etch_sample_surface(int B, int N, int total_faces, int max_faces, const doub
                         const int* face_offsets, const unsigned long long* keys, const double* center, void* workspace, float* points32,
                         double* points64, int* face, int* status, void* stream);
 
+/* ---- single-view scans: depth rasteriser, back-projection, stratified pick (csrc/depth_render.hip) --------------- */
+
+/* Bits of the per-view status words of etch_render_depth and etch_depth_pick. */
+#define ETCH_DEPTH_STATUS_VERTEX 1       /* a face of the view has a corner, or a projection of one, that is not finite */
+#define ETCH_DEPTH_STATUS_MESH 2         /* view_mesh names no mesh of the batch, or one without vertices: nothing was rendered */
+#define ETCH_DEPTH_STATUS_EMPTY 4        /* etch_depth_pick: the view has no valid pixel, nothing was picked */
+/* Workspace bytes of etch_render_depth for NV views of meshes with at most max_faces faces. */
+int etch_render_depth_workspace(int NV, int max_faces, long long* bytes);
+/* Candidate pixels above which a face is rasterised by the large-face launch. */
+int etch_depth_large_threshold(void);
+/* Depth maps of NV views of a ragged batch of B meshes, packed as etch_sample_surface takes it (verts fp64, faces int32 local to their mesh and
+ * clamped into it, vert_offsets / face_offsets (B+1) int32, max_faces >= every face count).  view_mesh (NV) int32 = the mesh each view looks
+ * at; cams (NV,16) fp64 = fx, fy, cx, cy, R (3x3 row-major), t (3), world to camera p_c = R x + t with x right, y down, z forward; pixel (r, c)
+ * has its centre at (c + 0.5, r + 0.5); near > 0.  Bit-defined, with the operation order of csrc/depth_render.hip: a face with a corner at
+ * z_c < near is dropped whole, a pixel is covered where the three edge functions are all >= 0 or all <= 0 (and it lies in the corners' box),
+ * z = 1 / sum_k ((w_k / area) / z_k); the smallest z wins, equal z -> the lowest face.  Outputs: depth (NV,H,W) fp64 (+inf = nothing hit),
+ * face (NV,H,W) int32 local to the mesh (-1), bary (NV,H,W,3) fp64 perspective-corrected (0 on a miss) or NULL, dropped (NV) int32 = faces
+ * dropped at the near plane, status (NV) int32 = ETCH_DEPTH_STATUS_* bits, n_large (NV) int32 = faces that took the large-face launch, or NULL. */
+int etch_render_depth(int B, int NV, int H, int W, int max_faces, const double* verts, const int* faces, const int* vert_offsets,
+                      const int* face_offsets, const int* view_mesh, const double* cams, double near, void* workspace, double* depth, int* face,
+                      double* bary, int* dropped, int* status, int* n_large, void* stream);
+/* Workspace bytes of etch_depth_compact. */
+int etch_depth_compact_workspace(int NV, int H, int W, long long* bytes);
+/* Back-projection of depth maps (NV,H,W) fp64, rendered or a caller's: a pixel is valid where near < z < far (far may be +inf; NaN, inf and 0
+ * are background).  Outputs: count (NV) int32, offsets (NV+1) int32, and for the valid pixels of all views, view after view in row-major order,
+ * index (their flat pixel r W + c, int32) and points (.,3) fp64 = R^T (p_c - t) with p_c = ((c + 0.5 - cx) / fx z, (r + 0.5 - cy) / fy z, z).
+ * index and points need room for offsets[NV] entries (NV H W is always enough). */
+int etch_depth_compact(int NV, int H, int W, const double* depth, const double* cams, double near, double far, void* workspace, int* count,
+                       int* offsets, int* index, double* points, void* stream);
+/* N points per view of the packed cloud, stratified in row-major order: sample j owns the rows [a_j, b_j) of its view, a_j = floor(j n / N),
+ * b_j = floor((j + 1) n / N) with n the view's count, and takes rank_j = a_j + min(w - 1, floor(u_j w)), w = b_j - a_j (rank_j = a_j where the
+ * stratum is empty, n < N); u_j is the 53-bit Philox uniform etch_sample_surface draws as u_f for sample j under keys[view].  The strata are
+ * disjoint: with n >= N no row is picked twice.  center (NV,3) fp64 is subtracted from the picked points, or NULL.  Outputs: out64 (NV,N,3)
+ * fp64, out32 its fp32 rounding, pixel (NV,N) int32, status (NV) int32 = ETCH_DEPTH_STATUS_EMPTY where n == 0 (that view's outputs are not
+ * written). */
+int etch_depth_pick(int NV, int N, const int* offsets, const int* index, const double* points, const unsigned long long* keys, const double* center,
+                    double* out64, float* out32, int* pixel, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
