@@ -243,8 +243,10 @@ __global__ void __launch_bounds__(256) inter_dfeat_kernel(int cin, int cbase, in
                 // Round 6: the 24 weights of this (match, anchor) once into registers, then every channel's 24 gradients as SIX 16-byte loads (a channel's
                 // row of dX1 is 24 consecutive floats, 96 bytes, 16-byte aligned: kk and KS are multiples of 4) -- the first form read them one float at a
                 // time with a stride of 24 between a thread's channels: 26 % of a training step (profiles/r06_train_kernel_stats.txt).  Same products,
-                // same order of the sum over k for every channel (k ascending; zero weights contribute +0 instead of being skipped: bitwise the same sum
-                // unless an accumulator is -0).
+                // same order of the sum over k for every channel (k ascending; zero weights contribute +0 instead of being skipped).
+                // A slot's 24 terms are summed from zero and the slot's sum is added to the running one -- the arithmetic of inter_dfeat_slots_kernel and its
+                // segment sum.  One fmaf chain through every slot and k (up to 64 x 24 terms) sat 4 - 6 x further from fp64 than the oracle's fp32 autograd
+                // (profiles/backward_fp64_pins.txt).
                 float wv[KS];
 #pragma unroll
                 for (int k = 0; k < KS; ++k) {
@@ -256,13 +258,13 @@ __global__ void __launch_bounds__(256) inter_dfeat_kernel(int cin, int cbase, in
 #pragma unroll
                 for (int c = 0; c < 16; ++c)
                     if (c < cper) {
-                        float s_ = acc[c];
+                        float s_ = 0.f;
 #pragma unroll
                         for (int k4 = 0; k4 < KS / 4; ++k4) {
                             const float4 d = drow[c * (KS / 4) + k4];
                             s_ = fmaf(wv[4 * k4], d.x, s_); s_ = fmaf(wv[4 * k4 + 1], d.y, s_); s_ = fmaf(wv[4 * k4 + 2], d.z, s_); s_ = fmaf(wv[4 * k4 + 3], d.w, s_);
                         }
-                        acc[c] = s_;
+                        acc[c] += s_;
                     }
             }
         }
@@ -536,7 +538,7 @@ int etch_intra_rows(long points, int C, int nt, const int* intra_idx, const floa
 int etch_colsum(long R, int C, const float* x, double* workspace, float* out, void* stream);
 int etch_colsum_fused(long R, int C, const float* x, long ldx, double* workspace, unsigned* counters, float* out, void* stream) {
     if (C <= 0) return ETCH_OK;
-    if (R < 0 || !x || !workspace || !counters || !out || ldx < C) return ETCH_EINVAL;
+    if (R < 0 || (!x && R > 0) || !workspace || !counters || !out || ldx < C) return ETCH_EINVAL;      // (no rows: an empty matrix has no address; the sums are 0)
     if ((C + 63) / 64 > ETCH_REDUCE_COUNTERS) return ldx == C ? etch_colsum(R, C, x, workspace, out, stream) : ETCH_EUNSUPPORTED;
     if (colstat_vec_ok(C, ldx, x))
         hipLaunchKernelGGL(colsum_fused_kernel<4>, dim3(colstat_chunks(R), colstat_groups<4>(C)), dim3(256), 0, (hipStream_t)stream, R, C, x, ldx, workspace, counters, out);

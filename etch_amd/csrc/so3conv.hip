@@ -604,6 +604,16 @@ __global__ void __launch_bounds__(256) intra_so3conv_kernel(int npts_total, int 
     for (int pi = 0; pi < PTS; ++pi)
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) acc[pi][mt] = (f32x4){0, 0, 0, 0};
+    // C >= 128: K = 12 C = 1536 / 3072, 384 / 768 dependent MFMA steps per output.  One fp32 chain of that length sat 5 - 8 x further from fp64 than a
+    // blocked BLAS sum (profiles/backward_fp64_pins.txt); the chains are closed after every tap (C / 4 steps) into a second accumulator.  C <= 64: as it was.
+    constexpr bool BLOCKED = C >= 128;
+    f32x4 tot[BLOCKED ? PTS : 1][BLOCKED ? MT : 1];
+    if constexpr (BLOCKED) {
+#pragma unroll
+        for (int pi = 0; pi < PTS; ++pi)
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) tot[pi][mt] = (f32x4){0, 0, 0, 0};
+    }
     for (int t = 0; t < NT; ++t) {
         const int tap = t / (C / 16), cb = (t - tap * (C / 16)) * 16;
         const int src = iidx[aa * 12 + tap];
@@ -619,6 +629,20 @@ __global__ void __launch_bounds__(256) intra_so3conv_kernel(int npts_total, int 
         acc[pi][mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt].C, bv[pi].C, acc[pi][mt], 0, 0, 0);
         I_STEP(x) I_STEP(y) I_STEP(z) I_STEP(w)
 #undef I_STEP
+        if constexpr (BLOCKED) {
+            if (cb == C - 16) {                              // the tap's last chunk
+#pragma unroll
+                for (int pi = 0; pi < PTS; ++pi)
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt) { tot[pi][mt] += acc[pi][mt]; acc[pi][mt] = (f32x4){0, 0, 0, 0}; }
+            }
+        }
+    }
+    if constexpr (BLOCKED) {
+#pragma unroll
+        for (int pi = 0; pi < PTS; ++pi)
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) acc[pi][mt] = tot[pi][mt];
     }
     // InstanceNorm statistics of the output, fused (stat_part != NULL; the host guarantees pts_per_batch % PTS == 0, so a workgroup's
     // points belong to one sample): per lane the sum / sum of squares of its 4 channels per tile over the workgroup's points

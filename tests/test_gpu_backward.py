@@ -17,6 +17,9 @@ def scan(seed, n):
 
 @pytest.mark.parametrize("stride,lazy,nn,cin,cout,chunk", [(2, False, 16, 16, 32, 64), (1, True, 32, 32, 32, 100), (2, False, 32, 64, 64, 256)])
 def test_inter_conv_gradients_vs_autograd_of_the_unfused_form(stride, lazy, nn, cin, cout, chunk):
+    """`chunk` target points per pass of the backward: A.CHUNK_BYTES is lowered for the two backward passes so that the parameter decides (with
+    the default bound every case here would run as one chunk) -- 150 points in chunks of 64, 300 in chunks of 100, 150 in one chunk of 256.
+    tests/test_gpu_backward_fp64.py holds the chunked and un-chunked forms of both feature-gradient kernels to fp64 per channel."""
     import etch_amd.vgtk_so3conv as V
     from etch_amd import autograd as A
     from etch_amd.utils.weights import load_seeded
@@ -43,7 +46,11 @@ def test_inter_conv_gradients_vs_autograd_of_the_unfused_form(stride, lazy, nn, 
     bg = conv.basic_conv.bias.detach().clone().requires_grad_()
     y = A.inter_so3conv(f_cl, Wg, bg, xyz.cuda(), new_xyz.cuda(), ball.cuda(), rk, sigma, chunk=chunk)
     assert rel_err(y.detach().cpu().permute(0, 3, 1, 2).numpy(), y_ref.detach().numpy()) < 1e-4
-    (y * G.float().permute(0, 2, 3, 1).contiguous().cuda()).sum().backward()
+    old_bytes, A.CHUNK_BYTES = A.CHUNK_BYTES, 1.0
+    try:
+        (y * G.float().permute(0, 2, 3, 1).contiguous().cuda()).sum().backward()
+    finally:
+        A.CHUNK_BYTES = old_bytes
     assert rel_err(Wg.grad.cpu().numpy(), W.grad.numpy()) < 1e-4
     assert rel_err(bg.grad.cpu().numpy(), bias.grad.numpy()) < 1e-4
     assert rel_err(f_cl.grad.cpu().permute(0, 3, 1, 2).numpy(), feats.grad.numpy()) < 1e-4
@@ -52,7 +59,11 @@ def test_inter_conv_gradients_vs_autograd_of_the_unfused_form(stride, lazy, nn, 
     W2 = Wg.detach().clone().requires_grad_()
     b2 = bg.detach().clone().requires_grad_()
     y2 = A.inter_so3conv(f2, W2, b2, xyz.cuda(), new_xyz.cuda(), ball.cuda(), rk, sigma, chunk=chunk)
-    (y2 * G.float().permute(0, 2, 3, 1).contiguous().cuda()).sum().backward()
+    old_bytes, A.CHUNK_BYTES = A.CHUNK_BYTES, 1.0
+    try:
+        (y2 * G.float().permute(0, 2, 3, 1).contiguous().cuda()).sum().backward()
+    finally:
+        A.CHUNK_BYTES = old_bytes
     assert torch.equal(W2.grad, Wg.grad) and torch.equal(f2.grad, f_cl.grad) and torch.equal(b2.grad, bg.grad)
 
 
