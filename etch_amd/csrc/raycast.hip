@@ -11,6 +11,7 @@
 // candidate per (face chunk, query) and a final kernel reduces the chunks in ascending order, so the result does not depend on the launch shape.
 #include "common.h"
 #include "etch_hip.h"
+#include "closest_tri.h"
 
 #define RC_BLOCK 256                 // queries per workgroup, one per lane
 #define RC_TILE 256                  // faces (points) staged in LDS per step
@@ -143,70 +144,12 @@ __global__ void __launch_bounds__(RC_BLOCK) rc_ray_final_kernel(int R, int nchun
 }
 
 // ---------------------------------------------------------------------------------------------- point / triangle
-// Ericson 5.1.5 ClosestPtPointTriangle, operation order (dot(x, y) = (x.x*y.x + x.y*y.y) + x.z*y.z; vector ops componentwise):
-//   ab = b - a, ac = c - a, ap = p - a;  d1 = dot(ab, ap), d2 = dot(ac, ap)
-//   region A   d1 <= 0 && d2 <= 0                                   -> a                    bary (1, 0, 0)
-//   bp = p - b;  d3 = dot(ab, bp), d4 = dot(ac, bp)
-//   region B   d3 >= 0 && d4 <= d3                                  -> b                    bary (0, 1, 0)
-//   vc = d1*d4 - d3*d2
-//   edge AB    vc <= 0 && d1 >= 0 && d3 <= 0    v = d1 / (d1 - d3)  -> a + v*ab             bary (1 - v, v, 0)
-//   cp = p - c;  d5 = dot(ab, cp), d6 = dot(ac, cp)
-//   region C   d6 >= 0 && d5 <= d6                                  -> c                    bary (0, 0, 1)
-//   vb = d5*d2 - d1*d6
-//   edge AC    vb <= 0 && d2 >= 0 && d6 <= 0    w = d2 / (d2 - d6)  -> a + w*ac             bary (1 - w, 0, w)
-//   va = d3*d6 - d5*d4
-//   edge BC    va <= 0 && (d4 - d3) >= 0 && (d5 - d6) >= 0
-//              w = (d4 - d3) / ((d4 - d3) + (d5 - d6))              -> b + w*(c - b)        bary (0, 1 - w, w)
-//   interior   denom = 1 / ((va + vb) + vc), v = vb*denom, w = vc*denom
-//                                                                   -> (a + ab*v) + ac*w    bary ((1 - v) - w, v, w)
-//   d2 = dot(p - q, p - q).  A degenerate triangle can give NaN: never below a running minimum, so never chosen.
-struct RcClosest {
-    double q[3], b[3], d2;
-};
+// Ericson 5.1.5 ClosestPtPointTriangle: the region test and its operation order are stated in closest_tri.h (shared with the fp32 surface fit);
+// this TU uses the fp64 instantiation.
+typedef RcClosestT<double> RcClosest;
 
 __device__ __forceinline__ RcClosest rc_closest(const double* p, const double* a, const double* b, const double* c) {
-    RcClosest o;
-    const double ab[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
-    const double ac[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
-    const double ap[3] = {p[0] - a[0], p[1] - a[1], p[2] - a[2]};
-    const double d1 = rc_dot(ab[0], ab[1], ab[2], ap[0], ap[1], ap[2]), d2 = rc_dot(ac[0], ac[1], ac[2], ap[0], ap[1], ap[2]);
-    const double bp[3] = {p[0] - b[0], p[1] - b[1], p[2] - b[2]};
-    const double d3 = rc_dot(ab[0], ab[1], ab[2], bp[0], bp[1], bp[2]), d4 = rc_dot(ac[0], ac[1], ac[2], bp[0], bp[1], bp[2]);
-    const double vc = d1 * d4 - d3 * d2;
-    const double cp[3] = {p[0] - c[0], p[1] - c[1], p[2] - c[2]};
-    const double d5 = rc_dot(ab[0], ab[1], ab[2], cp[0], cp[1], cp[2]), d6 = rc_dot(ac[0], ac[1], ac[2], cp[0], cp[1], cp[2]);
-    const double vb = d5 * d2 - d1 * d6;
-    const double va = d3 * d6 - d5 * d4;
-    if (d1 <= 0.0 && d2 <= 0.0) {
-        for (int i = 0; i < 3; ++i) o.q[i] = a[i];
-        o.b[0] = 1.0; o.b[1] = 0.0; o.b[2] = 0.0;
-    } else if (d3 >= 0.0 && d4 <= d3) {
-        for (int i = 0; i < 3; ++i) o.q[i] = b[i];
-        o.b[0] = 0.0; o.b[1] = 1.0; o.b[2] = 0.0;
-    } else if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {
-        const double v = d1 / (d1 - d3);
-        for (int i = 0; i < 3; ++i) o.q[i] = a[i] + v * ab[i];
-        o.b[0] = 1.0 - v; o.b[1] = v; o.b[2] = 0.0;
-    } else if (d6 >= 0.0 && d5 <= d6) {
-        for (int i = 0; i < 3; ++i) o.q[i] = c[i];
-        o.b[0] = 0.0; o.b[1] = 0.0; o.b[2] = 1.0;
-    } else if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {
-        const double w = d2 / (d2 - d6);
-        for (int i = 0; i < 3; ++i) o.q[i] = a[i] + w * ac[i];
-        o.b[0] = 1.0 - w; o.b[1] = 0.0; o.b[2] = w;
-    } else if (va <= 0.0 && (d4 - d3) >= 0.0 && (d5 - d6) >= 0.0) {
-        const double w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
-        for (int i = 0; i < 3; ++i) o.q[i] = b[i] + w * (c[i] - b[i]);
-        o.b[0] = 0.0; o.b[1] = 1.0 - w; o.b[2] = w;
-    } else {
-        const double denom = 1.0 / ((va + vb) + vc);
-        const double v = vb * denom, w = vc * denom;
-        for (int i = 0; i < 3; ++i) o.q[i] = (a[i] + ab[i] * v) + ac[i] * w;
-        o.b[0] = (1.0 - v) - w; o.b[1] = v; o.b[2] = w;
-    }
-    const double e[3] = {p[0] - o.q[0], p[1] - o.q[1], p[2] - o.q[2]};
-    o.d2 = rc_dot(e[0], e[1], e[2], e[0], e[1], e[2]);
-    return o;
+    return rc_closest_t<double>(p, a, b, c);
 }
 
 // One lane per point, a workgroup per (256 points, 2048-face chunk); each tile's (a, b, c) in LDS.  Output per (chunk, point): d2, face.

@@ -190,6 +190,38 @@ def fit_smpl_by_gender(args, pred_inner_points, pred_part_labels, pred_confidenc
     return meshes, markers, valid, info
 
 
+def surface_refine_fits(args, settings, inner, labels, confidences, gender_list, **fit_kwargs):
+    """--surface_refine: the marker fit per gender, then fit_surface on the same scans' inner points with the aggregated markers and the marker
+    fit as init (models/surface_refine.py) -> fit_smpl's return layout for the whole batch, the meshes and parameters being the refined ones
+    (joints in the scan's frame: (joints + trans) * scale, as inference_demo writes them)."""
+    from .models.chamfer_refine import init_from_fit
+    from .models.fit_SMPL import _resolve_body_model
+    from .models.surface_refine import fit_surface
+    B = inner.shape[0]
+    meshes, info = [None] * B, None
+    markers = torch.zeros((B, len(args.markerset), 3), dtype=torch.float32, device=inner.device)
+    valid = torch.zeros((B, len(args.markerset)), dtype=torch.bool, device=inner.device)
+    for g in sorted(set(gender_list)):
+        sel = [i for i, x in enumerate(gender_list) if x == g]
+        idx = torch.tensor(sel, device=inner.device)
+        pts = inner[idx].contiguous()
+        _, mk, vm, _, dev = fit_smpl(args, pts, labels[idx].contiguous(), confidences[idx].contiguous(), g, return_trace=True, **fit_kwargs)
+        verts, prm = fit_surface(_resolve_body_model(args, g), pts, init_from_fit(dev), markers=mk, valid=vm, marker_vids=list(args.markerset.values()),
+                                 **settings)
+        pose, beta, trans = (prm[k].cpu().numpy() for k in ("pose", "beta", "trans"))
+        joints = (prm["joints"].cpu().numpy() + trans[:, None]) * prm["scale"].cpu().numpy()[:, None]
+        inf = [pose[:, 3:].reshape(len(sel), -1, 3), beta, pose[:, :3], trans, joints]
+        if info is None:
+            info = [np.zeros((B,) + a.shape[1:], a.dtype) for a in inf]
+        for k, i in enumerate(sel):
+            meshes[i] = Mesh(verts[k], dev["faces"])
+            for a, src in zip(info, inf):
+                a[i] = src[k]
+        markers[idx] = mk
+        valid[idx] = vm
+    return meshes, markers, valid, info
+
+
 def evaluate_batch(args, model, hitpts, gender_list, ids=None, gt_vertices=None, gt_joints=None, output_folder=None, export=Mesh.export):
     """One eval.py iteration (eval.py:87-99,181-256) on a batch (B,K,3) already on the device.
     Returns a list of per-sample dicts {id, v2v, mpjpe, valid_full} (metrics only when ground truth is given).  export(mesh, path) writes the
@@ -201,8 +233,13 @@ def evaluate_batch(args, model, hitpts, gender_list, ids=None, gt_vertices=None,
         labels = ops.argmax_rows(results["part_labels"])
         inner = ops.inner_points(hitpts.contiguous(), results["direction"], results["magnitude"], float(args.scale_magnitude))
         pp = getattr(args, "fit_pose_prior", None)              # --pose_prior (main)
-        meshes, markers, valid, info = fit_smpl_by_gender(args, inner, labels, results["confidences"], gender_list,
-                                                          **({} if pp is None else {"pose_prior": pp}))
+        from .inference_demo import surface_refine_settings
+        surface = surface_refine_settings(args)
+        fit_kwargs = {} if pp is None else {"pose_prior": pp}
+        if surface is None:
+            meshes, markers, valid, info = fit_smpl_by_gender(args, inner, labels, results["confidences"], gender_list, **fit_kwargs)
+        else:
+            meshes, markers, valid, info = surface_refine_fits(args, surface, inner, labels, results["confidences"], gender_list, **fit_kwargs)
     out = []
     vsum = valid.sum(1).tolist()
     for j in range(B):
@@ -254,6 +291,8 @@ def build_parser():
     parser.add_argument("--view_distance", type=float, default=2.5, metavar="M")
     parser.add_argument("--view_fov", type=float, default=45.0, metavar="DEG")
     parser.add_argument("--view_size", type=int, nargs=2, default=(512, 512), metavar=("H", "W"))
+    from .inference_demo import add_surface_refine_flags
+    add_surface_refine_flags(parser)
     from .utils.prior import add_pose_prior_flags
     add_pose_prior_flags(parser)
     return parser
@@ -279,6 +318,8 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     view = view_from_args(parser, args)
+    from .inference_demo import surface_refine_settings
+    surface_refine_settings(args, parser)
     if not torch.cuda.is_available():
         raise RuntimeError("etch_amd.eval needs a GPU: etch_amd has no CPU path")
     args.cuda = True

@@ -63,14 +63,17 @@ def sample_points_from_mesh(mesh, num_points=5000, seed=0):
     return t[:, 0] + r[:, :1] * (t[:, 1] - t[:, 0]) + r[:, 1:] * (t[:, 2] - t[:, 0])
 
 
-def predict_smpl_batch(args, model, points_tensor, gender="neutral", **fit_kwargs):
-    """inference_demo.py:41-66 for a batch (B,N,3) already on the device: stage 1 -> labels / inner points -> stage 2."""
+def predict_smpl_batch(args, model, points_tensor, gender="neutral", inner_out=None, **fit_kwargs):
+    """inference_demo.py:41-66 for a batch (B,N,3) already on the device: stage 1 -> labels / inner points -> stage 2.
+    inner_out: a dict that receives stage 1's inner points (B,N,3) under "inner" (the dense surface refinement fits the body to them)."""
     if getattr(args, "fit_pose_prior", None) is not None:       # --pose_prior (main): the marker fit under the mixture prior
         fit_kwargs.setdefault("pose_prior", args.fit_pose_prior)
     with torch.no_grad():
         results, _ = model(points_tensor, pred_items=["confidence", "direction", "magnitude"], direction_mode="standard_vector")
         labels = ops.argmax_rows(results["part_labels"])
         inner = ops.inner_points(points_tensor.contiguous(), results["direction"], results["magnitude"], float(args.scale_magnitude))
+        if inner_out is not None:
+            inner_out["inner"] = inner
         return fit_smpl(args, inner, labels, results["confidences"], gender, **fit_kwargs)
 
 
@@ -108,31 +111,74 @@ def add_flags(parser):
     return parser
 
 
-def parse_args(argv=None):
+def add_surface_refine_flags(parser):
+    """--surface_refine and its settings (this command and etch_amd.eval).  Absent unless given, like --ingest: surface_refine_settings reads them."""
+    parser.add_argument("--surface_refine", action="store_true", default=argparse.SUPPRESS,
+                        help="after the marker fit, fit the body SURFACE to all of stage 1's inner points (models/surface_refine.py:fit_surface; the "
+                             "aggregated markers stay in the loss).  With --synthetic_body the stand-in body is SyntheticSurfaceSMPL, whose faces are a surface")
+    parser.add_argument("--surface_iters", type=int, default=argparse.SUPPRESS, help="Adam iterations of --surface_refine (200)")
+    parser.add_argument("--surface_trunc", type=float, default=argparse.SUPPRESS,
+                        help="inner points farther than this from the body (metres) are left out of an iteration's dense term (0.05; negative: none are)")
+    parser.add_argument("--surface_w", type=float, default=argparse.SUPPRESS, help="weight of the dense term of --surface_refine (1e2)")
+
+
+def surface_refine_settings(args, parser=None):
+    """None without --surface_refine, else fit_surface's keyword arguments from --surface_iters / --surface_trunc / --surface_w.  Both
+    refinements at once, or a setting without the flag, is an argument error."""
+    given = [k for k in ("surface_iters", "surface_trunc", "surface_w") if hasattr(args, k)]
+    err = parser.error if parser is not None else argparse.ArgumentParser().error
+    if not getattr(args, "surface_refine", False):
+        if given:
+            err("--" + given[0] + " needs --surface_refine")
+        return None
+    if getattr(args, "chamfer_refine", "none") != "none":
+        err("--surface_refine and --chamfer_refine are two refinements of the same fit: give one")
+    if getattr(args, "surface_iters", 200) < 1:
+        err("--surface_iters must be at least 1")
+    return dict(iterations=getattr(args, "surface_iters", 200), trunc=getattr(args, "surface_trunc", 0.05), w_dense=getattr(args, "surface_w", 1e2))
+
+
+def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("--scan_path", type=str, required=True, help="Path to input scan OBJ file")
-    return add_flags(parser).parse_args(argv)
+    add_surface_refine_flags(parser)      # this command and etch_amd.eval only: track, depth and animate share add_flags, not the refinement
+    return add_flags(parser)
+
+
+def parse_args(argv=None):
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    surface_refine_settings(args, parser)
+    return args
 
 
 def fit_and_refine(args, model, points, centered_mesh):
     """The marker fit of points (N,3), then with --chamfer_refine fit_cham against the centred scan's vertices (the script's `vertices_scan`).
     -> the fit's meshes, the body model, the refined vertices (None without --chamfer_refine) and the parameters as fit_cham's dict (without
-    --chamfer_refine its `init`, the marker fit's)."""
+    --chamfer_refine its `init`, the marker fit's).  With --surface_refine the refinement is fit_surface on stage 1's inner points instead."""
     from .models.chamfer_refine import fit_cham, init_from_fit
     from .models.fit_SMPL import _resolve_body_model
 
     points_tensor = torch.from_numpy(points).float().unsqueeze(0).to(args.device)
-    meshes, _, _, _, dev = predict_smpl_batch(args, model, points_tensor, args.gender, return_trace=True)
+    surface = surface_refine_settings(args)
+    if surface is not None:
+        inner = {}
+        meshes, _, _, _, dev = predict_smpl_batch(args, model, points_tensor, args.gender, return_trace=True, inner_out=inner)
+    else:
+        meshes, _, _, _, dev = predict_smpl_batch(args, model, points_tensor, args.gender, return_trace=True)
     bm = _resolve_body_model(args, args.gender)
     verts, prm = None, init_from_fit(dev)
-    if args.chamfer_refine != "none":
+    if surface is not None:
+        from .models.surface_refine import fit_surface
+        verts, prm = fit_surface(bm, inner["inner"], prm, markers=dev["markers"], valid=dev["valid"], marker_vids=list(args.markerset.values()), **surface)
+    elif args.chamfer_refine != "none":
         scan = torch.from_numpy(np.asarray(centered_mesh.vertices, np.float32)).unsqueeze(0).to(args.device)
         verts, prm = fit_cham(bm, scan, prm, prior=None, bidir=args.chamfer_refine, iterations=args.refine_iters)
     return meshes, bm, verts, prm
 
 
 def _refine_and_save(args, model, points, centered_mesh, original_center, scan_name, export=Mesh.export):
-    """--chamfer_refine: the OBJ is the refined mesh moved back by the scan centre; the .npz holds the refined parameters, `scale`, and the
+    """--chamfer_refine / --surface_refine: the OBJ is the refined mesh moved back by the scan centre; the .npz holds the refined parameters, `scale`, and the
     joints in the centred scan's frame ((joints + trans) * scale, the frame the LM joints of an unrefined run are written in)."""
     meshes, _, verts, prm = fit_and_refine(args, model, points, centered_mesh)
     final = Mesh(verts[0] + original_center, meshes[0].faces)
@@ -149,8 +195,9 @@ def _refine_and_save(args, model, points, centered_mesh, original_center, scan_n
 def resolve_body_model(args):
     """--synthetic_body / --body_model -> args.body_model (a BodyModel, or None = the reference's gender paths)."""
     if args.synthetic_body:
-        from .utils.body_model import SyntheticSMPL
-        args.body_model = SyntheticSMPL(7)
+        from .utils.body_model import SyntheticSMPL, SyntheticSurfaceSMPL
+        # SyntheticSMPL's faces are a strip for OBJ export, no surface: the surface refinement gets the stand-in that has one
+        args.body_model = SyntheticSurfaceSMPL(7) if getattr(args, "surface_refine", False) else SyntheticSMPL(7)
     elif args.body_model:
         from .utils.body_model import load_smpl_pkl, load_smplx
         # an SMPL-X model file (SMPLX_*.npz / .pkl) selects the 55-joint, 20-coefficient fit; anything else is read as an SMPL pickle
@@ -208,7 +255,7 @@ def prepare(args):
 def main(argv=None):
     args = parse_args(argv)
     model, export, points, centered_mesh, original_center, scan_name = prepare(args)
-    if args.chamfer_refine != "none":
+    if args.chamfer_refine != "none" or getattr(args, "surface_refine", False):
         _refine_and_save(args, model, points, centered_mesh, original_center, scan_name, export)
         print(f"Predicted SMPL mesh and smpl info saved under {args.output_folder}")
         return

@@ -1379,6 +1379,119 @@ def smpl_chamfer_refine(consts, scan, params, V, scan_lengths=None, prior=None, 
     return verts, joints, loss, tr
 
 
+# ------------------------------------------------------------------ dense surface refinement (csrc/surface_fit.hip)
+def _byte_workspace(name, device, *dims):
+    n = ctypes.c_longlong(0)
+    _lib.call(name, *dims, ctypes.byref(n))
+    return torch.empty((max(int(n.value), 8),), dtype=torch.uint8, device=device)
+
+
+def _mesh_args(points, verts, faces, what):
+    _need(points, torch.float32, "points"), _need(verts, torch.float32, "verts"), _need(faces, torch.int32, "faces")
+    if points.dim() != 3 or verts.dim() != 3 or points.shape[2] != 3 or verts.shape[2] != 3 or verts.shape[0] != points.shape[0] or faces.dim() != 2 \
+            or faces.shape[1] != 3:
+        raise _lib.EtchHipError(f"{what}: points (B,N,3), verts (B,V,3), faces (F,3), got {tuple(points.shape)}, {tuple(verts.shape)}, {tuple(faces.shape)}")
+    return points.shape[0], points.shape[1], verts.shape[1], faces.shape[0]
+
+
+def point_mesh_closest(points, verts, faces, lengths=None):
+    """Exact closest point of mesh b (verts (B,V,3) fp32, faces (F,3) int32 shared by the batch) to points (B,N,3) fp32 (lengths (B,) for
+    ragged point sets) -> face (B,N) int32, bary (B,N,3), d2 (B,N): Ericson's region test in fp32, every pair; the smallest d2 wins, equal
+    d2 -> the lowest face, NaN never wins; padding -> face -1, bary 0, d2 0."""
+    B, N, V, F = _mesh_args(points, verts, faces, "point_mesh_closest")
+    nl = _lengths(lengths, B, N, points.device, "lengths")
+    ws = _byte_workspace("etch_point_mesh_closest_workspace", points.device, B, N)
+    face = torch.empty((B, N), dtype=torch.int32, device=points.device)
+    bary = torch.empty((B, N, 3), dtype=torch.float32, device=points.device)
+    d2 = torch.empty((B, N), dtype=torch.float32, device=points.device)
+    _lib.call("etch_point_mesh_closest", B, N, V, F, points, nl, verts, faces, ws, face, bary, d2)
+    return face, bary, d2
+
+
+def _marker_args(markers, B, V, device):
+    """markers = None or (vids (M,) int, positions (B,M,3), valid (B,M)) -> (M, vids int32, positions fp32, valid fp32) device tensors."""
+    if markers is None:
+        return 0, None, None, None
+    vids, pos, valid = markers
+    vids = torch.as_tensor(vids).to(device=device, dtype=torch.int32).contiguous()
+    M = int(vids.numel())
+    pos = _need(torch.as_tensor(pos).to(device=device, dtype=torch.float32).contiguous(), torch.float32, "markers")
+    valid = torch.as_tensor(valid).to(device=device, dtype=torch.float32).contiguous()
+    if vids.dim() != 1 or tuple(pos.shape) != (B, M, 3) or tuple(valid.shape) != (B, M):
+        raise _lib.EtchHipError(f"markers: vids (M,), positions ({B},M,3), valid ({B},M)")
+    if M and (int(vids.min()) < 0 or int(vids.max()) >= V):
+        raise _lib.EtchHipError(f"marker vertex ids must lie in [0, {V})")
+    return M, vids, pos, valid
+
+
+def point_mesh_energy_grad(points, verts, faces, face, bary, d2, weights=None, trunc=-1.0, lengths=None, coef=None, w_dense=1.0, normalize=True,
+                           markers=None, w_marker=1.0, want_verts=True, want_points=False):
+    """The dense term on the correspondences of point_mesh_closest (held fixed): terms (B,2) fp64 = {sum w m d2, sum w m} with m = [d2 <=
+    trunc^2] (trunc < 0: no mask), g (B,V,3) = d/dverts of coef_b w_dense S1 / S0 (normalize) or coef_b w_dense S1, plus the marker term's
+    gradient for markers = (vids, positions, valid); gp (B,N,3) = the dense term's gradient w.r.t. the points.  -> (terms, g or None, gp or None)."""
+    B, N, V, F = _mesh_args(points, verts, faces, "point_mesh_energy_grad")
+    if tuple(face.shape) != (B, N) or tuple(bary.shape) != (B, N, 3) or tuple(d2.shape) != (B, N):
+        raise _lib.EtchHipError(f"point_mesh_energy_grad: face ({B},{N}), bary ({B},{N},3), d2 ({B},{N})")
+    _need(face, torch.int32, "face"), _need(bary, torch.float32, "bary"), _need(d2, torch.float32, "d2")
+    if weights is not None:
+        weights = _need(weights.to(torch.float32).contiguous(), torch.float32, "weights")
+        if tuple(weights.shape) != (B, N):
+            raise _lib.EtchHipError(f"weights must be ({B},{N})")
+    if coef is not None:
+        coef = _need(coef.to(torch.float32).contiguous(), torch.float32, "coef")
+        if tuple(coef.shape) != (B,):
+            raise _lib.EtchHipError(f"coef must be ({B},)")
+    nl = _lengths(lengths, B, N, points.device, "lengths")
+    M, vids, pos, valid = _marker_args(markers, B, V, points.device)
+    ws = _byte_workspace("etch_point_mesh_energy_grad_workspace", points.device, B, V)
+    terms = torch.zeros((B, 2), dtype=torch.float64, device=points.device)
+    g = torch.empty_like(verts) if want_verts else None
+    gp = torch.empty_like(points) if want_points else None
+    _lib.call("etch_point_mesh_energy_grad", B, N, V, F, points, nl, verts, faces, face, bary, d2, weights, float(trunc), coef, float(w_dense), int(bool(normalize)),
+              M, vids, pos, valid, float(w_marker), ws, terms, g, gp)
+    return terms, g, gp
+
+
+def smpl_surface_refine(consts, faces, points, params, lengths=None, weights=None, markers=None, prior=None, iters=200, lr=2e-2, beta1=0.9, beta2=0.999,
+                        eps=1e-8, w_dense=1e2, w_marker=1.0, w_beta=1e-2, w_prior=1e-7, trunc=0.05, optimize_scale=False, nj=24, nb=10, n_extra=21,
+                        want_trace=False):
+    """The dense surface refinement on the device: params (B, 3 nj + nb + 4) is updated IN PLACE.  faces (F,3) int32; points (B,N,3) (lengths,
+    weights (B,N) optional); markers = None or (vids (M,), positions (B,M,3), valid (B,M)); prior as smpl_chamfer_refine.  -> verts (B,V,3),
+    joints (B, nj + n_extra, 3) (without trans / scale), loss of the last forward (B,), loss trace (B, iters, 4) or None."""
+    _need(points, torch.float32, "points"), _need(params, torch.float32, "params"), _need(faces, torch.int32, "faces")
+    _check_body(consts, nj, nb, n_extra)
+    V = int(consts[0].shape[0])
+    if points.dim() != 3 or points.shape[2] != 3 or tuple(params.shape) != (points.shape[0], 3 * nj + nb + 4) or faces.dim() != 2 or faces.shape[1] != 3:
+        raise _lib.EtchHipError(f"points must be (B,N,3), params (B, {3 * nj + nb + 4}), faces (F,3)")
+    B, N, _ = points.shape
+    F = int(faces.shape[0])
+    if F and (int(faces.min()) < 0 or int(faces.max()) >= V):
+        raise _lib.EtchHipError(f"face vertex ids must lie in [0, {V})")
+    nl = _lengths(lengths, B, N, points.device, "lengths")
+    if weights is not None:
+        weights = _need(weights.to(torch.float32).contiguous(), torch.float32, "weights")
+        if tuple(weights.shape) != (B, N):
+            raise _lib.EtchHipError(f"weights must be ({B},{N})")
+    M, vids, pos, valid = _marker_args(markers, B, V, points.device)
+    arr = (ctypes.c_void_p * 8)(*[t.data_ptr() for t in consts])
+    G, parr = 0, None
+    if prior is not None:
+        means, prec, w = (_need(t, torch.float32, n) for t, n in zip(prior, ("means", "precisions", "nll_weights")))
+        G = int(w.shape[0])
+        if tuple(w.shape) != (G,) or tuple(means.shape) != (G, 69) or tuple(prec.shape) != (G, 69, 69):
+            raise _lib.EtchHipError("prior: means (G,69), precisions (G,69,69), nll_weights (G,)")
+        parr = (ctypes.c_void_p * 3)(means.data_ptr(), prec.data_ptr(), w.data_ptr())
+    ws = _byte_workspace("etch_smpl_surface_refine_workspace", points.device, B, N, V, int(nj), int(nb), int(n_extra))
+    verts = torch.empty((B, V, 3), dtype=torch.float32, device=points.device)
+    joints = torch.empty((B, nj + n_extra, 3), dtype=torch.float32, device=points.device)
+    loss = torch.empty((B,), dtype=torch.float32, device=points.device)
+    tr = torch.empty((B, iters, 4), dtype=torch.float32, device=points.device) if want_trace else None
+    _lib.call("etch_smpl_surface_refine", B, N, V, F, int(nj), int(nb), int(n_extra), arr, faces, points, nl, weights, M, vids, pos, valid, parr, G, int(iters),
+              float(lr), float(beta1), float(beta2), float(eps), float(w_dense), float(w_marker), float(w_beta), float(w_prior), float(trunc),
+              int(bool(optimize_scale)), params, verts, joints, tr, loss, ws)
+    return verts, joints, loss, tr
+
+
 # ------------------------------------------------------------------ SMPL+D registration and re-posing (csrc/register.hip)
 def smpl_skin_frames(consts, params, nj=24, nb=10):
     """params (B, 3 nj + nb + 4) = pose (global orient first) | beta | trans | scale -> base (B,V,3), R (B,V,9), A (B,nj,12) with

@@ -46,10 +46,11 @@ class BodyModel:
         return len(self.parents)
 
 
-def _synthetic(seed, V, NB, parents, extra_vids, shape_scale=0.01, pose_scale=0.001):
+def _synthetic(seed, V, NB, parents, extra_vids, shape_scale=0.01, pose_scale=0.001, v_template=None, faces=None):
+    """v_template / faces: a given rest surface (SyntheticSurfaceSMPL) in place of the random vertices and their strip."""
     rng = np.random.default_rng(seed)
     J = len(parents)
-    v_t = rng.standard_normal((V, 3)) * np.array([0.15, 0.45, 0.10])
+    v_t = rng.standard_normal((V, 3)) * np.array([0.15, 0.45, 0.10]) if v_template is None else np.asarray(v_template, np.float64)
     # a crude skeleton: joint centres = random vertices; weights = softmax over the 4 nearest joints
     cent = v_t[rng.choice(V, J, replace=False)]
     d2 = ((v_t[:, None] - cent[None]) ** 2).sum(-1)
@@ -63,8 +64,9 @@ def _synthetic(seed, V, NB, parents, extra_vids, shape_scale=0.01, pose_scale=0.
         Jreg[j, np.argsort(d2[:, j])[:50]] = 1.0 / 50
     S = rng.standard_normal((V, 3, NB)) * shape_scale
     P = rng.standard_normal((9 * (J - 1), V * 3)) * pose_scale
-    faces = np.stack([np.arange(V - 2), np.arange(1, V - 1), np.arange(2, V)], 1)[: 2 * V - 4 - (V - 2)]  # a strip, only for OBJ export
-    faces = np.concatenate([faces, faces[:, ::-1]])[:2 * V - 4]
+    if faces is None:
+        faces = np.stack([np.arange(V - 2), np.arange(1, V - 1), np.arange(2, V)], 1)[: 2 * V - 4 - (V - 2)]  # a strip, only for OBJ export
+        faces = np.concatenate([faces, faces[:, ::-1]])[:2 * V - 4]
     return BodyModel(v_t, S, P, Jreg, W, parents, faces, extra_vids)
 
 
@@ -72,6 +74,37 @@ def SyntheticSMPL(seed=7, V=6890, NB=10, shape_scale=0.01, pose_scale=0.001):
     """shape_scale / pose_scale: standard deviation of the shape / pose blend-shape entries (real SMPL: ~3e-2 / ~1e-2 m; the defaults
     are the gentler values every round-1/2 fixture was generated with)."""
     return _synthetic(seed, V, NB, SMPL_PARENTS, SMPL_EXTRA_JOINT_VIDS, shape_scale, pose_scale)
+
+
+def uv_ellipsoid(rings, segs, semi_axes=(0.15, 0.45, 0.10)):
+    """A closed UV grid on an ellipsoid with its poles on the y axis: vertex 0 = the top pole, then `rings` rings of `segs` vertices, then the
+    bottom pole -> vertices (rings segs + 2, 3), faces (2 rings segs, 3) wound outwards (a fan at each pole, two triangles per grid quad)."""
+    if rings < 1 or segs < 3:
+        raise ValueError("uv_ellipsoid needs rings >= 1 and segs >= 3")
+    a, b, c = semi_axes
+    th = np.pi * np.arange(1, rings + 1) / (rings + 1)
+    ph = 2 * np.pi * np.arange(segs) / segs
+    ring = np.stack([a * np.sin(th)[:, None] * np.cos(ph)[None], b * np.cos(th)[:, None] * np.ones(segs)[None],
+                     c * np.sin(th)[:, None] * np.sin(ph)[None]], -1).reshape(-1, 3)
+    verts = np.concatenate([[[0.0, b, 0.0]], ring, [[0.0, -b, 0.0]]])
+    idx = lambda r, s: 1 + (r - 1) * segs + s % segs
+    last = rings * segs + 1
+    faces = [(0, idx(1, s + 1), idx(1, s)) for s in range(segs)]
+    for r in range(1, rings):
+        for s in range(segs):
+            faces.append((idx(r, s), idx(r, s + 1), idx(r + 1, s + 1)))
+            faces.append((idx(r, s), idx(r + 1, s + 1), idx(r + 1, s)))
+    faces += [(last, idx(rings, s), idx(rings, s + 1)) for s in range(segs)]
+    return verts, np.asarray(faces, np.int32)
+
+
+def SyntheticSurfaceSMPL(seed=7, rings=82, segs=84, NB=10, shape_scale=0.01, pose_scale=0.001):
+    """SyntheticSMPL's recipe on a real surface: the rest vertices are a UV grid on the ellipsoid with semi-axes (0.15, 0.45, 0.10) and the
+    faces are the grid's triangulation, a closed manifold (SyntheticSMPL's faces are a strip over random vertices, kept for OBJ export only).
+    rings x segs = 82 x 84 gives SMPL's 6 890 vertices (13 776 faces).  For the dense surface refinement (models/surface_refine.py)."""
+    v_t, faces = uv_ellipsoid(rings, segs)
+    V = len(v_t)
+    return _synthetic(seed, V, NB, SMPL_PARENTS, SMPL_EXTRA_JOINT_VIDS % V, shape_scale, pose_scale, v_template=v_t, faces=faces)
 
 
 def SyntheticSMPLX(seed=7, V=10475, NB=20):

@@ -726,6 +726,47 @@ int etch_smpl_chamfer_refine(int B, int N, int V, int nj, int nb, int n_extra, c
                              const void* const* prior, int n_gauss, int bidir, int iters, float lr, float beta1, float beta2, float eps, float* params,
                              float* verts, float* joints, float* loss_trace, float* loss_last, void* workspace, void* stream);
 
+/* ---- dense surface refinement: the body surface against all predicted inner points (csrc/surface_fit.hip) ------------- */
+
+/* Workspace bytes of etch_point_mesh_closest. */
+int etch_point_mesh_closest_workspace(int B, int N, long long* bytes);
+/* Exact closest point of mesh b (verts (B,V,3) fp32, faces (F,3) int32 shared by the batch) to each point of points (B,N,3) fp32; n_len (B)
+ * int32 or NULL: points at or past a scan's length are padding.  Ericson's region test in fp32 with the operation order of
+ * csrc/closest_tri.h, every (point, face) pair, nothing approximate.  Outputs: face (B,N) int32, bary (B,N,3), d2 (B,N) =
+ * ((ex*ex)+(ey*ey))+(ez*ez) of e = p - q.  The smallest d2 wins, equal d2 -> the lowest face, a NaN d2 (degenerate face) never wins and
+ * neither does a face with a vertex index outside [0, V).  Padding rows (and a point no face could be chosen for): face -1, bary 0, d2 0. */
+int etch_point_mesh_closest(int B, int N, int V, int F, const float* points, const int* n_len, const float* verts, const int* faces, void* workspace, int* face,
+                            float* bary, float* d2, void* stream);
+/* Workspace bytes of etch_point_mesh_energy_grad. */
+int etch_point_mesh_energy_grad_workspace(int B, int V, long long* bytes);
+/* With the correspondences of etch_point_mesh_closest held fixed, m_i = [d2_i <= trunc^2] on the fp32 value (trunc < 0: no mask) and
+ * w_i = weights (B,N) or NULL (1): terms (B,2) fp64 = {S1 = sum_i w_i m_i d2_i, S0 = sum_i w_i m_i}, fixed-order sums; g (B,V,3) or NULL =
+ * d/dverts of  coef_b w_dense S1 / S0 (normalize 1; S0 = 0: the term is 0) or coef_b w_dense S1 (normalize 0)
+ *            + w_marker mean over the valid markers' coordinates of (v_vid(m) - t_m)^2   (M > 0: marker_vids (M) int32, markers (B,M,3),
+ *              marker_valid (B,M) fp32, > 0 = valid; no valid marker: the term is 0),
+ * coef (B) or NULL (1); gp (B,N,3) or NULL = the dense term's gradient w.r.t. the points.  The per-vertex sums are 2^-40 fixed-point
+ * differences added with 64-bit integer atomics: exact, independent of order; no floating-point atomics. */
+int etch_point_mesh_energy_grad(int B, int N, int V, int F, const float* points, const int* n_len, const float* verts, const int* faces, const int* face,
+                                const float* bary, const float* d2, const float* weights, float trunc, const float* coef, float w_dense, int normalize, int M,
+                                const int* marker_vids, const float* markers, const float* marker_valid, float w_marker, void* workspace, double* terms,
+                                float* g, float* gp, void* stream);
+/* Workspace bytes of etch_smpl_surface_refine; (nj, nb) in {(24, 10), (55, 20)}. */
+int etch_smpl_surface_refine_workspace(int B, int N, int V, int nj, int nb, int n_extra, long long* bytes);
+/* `iters` torch.optim.Adam steps (beta1, beta2, eps; fit_cham's schedule: step i at lr for i = 0 and lr (iters - i + 1) / iters after) on
+ * params (B, P = 3 nj + nb + 4, updated in place) of the per-scan loss
+ *   w_dense S1 / S0 + w_marker mean_valid (v_vid(m) - t_m)^2 + w_beta mean(beta^2) + w_prior min_k [0.5 d^T P_k d - log c_k] (pose[3:]),
+ * S1, S0 as in etch_point_mesh_energy_grad for the surface of verts = (LBS(pose, beta) + trans) * scale and points (B,N,3) (n_len, weights
+ * or NULL); the correspondences are recomputed at every iteration and held fixed inside the gradient.  optimize_scale 0: scale keeps its
+ * initial value.  prior: NULL (n_gauss 0) or {means (G,69), precisions (G,69,69), nll_weights (G)}, SMPL (nj 24) only.  Outputs: verts
+ * (B,V,3) and joints (B, nj + n_extra, 3; without trans and scale) of the final params, loss_last (B) = the loss of the last forward,
+ * loss_trace (B, iters, 4) = the four weighted terms at the iterate before each step, or NULL.  Everything is queued on `stream` without a
+ * host wait (capturable).  consts as etch_smpl_lbs. */
+int etch_smpl_surface_refine(int B, int N, int V, int F, int nj, int nb, int n_extra, const void* const* consts, const int* faces, const float* points,
+                             const int* n_len, const float* weights, int M, const int* marker_vids, const float* markers, const float* marker_valid,
+                             const void* const* prior, int n_gauss, int iters, float lr, float beta1, float beta2, float eps, float w_dense, float w_marker,
+                             float w_beta, float w_prior, float trunc, int optimize_scale, float* params, float* verts, float* joints, float* loss_trace,
+                             float* loss_last, void* workspace, void* stream);
+
 /* ---- SMPL+D registration and re-posing (csrc/register.hip) ------------------------------------------------------------ */
 
 /* Skinning frames of params (B, 3 nj + nb + 4) = pose (global orient first) | beta | trans | scale: with r_v the rest vertex after shape and
