@@ -114,7 +114,7 @@ def _evaluate_dataset_device(args, model, dataset, batch_size, output_folder, pr
         gtj = [it["gt_joints"] for it in items]
         recs += evaluate_batch(args, model, hitpts, [it["gender"] for it in items], ids=[it["id"] for it in items],
                                gt_vertices=[it["gt_vertices"] for it in items], gt_joints=None if any(j is None for j in gtj) else gtj,
-                               output_folder=output_folder, export=write_obj)
+                               output_folder=output_folder, export=write_obj, scans=scans)
     return recs
 
 
@@ -133,6 +133,14 @@ def evaluate_dataset(args, model, dataset, batch_size=8, output_folder=None, ing
     score = os.path.join(output_folder, "v2v_score.txt")
     if os.path.exists(score):
         os.remove(score)                                   # eval.py:82-84
+    from .inference_demo import surface_contain_settings
+    if surface_contain_settings(args) is not None:
+        if ingest != "device":
+            raise ValueError("--surface_contain needs the scans' meshes: host-ingest items carry none, use ingest='device'")
+        if view is not None:
+            raise ValueError("a single view is half a shell and has no inside: --surface_contain cannot be combined with a virtual view")
+        if os.path.exists(os.path.join(output_folder, "containment.txt")):
+            os.remove(os.path.join(output_folder, "containment.txt"))
     if ingest == "device":
         recs = _evaluate_dataset_device(args, model, dataset, batch_size, output_folder, prefetch, view)
     else:
@@ -190,10 +198,12 @@ def fit_smpl_by_gender(args, pred_inner_points, pred_part_labels, pred_confidenc
     return meshes, markers, valid, info
 
 
-def surface_refine_fits(args, settings, inner, labels, confidences, gender_list, **fit_kwargs):
+def surface_refine_fits(args, settings, inner, labels, confidences, gender_list, scans=None, contain=None, contain_out=None, **fit_kwargs):
     """--surface_refine: the marker fit per gender, then fit_surface on the same scans' inner points with the aggregated markers and the marker
     fit as init (models/surface_refine.py) -> fit_smpl's return layout for the whole batch, the meshes and parameters being the refined ones
-    (joints in the scan's frame: (joints + trans) * scale, as inference_demo writes them)."""
+    (joints in the scan's frame: (joints + trans) * scale, as inference_demo writes them).  contain (--surface_contain: fit_surface's
+    containment arguments) with scans = the batch's scan meshes in the frame of the points: the term joins the loss, and contain_out (a list
+    of B slots) receives per scan (metrics of the marker fit, metrics of the refined body) from containment.containment_metrics."""
     from .models.chamfer_refine import init_from_fit
     from .models.fit_SMPL import _resolve_body_model
     from .models.surface_refine import fit_surface
@@ -205,9 +215,18 @@ def surface_refine_fits(args, settings, inner, labels, confidences, gender_list,
         sel = [i for i, x in enumerate(gender_list) if x == g]
         idx = torch.tensor(sel, device=inner.device)
         pts = inner[idx].contiguous()
-        _, mk, vm, _, dev = fit_smpl(args, pts, labels[idx].contiguous(), confidences[idx].contiguous(), g, return_trace=True, **fit_kwargs)
+        m0, mk, vm, _, dev = fit_smpl(args, pts, labels[idx].contiguous(), confidences[idx].contiguous(), g, return_trace=True, **fit_kwargs)
+        extra = {}
+        if contain is not None:
+            from .containment import containment_metrics, pack_scans
+            packed = pack_scans([scans[i] for i in sel], inner.device)
+            before = containment_metrics(packed, np.stack([np.asarray(m.vertices, np.float32) for m in m0]))
+            extra = dict(scan=packed, **contain)
         verts, prm = fit_surface(_resolve_body_model(args, g), pts, init_from_fit(dev), markers=mk, valid=vm, marker_vids=list(args.markerset.values()),
-                                 **settings)
+                                 **settings, **extra)
+        if contain is not None and contain_out is not None:
+            for i, mb, ma in zip(sel, before, containment_metrics(packed, verts)):
+                contain_out[i] = (mb, ma)
         pose, beta, trans = (prm[k].cpu().numpy() for k in ("pose", "beta", "trans"))
         joints = (prm["joints"].cpu().numpy() + trans[:, None]) * prm["scale"].cpu().numpy()[:, None]
         inf = [pose[:, 3:].reshape(len(sel), -1, 3), beta, pose[:, :3], trans, joints]
@@ -222,10 +241,12 @@ def surface_refine_fits(args, settings, inner, labels, confidences, gender_list,
     return meshes, markers, valid, info
 
 
-def evaluate_batch(args, model, hitpts, gender_list, ids=None, gt_vertices=None, gt_joints=None, output_folder=None, export=Mesh.export):
+def evaluate_batch(args, model, hitpts, gender_list, ids=None, gt_vertices=None, gt_joints=None, output_folder=None, export=Mesh.export, scans=None):
     """One eval.py iteration (eval.py:87-99,181-256) on a batch (B,K,3) already on the device.
     Returns a list of per-sample dicts {id, v2v, mpjpe, valid_full} (metrics only when ground truth is given).  export(mesh, path) writes the
-    predicted bodies (default Mesh.export)."""
+    predicted bodies (default Mesh.export).  With --surface_contain, scans = the batch's scan meshes (in the frame of hitpts): each record
+    gains outside_share, protrusion_rms_mm, protrusion_max_mm of the refined body and the same three with the suffix _before for the
+    marker fit, and containment.txt beside v2v_score.txt a line per sample."""
     B = hitpts.shape[0]
     ids = list(ids) if ids is not None else [str(i) for i in range(B)]
     with torch.no_grad():
@@ -233,13 +254,18 @@ def evaluate_batch(args, model, hitpts, gender_list, ids=None, gt_vertices=None,
         labels = ops.argmax_rows(results["part_labels"])
         inner = ops.inner_points(hitpts.contiguous(), results["direction"], results["magnitude"], float(args.scale_magnitude))
         pp = getattr(args, "fit_pose_prior", None)              # --pose_prior (main)
-        from .inference_demo import surface_refine_settings
+        from .inference_demo import format_containment, surface_contain_settings, surface_refine_settings
         surface = surface_refine_settings(args)
+        contain = surface_contain_settings(args)
+        if contain is not None and scans is None:
+            raise ValueError("--surface_contain needs the scans' meshes (evaluate_batch's scans)")
+        contained = [None] * B
         fit_kwargs = {} if pp is None else {"pose_prior": pp}
         if surface is None:
             meshes, markers, valid, info = fit_smpl_by_gender(args, inner, labels, results["confidences"], gender_list, **fit_kwargs)
         else:
-            meshes, markers, valid, info = surface_refine_fits(args, surface, inner, labels, results["confidences"], gender_list, **fit_kwargs)
+            meshes, markers, valid, info = surface_refine_fits(args, surface, inner, labels, results["confidences"], gender_list, scans=scans,
+                                                               contain=contain, contain_out=contained, **fit_kwargs)
     out = []
     vsum = valid.sum(1).tolist()
     for j in range(B):
@@ -248,6 +274,12 @@ def evaluate_batch(args, model, hitpts, gender_list, ids=None, gt_vertices=None,
             rec["v2v"] = v2v(gt_vertices[j], meshes[j].vertices)
         if gt_joints is not None:
             rec["mpjpe"] = mpjpe(gt_joints[j], info[4][j])
+        if contained[j] is not None:
+            rec.update(contained[j][1])
+            rec.update({k + "_before": v for k, v in contained[j][0].items()})
+            if output_folder is not None:
+                with open(os.path.join(output_folder, "containment.txt"), "a") as f:
+                    f.write(f"{ids[j]}: {format_containment(contained[j][1])} (marker fit: {format_containment(contained[j][0])})\n")
         if output_folder is not None:
             d = os.path.join(output_folder, f"{ids[j]}")
             os.makedirs(d, exist_ok=True)
@@ -310,6 +342,18 @@ def view_from_args(parser, args):
             "size": tuple(args.view_size)}
 
 
+def contain_from_args(parser, args, view):
+    """--surface_contain's argument errors: inference_demo's, and what this command adds -- it needs the scans' meshes, which only --ingest
+    device items carry, and a closed surface, which a single view is not (half a shell: its winding number is ~0.5 everywhere behind it)."""
+    from .inference_demo import surface_contain_settings
+    contain = surface_contain_settings(args, parser)
+    if contain is not None and args.ingest != "device":
+        parser.error("--surface_contain needs the scans' meshes: host-ingest items carry none, use --ingest device")
+    if contain is not None and view is not None:
+        parser.error("--surface_contain and --view_azimuth: a single view is half a shell and has no inside")
+    return contain
+
+
 def main(argv=None):
     """eval.py:270-315.  Returns (records, average v2v)."""
     from .inference_demo import load_model, resolve_body_model
@@ -320,6 +364,7 @@ def main(argv=None):
     view = view_from_args(parser, args)
     from .inference_demo import surface_refine_settings
     surface_refine_settings(args, parser)
+    contain_from_args(parser, args, view)
     if not torch.cuda.is_available():
         raise RuntimeError("etch_amd.eval needs a GPU: etch_amd has no CPU path")
     args.cuda = True

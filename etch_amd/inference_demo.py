@@ -120,6 +120,12 @@ def add_surface_refine_flags(parser):
     parser.add_argument("--surface_trunc", type=float, default=argparse.SUPPRESS,
                         help="inner points farther than this from the body (metres) are left out of an iteration's dense term (0.05; negative: none are)")
     parser.add_argument("--surface_w", type=float, default=argparse.SUPPRESS, help="weight of the dense term of --surface_refine (1e2)")
+    parser.add_argument("--surface_contain", action="store_true", default=argparse.SUPPRESS,
+                        help="with --surface_refine: keep the body inside the scan's mesh (etch_amd/containment.py: vertices whose generalised winding "
+                             "number says they are outside are pulled back to the scan's surface) and print how much of it lies outside before and after")
+    parser.add_argument("--contain_w", type=float, default=argparse.SUPPRESS, help="weight of the containment term of --surface_contain (1e2)")
+    parser.add_argument("--contain_every", type=int, default=argparse.SUPPRESS,
+                        help="iterations between two recomputations of which vertices are outside and where they are pulled to (10)")
 
 
 def surface_refine_settings(args, parser=None):
@@ -138,6 +144,28 @@ def surface_refine_settings(args, parser=None):
     return dict(iterations=getattr(args, "surface_iters", 200), trunc=getattr(args, "surface_trunc", 0.05), w_dense=getattr(args, "surface_w", 1e2))
 
 
+def surface_contain_settings(args, parser=None):
+    """None without --surface_contain, else fit_surface's containment keyword arguments from --contain_w / --contain_every.  The flag without
+    --surface_refine, or a setting without the flag, is an argument error."""
+    given = [k for k in ("contain_w", "contain_every") if hasattr(args, k)]
+    err = parser.error if parser is not None else argparse.ArgumentParser().error
+    if not getattr(args, "surface_contain", False):
+        if given:
+            err("--" + given[0] + " needs --surface_contain")
+        return None
+    if not getattr(args, "surface_refine", False):
+        err("--surface_contain is a term of the surface refinement: it needs --surface_refine")
+    if getattr(args, "contain_every", 10) < 1:
+        err("--contain_every must be at least 1")
+    if not getattr(args, "contain_w", 1e2) >= 0:
+        err("--contain_w must not be negative")
+    return dict(w_contain=getattr(args, "contain_w", 1e2), contain_every=getattr(args, "contain_every", 10))
+
+
+def format_containment(m):
+    return f"outside_share {m['outside_share']:.4f} protrusion_rms_mm {m['protrusion_rms_mm']:.3f} protrusion_max_mm {m['protrusion_max_mm']:.3f}"
+
+
 def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("--scan_path", type=str, required=True, help="Path to input scan OBJ file")
@@ -149,6 +177,7 @@ def parse_args(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     surface_refine_settings(args, parser)
+    surface_contain_settings(args, parser)
     return args
 
 
@@ -170,7 +199,17 @@ def fit_and_refine(args, model, points, centered_mesh):
     verts, prm = None, init_from_fit(dev)
     if surface is not None:
         from .models.surface_refine import fit_surface
+        contain = surface_contain_settings(args)
+        if contain is not None:
+            # the centred mesh the command ingested (either --ingest mode) is the frame of the points and so of the fit
+            from .containment import containment_metrics, pack_scans
+            scans = pack_scans([centered_mesh], args.device)
+            before = containment_metrics(scans, np.asarray(meshes[0].vertices, np.float32)[None])[0]
+            surface = dict(surface, scan=scans, **contain)
         verts, prm = fit_surface(bm, inner["inner"], prm, markers=dev["markers"], valid=dev["valid"], marker_vids=list(args.markerset.values()), **surface)
+        if contain is not None:
+            print("containment before the refinement: " + format_containment(before))
+            print("containment after the refinement:  " + format_containment(containment_metrics(scans, verts)[0]))
     elif args.chamfer_refine != "none":
         scan = torch.from_numpy(np.asarray(centered_mesh.vertices, np.float32)).unsqueeze(0).to(args.device)
         verts, prm = fit_cham(bm, scan, prm, prior=None, bidir=args.chamfer_refine, iterations=args.refine_iters)

@@ -64,7 +64,8 @@ def point_mesh_face_distance(verts, faces, points, lengths=None, weights=None, t
 
 
 def fit_surface(body_model, inner_points, init, markers=None, valid=None, marker_vids=None, weights=None, lengths=None, prior=None, iterations=200,
-                lr=2e-2, w_dense=1e2, w_marker=1.0, w_beta=1e-2, w_prior=1e-7, trunc=0.05, optimize_scale=False, want_trace=False):
+                lr=2e-2, w_dense=1e2, w_marker=1.0, w_beta=1e-2, w_prior=1e-7, trunc=0.05, optimize_scale=False, want_trace=False, scan=None,
+                w_contain=1e2, contain_every=10):
     """Refine a fitted body so that its surface passes through the inner points.  inner_points (B,N,3) (GPU tensor or array; lengths (B,) for
     ragged scans, weights (B,N) >= 0 optional), init = fit_cham's dict {pose (B,3J), beta (B,NB), trans (B,3), scale (B,1)}
     (chamfer_refine.init_from_fit), markers (B,M,3) with valid (B,M) and marker_vids (M,): the aggregated markers of stage 2, optional;
@@ -73,9 +74,16 @@ def fit_surface(body_model, inner_points, init, markers=None, valid=None, marker
     d2_i the squared distance to the body surface, m_i = [d2_i <= trunc^2] (trunc None or < 0: no mask); correspondences are recomputed at every
     iteration.  scale keeps its initial value unless optimize_scale.  Every scan follows the trajectory it would follow alone.
     Returns (vertices (B,V,3) numpy, params) with params of fit_cham's shape: {loss, loss_per_scan, pose, beta, trans, scale, joints, verts},
-    tensors on the GPU; with want_trace also params["loss_trace"] (B, iterations, 4): the dense, marker, beta and prior terms."""
+    tensors on the GPU; with want_trace also params["loss_trace"] (B, iterations, 4): the dense, marker, beta and prior terms.
+    scan: the scans the bodies lie under, in the frame of the inner points -- a list of B Mesh or containment.pack_scans' tuple.
+    The loss gains w_contain (sum_v o_v |v - c_v|^2) / V over the body's vertices, o_v = the vertex is outside its scan (|winding number| <
+    0.5), c_v its closest point on the scan, both recomputed every contain_every iterations and held in between.  w_contain = 1e2 is w_dense's
+    value (both terms are mean squared metres): a default, not a tuned optimum.  params gains "outside_share" (B,) float64, the share of the
+    final vertices outside, and the trace a fifth column.  scan=None is the refinement without the term, through the entry point it always used."""
     if iterations < 1:
         raise ValueError("iterations must be >= 1")
+    if scan is not None and contain_every < 1:
+        raise ValueError("contain_every must be >= 1")
     dev = torch.device("cuda", torch.cuda.current_device()) if not torch.is_tensor(inner_points) or not inner_points.is_cuda else inner_points.device
     pts = torch.as_tensor(inner_points).to(device=dev, dtype=torch.float32).contiguous()
     if pts.dim() == 2:
@@ -99,11 +107,19 @@ def fit_surface(body_model, inner_points, init, markers=None, valid=None, marker
     if str(dev) not in faces:
         faces[str(dev)] = _faces_tensor(body_model.faces, dev)
     pr = _prior_tensors(prior, nj, dev)
-    verts, joints, loss, tr = ops.smpl_surface_refine(db.lbs_consts, faces[str(dev)], pts, params, nl, weights, mk, pr, iterations, lr, w_dense=w_dense,
-                                                      w_marker=w_marker, w_beta=w_beta, w_prior=w_prior, trunc=-1.0 if trunc is None else trunc,
-                                                      optimize_scale=optimize_scale, nj=nj, nb=nb, n_extra=db.n_extra, want_trace=want_trace)
+    kw = dict(w_dense=w_dense, w_marker=w_marker, w_beta=w_beta, w_prior=w_prior, trunc=-1.0 if trunc is None else trunc, optimize_scale=optimize_scale,
+              nj=nj, nb=nb, n_extra=db.n_extra, want_trace=want_trace)
+    if scan is None:
+        verts, joints, loss, tr = ops.smpl_surface_refine(db.lbs_consts, faces[str(dev)], pts, params, nl, weights, mk, pr, iterations, lr, **kw)
+    else:
+        from ..containment import _scans, containment_metrics
+        scans = _scans(scan, dev)
+        verts, joints, loss, tr = ops.smpl_surface_refine_contain(db.lbs_consts, faces[str(dev)], pts, params, scans, nl, weights, mk, pr, iterations, lr,
+                                                                  w_contain=w_contain, contain_every=contain_every, **kw)
     out = dict(loss=loss.sum(), loss_per_scan=loss, pose=params[:, :3 * nj], beta=params[:, 3 * nj:3 * nj + nb],
                trans=params[:, 3 * nj + nb:3 * nj + nb + 3], scale=params[:, 3 * nj + nb + 3:], joints=joints, verts=verts)
     if want_trace:
         out["loss_trace"] = tr
+    if scan is not None:
+        out["outside_share"] = torch.tensor([m["outside_share"] for m in containment_metrics(scans, verts)], dtype=torch.float64)
     return verts.cpu().numpy(), out

@@ -1492,6 +1492,125 @@ def smpl_surface_refine(consts, faces, points, params, lengths=None, weights=Non
     return verts, joints, loss, tr
 
 
+# ------------------------------------------------------------------ containment (csrc/containment.hip)
+def _ragged_mesh_args(mesh, B, what):
+    """mesh = (verts (sum V,3) fp32, faces (sum F,3) int32, vert_offsets (B+1) int32, face_offsets (B+1) int32, max_faces): the packed batch of
+    mesh_io.pack_meshes on the device (containment.pack_scans) -> the four tensors and max_faces, shapes and dtypes checked.  The offsets stay
+    on the device: max_faces is the caller's (a host integer known when the batch was packed)."""
+    if len(mesh) != 5:
+        raise _lib.EtchHipError(f"{what}: the scan meshes are (verts, faces, vert_offsets, face_offsets, max_faces)")
+    verts, faces, voff, foff, max_faces = mesh
+    _need(verts, torch.float32, "scan verts"), _need(faces, torch.int32, "scan faces"), _need(voff, torch.int32, "vert_offsets")
+    _need(foff, torch.int32, "face_offsets")
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or tuple(voff.shape) != (B + 1,) or tuple(foff.shape) != (B + 1,):
+        raise _lib.EtchHipError(f"{what}: scan verts (sum V,3), faces (sum F,3), vert_offsets and face_offsets ({B + 1},), got {tuple(verts.shape)}, "
+                                f"{tuple(faces.shape)}, {tuple(voff.shape)}, {tuple(foff.shape)}")
+    if int(max_faces) < 0 or int(max_faces) > faces.shape[0]:
+        raise _lib.EtchHipError(f"{what}: max_faces must lie in [0, {faces.shape[0]}], got {max_faces}")
+    return verts, faces, voff, foff, int(max_faces)
+
+
+def _queries(points, what):
+    _need(points, torch.float32, what)
+    if points.dim() != 3 or points.shape[2] != 3:
+        raise _lib.EtchHipError(f"{what} must be (B,Q,3), got {tuple(points.shape)}")
+    return points.shape[0], points.shape[1]
+
+
+def mesh_winding_number(mesh, queries, lengths=None):
+    """Generalised winding number of scan b (mesh: the packed batch, see _ragged_mesh_args) at queries (B,Q,3) fp32 (lengths (B,) for ragged
+    query sets; padding gets 0) -> w (B,Q) fp32: 1 inside a closed outward-oriented surface, 0 outside, -1 inside a reversed one.  Every
+    (query, face) pair, van Oosterom-Strackee in fp32, fixed-order sums: bitwise reproducible, scan b alone = scan b in a batch."""
+    B, Q = _queries(queries, "queries")
+    verts, faces, voff, foff, mf = _ragged_mesh_args(mesh, B, "mesh_winding_number")
+    ql = _lengths(lengths, B, Q, queries.device, "lengths")
+    ws = _byte_workspace("etch_mesh_winding_number_workspace", queries.device, B, Q, mf)
+    w = torch.empty((B, Q), dtype=torch.float32, device=queries.device)
+    _lib.call("etch_mesh_winding_number", B, Q, mf, verts, faces, voff, foff, queries, ql, ws, w)
+    return w
+
+
+def ragged_mesh_closest(mesh, points, lengths=None):
+    """point_mesh_closest for the packed batch of scan meshes (per-scan faces) -> face (B,N) int32 local to the scan, bary (B,N,3), d2 (B,N);
+    the same region test, tie rule (lowest face), NaN rule and padding rule (face -1, bary 0, d2 0)."""
+    B, N = _queries(points, "points")
+    verts, faces, voff, foff, mf = _ragged_mesh_args(mesh, B, "ragged_mesh_closest")
+    nl = _lengths(lengths, B, N, points.device, "lengths")
+    ws = _byte_workspace("etch_ragged_mesh_closest_workspace", points.device, B, N)
+    face = torch.empty((B, N), dtype=torch.int32, device=points.device)
+    bary = torch.empty((B, N, 3), dtype=torch.float32, device=points.device)
+    d2 = torch.empty((B, N), dtype=torch.float32, device=points.device)
+    _lib.call("etch_ragged_mesh_closest", B, N, mf, verts, faces, voff, foff, points, nl, ws, face, bary, d2)
+    return face, bary, d2
+
+
+def containment_energy_grad(body_verts, mesh, w, face, bary, d2, coef=None, w_contain=1.0, g=None):
+    """The containment term of body_verts (B,V,3) against the scans: o_v = [|w_v| < 0.5] (NaN and face -1 are not outside), c_v the closest
+    point of (face, bary) -> terms (B,2) fp64 = {sum_v o_v d2_v, sum_v o_v} and g (B,V,3) (given: updated IN PLACE; None: zeros first) with
+    coef_b w_contain (2 / V) o_v (v - c_v) added.  -> (terms, g)."""
+    B, V = _queries(body_verts, "body_verts")
+    verts, faces, voff, foff, _ = _ragged_mesh_args(mesh, B, "containment_energy_grad")
+    if tuple(w.shape) != (B, V) or tuple(face.shape) != (B, V) or tuple(bary.shape) != (B, V, 3) or tuple(d2.shape) != (B, V):
+        raise _lib.EtchHipError(f"containment_energy_grad: w ({B},{V}), face ({B},{V}), bary ({B},{V},3), d2 ({B},{V})")
+    _need(w, torch.float32, "w"), _need(face, torch.int32, "face"), _need(bary, torch.float32, "bary"), _need(d2, torch.float32, "d2")
+    if coef is not None:
+        coef = _need(coef.to(torch.float32).contiguous(), torch.float32, "coef")
+        if tuple(coef.shape) != (B,):
+            raise _lib.EtchHipError(f"coef must be ({B},)")
+    if g is None:
+        g = torch.zeros_like(body_verts)
+    elif tuple(g.shape) != (B, V, 3):
+        raise _lib.EtchHipError(f"g must be ({B},{V},3)")
+    _need(g, torch.float32, "g")
+    ws = _byte_workspace("etch_containment_energy_grad_workspace", body_verts.device, B, V)
+    terms = torch.zeros((B, 2), dtype=torch.float64, device=body_verts.device)
+    _lib.call("etch_containment_energy_grad", B, V, body_verts, verts, faces, voff, foff, w, face, bary, d2, coef, float(w_contain), ws, terms, g)
+    return terms, g
+
+
+def smpl_surface_refine_contain(consts, faces, points, params, scan, lengths=None, weights=None, markers=None, prior=None, iters=200, lr=2e-2, beta1=0.9,
+                                beta2=0.999, eps=1e-8, w_dense=1e2, w_marker=1.0, w_beta=1e-2, w_prior=1e-7, trunc=0.05, optimize_scale=False,
+                                w_contain=1e2, contain_every=10, nj=24, nb=10, n_extra=21, want_trace=False):
+    """smpl_surface_refine with the containment term against scan = the packed batch of scan meshes in the body's frame (_ragged_mesh_args):
+    + w_contain (sum_v o_v |v - c_v|^2) / V, o_v and c_v recomputed at iterations 0, K, 2K, ... (K = contain_every) and held in between.
+    params is updated IN PLACE.  -> verts, joints, loss of the last forward (B,), loss trace (B, iters, 5) or None."""
+    _need(points, torch.float32, "points"), _need(params, torch.float32, "params"), _need(faces, torch.int32, "faces")
+    _check_body(consts, nj, nb, n_extra)
+    V = int(consts[0].shape[0])
+    if points.dim() != 3 or points.shape[2] != 3 or tuple(params.shape) != (points.shape[0], 3 * nj + nb + 4) or faces.dim() != 2 or faces.shape[1] != 3:
+        raise _lib.EtchHipError(f"points must be (B,N,3), params (B, {3 * nj + nb + 4}), faces (F,3)")
+    B, N, _ = points.shape
+    F = int(faces.shape[0])
+    if F and (int(faces.min()) < 0 or int(faces.max()) >= V):
+        raise _lib.EtchHipError(f"face vertex ids must lie in [0, {V})")
+    if int(contain_every) < 1:
+        raise _lib.EtchHipError("contain_every must be at least 1")
+    sv, sf, svo, sfo, mf = _ragged_mesh_args(scan, B, "smpl_surface_refine_contain")
+    nl = _lengths(lengths, B, N, points.device, "lengths")
+    if weights is not None:
+        weights = _need(weights.to(torch.float32).contiguous(), torch.float32, "weights")
+        if tuple(weights.shape) != (B, N):
+            raise _lib.EtchHipError(f"weights must be ({B},{N})")
+    M, vids, pos, valid = _marker_args(markers, B, V, points.device)
+    arr = (ctypes.c_void_p * 8)(*[t.data_ptr() for t in consts])
+    G, parr = 0, None
+    if prior is not None:
+        means, prec, w = (_need(t, torch.float32, n) for t, n in zip(prior, ("means", "precisions", "nll_weights")))
+        G = int(w.shape[0])
+        if tuple(w.shape) != (G,) or tuple(means.shape) != (G, 69) or tuple(prec.shape) != (G, 69, 69):
+            raise _lib.EtchHipError("prior: means (G,69), precisions (G,69,69), nll_weights (G,)")
+        parr = (ctypes.c_void_p * 3)(means.data_ptr(), prec.data_ptr(), w.data_ptr())
+    ws = _byte_workspace("etch_smpl_surface_refine_contain_workspace", points.device, B, N, V, int(nj), int(nb), int(n_extra), mf)
+    verts = torch.empty((B, V, 3), dtype=torch.float32, device=points.device)
+    joints = torch.empty((B, nj + n_extra, 3), dtype=torch.float32, device=points.device)
+    loss = torch.empty((B,), dtype=torch.float32, device=points.device)
+    tr = torch.empty((B, iters, 5), dtype=torch.float32, device=points.device) if want_trace else None
+    _lib.call("etch_smpl_surface_refine_contain", B, N, V, F, int(nj), int(nb), int(n_extra), arr, faces, points, nl, weights, M, vids, pos, valid, parr, G,
+              int(iters), float(lr), float(beta1), float(beta2), float(eps), float(w_dense), float(w_marker), float(w_beta), float(w_prior), float(trunc),
+              int(bool(optimize_scale)), mf, sv, sf, svo, sfo, float(w_contain), int(contain_every), params, verts, joints, tr, loss, ws)
+    return verts, joints, loss, tr
+
+
 # ------------------------------------------------------------------ SMPL+D registration and re-posing (csrc/register.hip)
 def smpl_skin_frames(consts, params, nj=24, nb=10):
     """params (B, 3 nj + nb + 4) = pose (global orient first) | beta | trans | scale -> base (B,V,3), R (B,V,9), A (B,nj,12) with

@@ -767,6 +767,59 @@ int etch_smpl_surface_refine(int B, int N, int V, int F, int nj, int nb, int n_e
                              float w_beta, float w_prior, float trunc, int optimize_scale, float* params, float* verts, float* joints, float* loss_trace,
                              float* loss_last, void* workspace, void* stream);
 
+/* ---- containment: keep the fitted body inside the scan (csrc/containment.hip) ------------------------------------------- */
+
+/* A ragged batch of B scan meshes is given as mesh_io.pack_meshes lays it out: verts (sum V,3) fp32, already in the frame of the queries,
+ * faces (sum F,3) int32 local to their scan, vert_offsets and face_offsets (B+1) int32 in device memory, starting at 0 and not decreasing;
+ * max_faces >= every scan's face count sizes the launches (a scan's faces past it are not visited).  Nothing is read on the host. */
+
+/* Workspace bytes of etch_mesh_winding_number. */
+int etch_mesh_winding_number_workspace(int B, int Q, int max_faces, long long* bytes);
+/* Generalised winding number w (B,Q) fp32 of scan b at queries (B,Q,3) fp32; q_len (B) int32 or NULL: queries at or past a scan's length
+ * are padding and get 0.  Per (query q, face (a, b, c)), with A = a - q, B = b - q, C = c - q, la, lb, lc their norms, every operation fp32
+ * in the order of csrc/containment.hip:  Omega / 2 = atan2f(A . (B x C), la lb lc + (A . B) lc + (B . C) la + (C . A) lb)  (van Oosterom and
+ * Strackee).  A thread adds the terms of one 1024-face chunk in ascending face order in fp32; the chunks are added in ascending order in
+ * fp64, multiplied by 1 / (2 pi) and rounded once: w = 1 inside a closed outward-oriented surface, 0 outside, -1 inside a reversed one.
+ * A face with a vertex index outside [0, V_b) contributes 0; a non-finite vertex or query gives NaN.  No atomics: scan b in a batch is
+ * bitwise scan b alone, and two runs are bitwise equal. */
+int etch_mesh_winding_number(int B, int Q, int max_faces, const float* verts, const int* faces, const int* vert_offsets, const int* face_offsets,
+                             const float* queries, const int* q_len, void* workspace, float* w, void* stream);
+/* Workspace bytes of etch_ragged_mesh_closest. */
+int etch_ragged_mesh_closest_workspace(int B, int N, long long* bytes);
+/* etch_point_mesh_closest for the ragged batch: the exact closest point of scan b's mesh to each point of points (B,N,3) fp32 (n_len (B) or
+ * NULL).  The same region test (csrc/closest_tri.h), the same key merge and the same rules: the smallest d2 wins, equal d2 -> the lowest
+ * face, a NaN d2 never wins and neither does a face with a vertex index outside [0, V_b).  Outputs: face (B,N) int32 local to the scan, bary
+ * (B,N,3), d2 (B,N); padding rows (and a point no face could be chosen for): face -1, bary 0, d2 0. */
+int etch_ragged_mesh_closest(int B, int N, int max_faces, const float* verts, const int* faces, const int* vert_offsets, const int* face_offsets,
+                             const float* points, const int* n_len, void* workspace, int* face, float* bary, float* d2, void* stream);
+/* Workspace bytes of etch_containment_energy_grad. */
+int etch_containment_energy_grad_workspace(int B, int V, long long* bytes);
+/* The containment term of body_verts (B,V,3) fp32 against the scans, from w (B,V) = the winding numbers of the vertices and (face, bary, d2)
+ * (B,V) = their correspondences on the scan (etch_ragged_mesh_closest):  o_v = [ |w_v| < 0.5 ] (a NaN w is not outside; neither is a vertex
+ * whose face is -1, out of range, or has a vertex index out of range), c_v = sum_k bary_k s_k the closest point.  Outputs: terms (B,2) fp64 =
+ * {sum_v o_v d2_v, sum_v o_v}, fixed order; g (B,V,3) or NULL, to which coef_b w_contain (2 / V) o_v (v - c_v) is ADDED (coef (B) or NULL =
+ * 1): the gradient of coef_b w_contain (sum_v o_v d2_v) / V with the correspondences held.  Each vertex receives one term, computed in fp64
+ * and added with one rounding: no scatter, no atomics; a vertex that is not outside keeps its bits, and so does every vertex when
+ * coef_b w_contain is 0. */
+int etch_containment_energy_grad(int B, int V, const float* body_verts, const float* verts, const int* faces, const int* vert_offsets,
+                                 const int* face_offsets, const float* w, const int* face, const float* bary, const float* d2, const float* coef,
+                                 float w_contain, void* workspace, double* terms, float* g, void* stream);
+/* Workspace bytes of etch_smpl_surface_refine_contain. */
+int etch_smpl_surface_refine_contain_workspace(int B, int N, int V, int nj, int nb, int n_extra, int max_faces, long long* bytes);
+/* etch_smpl_surface_refine with a fifth term of the loss, w_contain (sum_v o_v |v - c_v|^2) / V over the body's V vertices, against the scan
+ * meshes (max_scan_faces, scan_verts, scan_faces, scan_vert_offsets, scan_face_offsets: the ragged batch above, in the frame of the body).
+ * At iterations 0, K, 2K, ... (K = contain_every >= 1) the winding numbers and the scan correspondences of the current vertices are
+ * recomputed, every vertex against every face; in between o_v and c_v -- the target POINT, not the face -- are held, and |v - c_v|^2 is
+ * taken in fp64 at the current vertices.  The term is normalised by V, not by the count of outside vertices, so it is zero and flat where a
+ * vertex crosses the surface.  loss_trace is (B, iters, 5) or NULL, the fifth column this term.  With w_contain = 0 the parameters and the
+ * first four trace columns are bitwise those of etch_smpl_surface_refine.  Everything is queued on `stream` without a host wait. */
+int etch_smpl_surface_refine_contain(int B, int N, int V, int F, int nj, int nb, int n_extra, const void* const* consts, const int* faces, const float* points,
+                                     const int* n_len, const float* weights, int M, const int* marker_vids, const float* markers, const float* marker_valid,
+                                     const void* const* prior, int n_gauss, int iters, float lr, float beta1, float beta2, float eps, float w_dense,
+                                     float w_marker, float w_beta, float w_prior, float trunc, int optimize_scale, int max_scan_faces, const float* scan_verts,
+                                     const int* scan_faces, const int* scan_vert_offsets, const int* scan_face_offsets, float w_contain, int contain_every,
+                                     float* params, float* verts, float* joints, float* loss_trace, float* loss_last, void* workspace, void* stream);
+
 /* ---- SMPL+D registration and re-posing (csrc/register.hip) ------------------------------------------------------------ */
 
 /* Skinning frames of params (B, 3 nj + nb + 4) = pose (global orient first) | beta | trans | scale: with r_v the rest vertex after shape and
