@@ -22,7 +22,7 @@ class EtchHipError(RuntimeError):
 
 def has_experiments():
     """True if the loaded library was built with ETCH_BUILD_EXPERIMENTS=1 (the opt-in kernels measured slower than the default path:
-    etch_inter_so3conv32, etch_pt_block_k1 / _k2)."""
+    etch_pt_block_k1 / _k2)."""
     return hasattr(lib()._cdll, "etch_pt_block_k1")
 
 

@@ -30,17 +30,15 @@ def hipcc():
     raise RuntimeError("hipcc not found")
 
 
-EXPERIMENTS = os.environ.get("ETCH_BUILD_EXPERIMENTS", "0") == "1"
-EXPERIMENT_SOURCES = {"so3conv32.hip"}         # opt-in kernels measured slower than the default path (+ the `#ifdef ETCH_BUILD_EXPERIMENTS` parts of pt.hip)
+EXPERIMENTS = os.environ.get("ETCH_BUILD_EXPERIMENTS", "0") == "1"    # the opt-in kernels measured slower than the default path: the `#ifdef ETCH_BUILD_EXPERIMENTS` part of pt.hip
 
 
 EXP_OBJDIR = os.path.join(LIBDIR, "obj_exp")
 EXP_LIB = os.path.join(LIBDIR, "libetch_hip_exp.so")      # the library WITH the experiment kernels, beside the product's (tests of those kernels only)
 
 
-def sources(experiments=None):
-    experiments = EXPERIMENTS if experiments is None else experiments
-    return sorted(f for f in os.listdir(CSRC) if f.endswith(".hip") and (experiments or f not in EXPERIMENT_SOURCES))
+def sources():
+    return sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
 
 
 def _stale(target, deps):
@@ -56,7 +54,7 @@ def build(force=False, verbose=False):
 
 
 def build_experiments(force=False, verbose=False):
-    """libetch_hip_exp.so: every source with the experiment kernels (-DETCH_BUILD_EXPERIMENTS, so3conv32.hip) as a library of its own.  The product
+    """libetch_hip_exp.so: every source with the experiment kernels (-DETCH_BUILD_EXPERIMENTS) as a library of its own.  The product
     never loads it; the tests of those kernels run through it (_lib.experiments_library())."""
     return _build(EXP_OBJDIR, True, EXP_LIB, force, verbose, stamp=False)
 
@@ -66,7 +64,7 @@ def _compile_jobs(objdir, experiments, force):
     headers.append(os.path.join(os.path.dirname(HERE), "include", "etch_hip.h"))
     cc = hipcc()
     jobs, objs = [], []
-    for src in sources(experiments):
+    for src in sources():
         obj = os.path.join(objdir, src.replace(".hip", ".o"))
         objs.append(obj)
         if force or _stale(obj, [os.path.join(CSRC, src)] + headers + [os.path.abspath(__file__)]):

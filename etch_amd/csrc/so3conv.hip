@@ -1051,6 +1051,19 @@ __global__ void __launch_bounds__(256) instnorm_act_add_kernel(unsigned per4, in
     if (i < per4) one(i, X1[i], X2 ? X2[i] : z4);
 }
 
+// x [rows][C] fp32 -> planes [rows][3][C] bf16 (exact split); thread = 4 consecutive channels
+__global__ void __launch_bounds__(256) split3_planes_kernel(long n4, int C, const float* __restrict__ x, unsigned short* __restrict__ planes) {
+    const int c4 = C >> 2;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const long row = i / c4;
+        const int c = (int)(i - row * c4) * 4;
+        uint2 hi, mid, lo;
+        split3_pack4(reinterpret_cast<const float4*>(x)[i], hi, mid, lo);
+        unsigned short* pr = planes + (size_t)row * 3 * C + c;
+        *reinterpret_cast<uint2*>(pr) = hi; *reinterpret_cast<uint2*>(pr + C) = mid; *reinterpret_cast<uint2*>(pr + 2 * C) = lo;
+    }
+}
+
 // The final pass of the block whose output feeds the heads: the same `out`, plus the mean over each point's NA anchor rows (mean [b * p][C]), which the
 // heads' 3-NN blend reads -- token_mean_kernel re-read the whole tensor (0.61 GB at 32 x 5 000 points) for it.  A workgroup takes whole points; thread t
 // handles the point's float4 numbers t, t + 256, ... (anchor a0 + k AP of channel quad c4: token_mean_kernel's assignment), adds them in that order,
@@ -1347,6 +1360,23 @@ int etch_instnorm_act_add_planes_f16(int b, int rows, int C, const float* x1, co
 int etch_instnorm_act_add_k1_planes_f16(int b, int rows, int C, const float* x1, const float* m1, const float* r1, const float* f, const float* slope,
                                         const float* offset, float* out, void* planes, void* stream) {
     return instnorm_act_add_launch(true, b, rows, C, x1, m1, r1, f, slope, offset, out, planes, stream, true);
+}
+
+// the three bf16 planes of etch_instnorm_act_add_planes from fp32 rows that no producer kernel split
+int etch_split3_planes(long rows, int C, const float* x, void* planes, void* stream) {
+    if (rows <= 0) return ETCH_OK;
+    if (C <= 0 || (C & 3) || ((uintptr_t)x & 15) || ((uintptr_t)planes & 7)) return ETCH_EUNSUPPORTED;
+    const long n4 = rows * (C / 4);
+    long blocks = (n4 + 255) / 256;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    hipLaunchKernelGGL(split3_planes_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n4, C, x, reinterpret_cast<unsigned short*>(planes));
+    ETCH_RETURN_IF_LAUNCH_FAILED();
+    return ETCH_OK;
+}
+
+// 1 if etch_inter_so3conv_planes_kq (so3conv_y.hip) has an instantiation for the shape (the callers' routing test), else 0
+int etch_inter_so3conv_planes_supported(int cin, int cout, int nn) {
+    return ((cin == 32 && (cout == 32 || cout == 64)) || (cin == 64 && cout == 64)) && (nn == 32 || nn == 64);
 }
 
 // x1 / x2 / out (b, p, 60, C); mean (b * p, C) = the mean of out over each point's 60 anchor rows (what etch_token_mean gives on out).  C in {32, 64, 128, 256};

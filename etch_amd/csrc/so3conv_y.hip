@@ -4,7 +4,7 @@
 //                                  (/root/reference/external/vgtk/vgtk/so3conv/functional.py:286-324, :61-67, modules.py:33-39)
 //   etch_inter_kpoint_operand      rotated kernel points (functional.py:296) -> the B operand of the pre-activation product
 //
-// inter_so3conv_x32_kernel (so3conv_x.hip) generates every kernel weight w[a, k, n] = relu(1 - |g_n - R_a kappa_k|^2 / sigma) on the VALU: four
+// The round-4 kernel this one replaced (retired, DESIGN.md "Retired kernels") generated every kernel weight w[a, k, n] = relu(1 - |g_n - R_a kappa_k|^2 / sigma) on the VALU: four
 // packed fp32 instructions per weight pair behind two LDS table reads, as a dependent chain per pair, laid between the matrix instructions in
 // program order -- profiles/r04_inter_x_counters_and_ablations.txt: with the gathers, step 1's MFMAs and step 2 compiled out the kernels still take
 // 2.2 / 1.5 / 2.2 ms, i.e. ~1 800 cycles per (anchor, chunk) step for ~150 instructions; packed fp32 instructions never hide behind an MFMA
@@ -19,7 +19,7 @@
 //   * kernel-point factor: a table of the layer, [60 anchors][2][64 lanes][8] bf16 (122 880 bytes, L2-resident), two 16-byte loads per anchor;
 //   * the neighbour order of the product's rows is the staging tile's row order with bits 2 and 3 swapped, which makes the accumulator layout
 //     (rows 8 (v / 4) + 4 (lane / 32) + v % 4) land on the K slots 8 (lane / 32) + e of the two K steps of step 1.
-// Step 1 (transposed product on the gathered bf16 planes), the X1 tile, step 2 and the epilogue are those of inter_so3conv_x32_kernel.
+// Step 1 is the transposed product on the gathered planes (v_mfma_f32_32x32x16), the X1 tile is parked in LDS, step 2 (H32Step2) contracts it with W.
 // No inline-asm LDS reads are left in the loop (see etch_amd/isa_lint.py for why that matters); the W stream of step 2 keeps its asm ring.
 #include "so3conv_x.h"
 #include "etch_hip.h"
@@ -68,7 +68,7 @@ __global__ void __launch_bounds__(128) inter_kpoint_operand_kernel(float inv_sig
 
 // step 2 of the 32x32x16 kernels on the fp16 matrix cores: Y[o][a] += sum_kappa W[o][kappa] X1[a][kappa] with both operands as two fp16 planes (W pre-split
 // with every output channel's row times its own power of two, ops.inter_weight_split32_f16 -- undone per channel in the epilogue; the X1 row split by the wave that reads it) and the three largest cross products.
-// W fragments: [K step of 16][o tile of 32][plane][lane][8], streamed from L2 one batch ahead (inline-asm loads + counted waits, see X32Step2).
+// W fragments: [K step of 16][o tile of 32][plane][lane][8], streamed from L2 ahead of their use (inline-asm loads, x_wload_s, + counted waits).
 // Round 6: the look-ahead ring holds RD batches.  With ONE batch ahead (round 5) a batch's loads were requested 3 MFMAs (~100 cycles) before their wait --
 // an L2 round trip is several times that, and the 64-channel kernel (one wave per SIMD: nothing else to run meanwhile) spent step 2 waiting for W.
 template <int CIN, int COUT, int PAD, int RD>
@@ -199,7 +199,7 @@ __global__ void __launch_bounds__(256, INTER_Y_WPE(CIN)) inter_so3conv_y_kernel(
     constexpr int CH = CIN / 2;                    // channels per X1 half
     constexpr int NKR = CH / 2;                    // accumulator registers of a lane per half
     constexpr int KH = CH * KS;                    // contraction length of step 2 per half
-    constexpr int S = KH + Y_PAD(CIN);             // X1s row stride (floats), S / 4 odd (see inter_so3conv_x32_kernel); 32 input channels: the tile,
+    constexpr int S = KH + Y_PAD(CIN);             // X1s row stride (floats), S / 4 odd (the 32 rows of a B-fragment read start in different 16-byte slots); 32 input channels: the tile,
                                                    // the tables and the staging tiles of TWO workgroups must fit the 160 KB of a compute unit
     static_assert((S / 4) % 2 == 1, "row stride");
     constexpr int PS = COUT + 4;
@@ -215,7 +215,7 @@ __global__ void __launch_bounds__(256, INTER_Y_WPE(CIN)) inter_so3conv_y_kernel(
     float* dump = reinterpret_cast<float*>(noffs + 2 * NN);             // [64 lanes][4]: where the lanes of the unused kernel points 24 .. 31 store
     unsigned* s_next = reinterpret_cast<unsigned*>(dump + 256);         // the work item after next (from the counter)
     double* s_stat = reinterpret_cast<double*>(dump + 260);             // [256 threads][2]: the statistics' partial sums of pass 0, parked over pass 1's step 1
-    __shared__ __attribute__((aligned(16))) char stage[4 * STG];       // [4 waves][STG]: its own LDS object (see inter_so3conv_x_kernel)
+    __shared__ __attribute__((aligned(16))) char stage[4 * STG];       // [4 waves][STG]: an LDS object of its own
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
     // ---- work items of this workgroup: XCD xcd walks the slots [xcd * per, xcd * per + cnt) of every scan's processing order, item m = (scan m / cnt, slot m % cnt)
@@ -251,7 +251,8 @@ __global__ void __launch_bounds__(256, INTER_Y_WPE(CIN)) inter_so3conv_y_kernel(
     __syncthreads();
     const int kp = lane & 31, kg = lane >> 5;      // this lane's kernel point (weights: column of B; X1: column of D) and neighbour group / channel sub-block
     const bool kok = kp < KS;
-    // staging image of one plane of a chunk (see inter_so3conv_x32_kernel): load side -- lane = (row rl of the row block, 16-byte piece sl)
+    // staging image of one plane of a chunk: [32 rows][CIN fp16]; CIN = 64: the two 64-byte tile segments of row r swapped when (r >> 1) & 1, so that the four
+    // rows x 64 bytes the first two lane groups of a transposing read touch cover all 64 banks.  Load side -- lane = (row rl of the row block, 16-byte piece sl)
     const int rl = lane / PPR, sl = lane % PPR;
     const unsigned pieceoff = NT32 == 1 ? (unsigned)(sl * 16) : (unsigned)((4 * (((sl >> 2) - (rl >> 1)) & 1) + (sl & 3)) * 16);
     unsigned roff[NCH][NRB];
@@ -762,7 +763,8 @@ int etch_inter_kpoint_operand(float sigma, const float* rk, void* kq, void* stre
     return ETCH_OK;
 }
 
-// etch_inter_so3conv_planes32 with the kernel weights formed on the matrix cores.  kq = etch_inter_kpoint_operand(sigma, rk); Wq32 and feats_planes as there.
+// The inter conv on the 32x32x16 matrix instructions with the kernel weights formed on the matrix cores.  kq = etch_inter_kpoint_operand(sigma, rk); Wq32, wsc =
+// ops.inter_weight_split32_f16; feats_planes [b][p1][60][2][cin] fp16 (fsc: their per-scan scale, or NULL).
 int etch_inter_so3conv_planes_kq(int b, int cin, int cout, int p1, int p2, int nn, float sigma, const float* xyz, const float* new_xyz,
                                  const int* ball_idx, const void* feats_planes, const void* kq, const void* Wq32, const float* wsc, const float* fsc,
                                  const float* bias, float* out, const int* order, double* stat_part, void* stream) {

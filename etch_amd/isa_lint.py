@@ -1,6 +1,6 @@
 """ISA lint for the kernels that issue memory operations from inline asm with hand-counted waits.
 
-    python -m etch_amd.isa_lint etch_amd/csrc/so3conv_x.hip [-D...]      (cross-compiles for gfx950, no GPU needed)
+    python -m etch_amd.isa_lint etch_amd/csrc/so3conv_y.hip [-D...]      (cross-compiles for gfx950, no GPU needed)
 
 Why.  `asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : ...)` / `global_load_dwordx4 %0, ...` return their data ASYNCHRONOUSLY, but the compiler
 believes an asm statement's output is valid when the statement ends.  Between the load and the `s_waitcnt` asm that the source pairs it with, the

@@ -200,7 +200,7 @@ class SeparableSO3ConvBlock(nn.Module):
                 cloud.anchor_mean = amean
             return inter_idx, None, sample_idx, cloud
         s, m3, r3 = branch
-        # emit_planes (set by EquivBackbone when the NEXT conv gathers planes; True / "bf16" / "f16" = their format): the output is also written split, once, by this pass
+        # emit_planes (set by EquivBackbone when the NEXT conv gathers planes: "f16", their format -- InterSO3Conv.wants_planes): the output is also written split, once, by this pass
         planes, amean = None, None
         if self.emit_planes:
             out, planes = ops.instnorm_act_add(z.feats_cl, m2, r2, s, m3, r3, want_planes=self.emit_planes)

@@ -300,33 +300,15 @@ def split3_bf16(x):
     return torch.stack([(t >> 16).to(torch.int16) for t in (hi, mid, lo)])
 
 
-def inter_weight_split(W, cin, ks=24, natural=False):
-    """Weight of the inter conv for the split-operand kernels: columns in the kernel's contraction order (etch_inter_so3conv_split: the one of
-    inter_weight_frag; natural=True, etch_inter_so3conv_planes: W's own column order c * 24 + k), split into three bf16 planes, in
+def inter_weight_split(W, cin, ks=24):
+    """Weight of etch_inter_so3conv_split: columns in the kernel's contraction order (the one of inter_weight_frag), split into three bf16 planes, in
     v_mfma_f32_16x16x32_bf16 A-fragment order: [chunk of 32 kappas][o tile][plane][lane = 16 * (k / 8) + o % 16][8]."""
     cout = W.shape[0]
     assert cin % 16 == 0 and cout % 16 == 0 and W.shape[1] == cin * ks and ks == 24
-    planes = split3_bf16(W if natural else W[:, _inter_contraction_cols(cin, ks, W.device)])     # [3][cout][K]
+    planes = split3_bf16(W[:, _inter_contraction_cols(cin, ks, W.device)])     # [3][cout][K]
     K = cin * ks
     q = planes.reshape(3, cout // 16, 16, K // 32, 4, 8)                 # [pl][mt][ol][tg][kg][e]
     return q.permute(3, 1, 0, 4, 2, 5).contiguous().reshape(-1)          # [tg][mt][pl][kg][ol][e]
-
-
-def inter_weight_split32(W, cin, ks=24):
-    """Weight of etch_inter_so3conv_planes32 (v_mfma_f32_32x32x16_bf16): the columns of W [cout, cin*24] in the kernel's PHYSICAL contraction order --
-    per channel half h (CH = cin / 2 channels), kernel point k, 16-byte block pb, element i: channel h*CH + 4*(pb ^ sw(k)) + i with the X1 tile's
-    store swizzle sw(k) = (k >> 1) & 3 (CH = 16) / k & 7 (CH = 32) -- split into three bf16 planes, in A-fragment order
-    [K step of 16][o tile of 32][plane][lane = 32 * (kappa / 8 % 2) + o % 32][8]."""
-    cout = W.shape[0]
-    assert ks == 24 and cin in (32, 64) and cout % 32 == 0 and W.shape[1] == cin * ks
-    ch = cin // 2
-    cols = [(h * ch + 4 * (pb ^ (((k >> 1) & 3) if ch == 16 else (k & 7))) + i) * ks + k
-            for h in range(2) for k in range(ks) for pb in range(ch // 4) for i in range(4)]
-    assert sorted(cols) == list(range(cin * ks))
-    planes = split3_bf16(W[:, torch.tensor(cols, dtype=torch.long, device=W.device)])     # [3][cout][K]
-    K = cin * ks
-    q = planes.reshape(3, cout // 32, 32, K // 16, 2, 8)                 # [pl][mt][o][s][kg][e]
-    return q.permute(3, 1, 0, 4, 2, 5).contiguous().reshape(-1)          # [s][mt][pl][kg][o][e]
 
 
 def intra_weight_split(w2):
@@ -373,33 +355,10 @@ def intra_weight_split_f16(w2):
     return out
 
 
-def inter_weight_frag32(W, cin, ks=24):
-    """Fragment order of the 32x32x2 inter conv (csrc/so3conv32.hip): [slice = 3 h + g][mt][kp][u][lane][4] with
-    [lane][s] = W[32 mt + lane % 32][(32 h + c) * 24 + 8 g + 4 (lane / 32) + s], c = kp * NU + u -- h = 32-channel tile of the input,
-    g = group of 8 kernel points, the slice's 256 contraction entries split over NKP = 8 / MT waves of NU = 32 / NKP k-steps."""
-    cout = W.shape[0]
-    assert ks == 24 and cin % 32 == 0 and cout in (32, 64) and W.shape[1] == cin * ks
-    mt, ntil = cout // 32, cin // 32
-    nkp = 8 // mt
-    nu = 32 // nkp
-    w = W.reshape(mt, 32, ntil, nkp, nu, 3, 2, 4)          # [mt][j][h][kp][u][g][kk][s]
-    return w.permute(2, 5, 0, 3, 4, 6, 1, 7).contiguous().reshape(-1)
-
-
 INTER_SPLIT = os.environ.get("ETCH_INTER_SPLIT", "1") != "0"      # step 2 of the inter conv on the bf16 matrix cores (split fp32 operands); 0: fp32 MFMA
-INTER_MFMA32 = os.environ.get("ETCH_INTER_MFMA32", "0") == "1"     # (32|64) -> (32|64) channels: the 32x32x2 MFMA form, two points per workgroup
-INTER_MFMA32_SHAPES = ((32, 32), (32, 64), (64, 64))
-INTER_X = os.environ.get("ETCH_INTER_X", "1") != "0"             # both contractions of the inter conv on the bf16 matrix cores, gathered rows as bf16 planes (csrc/so3conv_x.hip)
-INTER_X32 = os.environ.get("ETCH_INTER_X", "1") != "16"          # 64 input channels: the 32x32x16 MFMA form (ETCH_INTER_X=16: the 16x16x32 form everywhere)
-
-
+INTER_X = os.environ.get("ETCH_INTER_X", "1") != "0"             # both contractions of the inter conv on the matrix cores, gathered rows as planes (csrc/so3conv_y.hip); 0: the round-3 kernels
 INTER_KQ = os.environ.get("ETCH_INTER_KQ", "1") != "0"          # kernel weights formed on the matrix cores (csrc/so3conv_y.hip); 0: the round-3 kernels (fp32 MFMA step 1,
-                                                                 # exact three-plane step 2) -- or, in an ETCH_BUILD_EXPERIMENTS library, the retired round-4 planes kernels
-
-
-def inter_planes_form(cin):
-    """MFMA shape of the round-4 planes kernel for this width: 32 (etch_inter_so3conv_planes32, 64 input channels) or 16 (etch_inter_so3conv_planes)."""
-    return 32 if (INTER_X32 and cin == 64) else 16
+                                                                 # exact three-plane step 2)
 
 
 def split2_planes_f16(x_cl):
@@ -425,9 +384,11 @@ def split2_planes_f16_scaled(x_cl):
 
 
 def inter_weight_split32_f16(W, cin, ks=24):
-    """Weight of etch_inter_so3conv_planes_kq: the columns of W [cout, cin*24] in the physical contraction order of inter_weight_split32, every row (output
-    channel) times its own power of two (_row_pow2: exact; `.wsc` = the inverse powers, applied by the kernel's epilogue), as two fp16 planes
-    h = fp16(w), l = fp16(w - h), in A-fragment order [K step of 16][o tile of 32][plane][lane = 32 * (kappa / 8 % 2) + o % 32][8]."""
+    """Weight of etch_inter_so3conv_planes_kq: the columns of W [cout, cin*24] in the kernel's PHYSICAL contraction order -- per channel half h
+    (CH = cin / 2 channels), kernel point k, 16-byte block pb, element i: channel h*CH + 4*(pb ^ sw(k)) + i with the X1 tile's store swizzle
+    sw(k) = (k >> 1) & 3 (CH = 16) / k & 7 (CH = 32) --, every row (output channel) times its own power of two (_row_pow2: exact; `.wsc` = the inverse
+    powers, applied by the kernel's epilogue), as two fp16 planes h = fp16(w), l = fp16(w - h), in A-fragment order
+    [K step of 16][o tile of 32][plane][lane = 32 * (kappa / 8 % 2) + o % 32][8]."""
     cout = W.shape[0]
     assert ks == 24 and cin in (32, 64) and cout % 32 == 0 and W.shape[1] == cin * ks
     ch = cin // 2
@@ -455,13 +416,13 @@ def inter_kpoint_operand(rk, sigma):
 
 
 def inter_planes_supported(cin, cout, nn):
-    """Shapes etch_inter_so3conv_planes covers (the three convs of the released encoder depth)."""
+    """Shapes etch_inter_so3conv_planes_kq covers (the three convs of the released encoder depth)."""
     return INTER_X and (cin, cout) in ((32, 32), (32, 64), (64, 64)) and nn in (32, 64)      # = etch_inter_so3conv_planes_supported
 
 
 def split3_planes(x_cl):
-    """x (..., C) fp32 -> (..., 3, C) int16: the bf16 bit patterns of the exact split x = hi + mid + lo, the layout etch_inter_so3conv_planes
-    gathers (the encoder's own producer, instnorm_act_add(want_planes=True), writes it directly)."""
+    """x (..., C) fp32 -> (..., 3, C) int16: the bf16 bit patterns of the exact split x = hi + mid + lo (the layout instnorm_act_add(want_planes=True)
+    writes)."""
     _need(x_cl, torch.float32, "x")
     C = x_cl.shape[-1]
     planes = torch.empty(tuple(x_cl.shape[:-1]) + (3, C), dtype=torch.int16, device=x_cl.device)
@@ -480,14 +441,14 @@ def spatial_order(xyz):
     return order
 
 
-def inter_so3conv(xyz, new_xyz, ball_idx, feats_cl, rk, W, Wp, bias, sigma, order=None, want_stats=False, Wp32=None, Wq=None, Wqn=None,
-                  feats_planes=None, Wq32=None, kq=None, Wqh=None):
+def inter_so3conv(xyz, new_xyz, ball_idx, feats_cl, rk, W, Wp, bias, sigma, order=None, want_stats=False, Wq=None, feats_planes=None, kq=None, Wqh=None):
     """feats_cl (b,p1,60,cin) channels-last -> (b,p2,60,cout) pre-norm.  order (b,p2) int32: processing order of the output points.
-    want_stats: also return the InstanceNorm (mean, rstd) of the output, accumulated in the conv's epilogue.
-    kq (inter_kpoint_operand) + Wqh (inter_weight_split32_f16): the round-5 kernel (weights' pre-activation on the matrix cores, two fp16 planes per
-    operand, every covered shape); feats_planes (b,p1,60,2,cin) float16 = split2_planes_f16 (made here when absent or in the bf16 format).
-    Wq32 (inter_weight_split32) / Wqn (inter_weight_split(natural=True)): both contractions on the bf16 matrix cores where the shape is covered
-    (32x32x16 for 64 input channels / 16x16x32 MFMA form); feats_planes (b,p1,60,3,cin) int16 = the producer's split of feats_cl (made here when absent)."""
+    want_stats: also return the InstanceNorm (mean, rstd) of the output, accumulated in the conv's epilogue.  Three paths, the first that applies:
+    kq (inter_kpoint_operand) + Wqh (inter_weight_split32_f16), a shape of inter_planes_supported: etch_inter_so3conv_planes_kq (weights' pre-activation
+    on the matrix cores, two fp16 planes per operand); feats_planes (b,p1,60,2,cin) float16 = split2_planes_f16 (made here when absent or in the bf16
+    format).  ETCH_INTER_KQ=0 / ETCH_INTER_X=0 switch it off.
+    Wq (inter_weight_split), cin a multiple of 16: etch_inter_so3conv_split, the round-3 kernel with step 2 on the bf16 matrix cores (ETCH_INTER_SPLIT=0: off).
+    Otherwise etch_inter_so3conv_ordered, the fp32 kernel (W, Wp = inter_weight_frag)."""
     b, p1, na, cin = feats_cl.shape
     p2, nn = ball_idx.shape[1], ball_idx.shape[2]
     cout = W.shape[0]
@@ -511,23 +472,6 @@ def inter_so3conv(xyz, new_xyz, ball_idx, feats_cl, rk, W, Wp, bias, sigma, orde
         assert tuple(feats_planes.shape) == (b, p1, na, 2, cin) and kq.numel() == 60 * 2 * 64 * 8 and Wqh.numel() == 2 * cout * cin * 24
         _lib.call("etch_inter_so3conv_planes_kq", b, cin, cout, p1, p2, nn, float(sigma), xyz, new_xyz, ball_idx, feats_planes, kq, Wqh, Wqh.wsc, fsc, bias,
                   out, order, part)
-    elif Wq32 is not None and cin == 64 and inter_planes_form(cin) == 32 and inter_planes_supported(cin, cout, nn) and _lib.has_experiments():
-        _need(Wq32, torch.int16, "Wq32")
-        if feats_planes is None or feats_planes.dtype != torch.int16:
-            feats_planes = split3_planes(feats_cl)
-        _need(feats_planes, torch.int16, "feats_planes")
-        assert tuple(feats_planes.shape) == (b, p1, na, 3, cin)
-        _lib.call("etch_inter_so3conv_planes32", b, cin, cout, p1, p2, nn, float(sigma), xyz, new_xyz, ball_idx, feats_planes, rk, Wq32, bias, out, order, part)
-    elif Wqn is not None and inter_planes_supported(cin, cout, nn) and _lib.has_experiments():
-        _need(Wqn, torch.int16, "Wqn")
-        if feats_planes is None or feats_planes.dtype != torch.int16:
-            feats_planes = split3_planes(feats_cl)
-        _need(feats_planes, torch.int16, "feats_planes")
-        assert tuple(feats_planes.shape) == (b, p1, na, 3, cin)
-        _lib.call("etch_inter_so3conv_planes", b, cin, cout, p1, p2, nn, float(sigma), xyz, new_xyz, ball_idx, feats_planes, rk, Wqn, bias, out, order, part)
-    elif Wp32 is not None and INTER_MFMA32 and (cin, cout) in INTER_MFMA32_SHAPES and _lib.has_experiments():
-        _need(Wp32, torch.float32, "Wp32")
-        _lib.call("etch_inter_so3conv32", b, cin, cout, p1, p2, nn, float(sigma), xyz, new_xyz, ball_idx, feats_cl, rk, Wp32, bias, out, order, part)
     elif Wq is not None and INTER_SPLIT and cin % 16 == 0:
         _need(Wq, torch.int16, "Wq")
         _lib.call("etch_inter_so3conv_split", b, cin, cout, p1, p2, nn, float(sigma), xyz, new_xyz, ball_idx, feats_cl, rk, Wq, bias, out, order, part)

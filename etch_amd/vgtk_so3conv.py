@@ -136,10 +136,7 @@ class InterSO3Conv(nn.Module):
         self.register_buffer("kernels", torch.from_numpy(kernels))
         self._d = _Derived()
         self._drk = _Derived()
-        self._d32 = _Derived()
         self._dq = _Derived()
-        self._dqn = _Derived()
-        self._dq32 = _Derived()
         self._dkq = _Derived()
         self._dqh = _Derived()
 
@@ -162,13 +159,6 @@ class InterSO3Conv(nn.Module):
 
         return (self.rotated_kernels(),) + self._d.get((W, bias), build)
 
-    def _wp32(self):
-        """Weight in the fragment order of the 32x32x2 kernel (csrc/so3conv32.hip), for the widths it covers; else None."""
-        if (self.dim_in, self.dim_out) not in ops.INTER_MFMA32_SHAPES or self.kernel_size != 24:
-            return None
-        W = self.basic_conv.W
-        return self._d32.get((W,), lambda: ops.inter_weight_frag32(W.detach().contiguous(), self.dim_in, self.kernel_size))
-
     def _wq(self):
         """Weight as three bf16 planes in the fragment order of the split-operand kernel (etch_inter_so3conv_split); None for cin < 16."""
         if self.dim_in % 16 != 0 or self.dim_out % 16 != 0 or self.kernel_size != 24:
@@ -176,23 +166,8 @@ class InterSO3Conv(nn.Module):
         W = self.basic_conv.W
         return self._dq.get((W,), lambda: ops.inter_weight_split(W.detach().contiguous(), self.dim_in, self.kernel_size))
 
-    def _wqn(self):
-        """The same planes in W's natural column order: etch_inter_so3conv_planes (both contractions on the bf16 matrix cores); None where
-        that kernel has no instantiation."""
-        if not ops.inter_planes_supported(self.dim_in, self.dim_out, self.n_neighbor) or self.kernel_size != 24:
-            return None
-        W = self.basic_conv.W
-        return self._dqn.get((W,), lambda: ops.inter_weight_split(W.detach().contiguous(), self.dim_in, self.kernel_size, natural=True))
-
-    def _wq32(self):
-        """The planes in the physical contraction order of the 32x32x16 kernel (etch_inter_so3conv_planes32); None where it has no instantiation."""
-        if not (self.wants_planes() and ops.inter_planes_form(self.dim_in) == 32):
-            return None
-        W = self.basic_conv.W
-        return self._dq32.get((W,), lambda: ops.inter_weight_split32(W.detach().contiguous(), self.dim_in, self.kernel_size))
-
     def _wqh(self):
-        """The two fp16 planes of 2^6 W in the physical contraction order of the 32x32x16 kernels (etch_inter_so3conv_planes_kq); None where unused."""
+        """The two fp16 planes of 2^6 W in the physical contraction order of the 32x32x16 kernel (etch_inter_so3conv_planes_kq); None where unused."""
         if not (ops.INTER_KQ and self.wants_planes()):
             return None
         W = self.basic_conv.W
@@ -207,13 +182,10 @@ class InterSO3Conv(nn.Module):
 
     def wants_planes(self):
         """Falsy, or the plane format this conv gathers its input in (its producer should emit it: SeparableSO3ConvBlock.emit_planes):
-        "f16" (two fp16 planes, etch_inter_so3conv_planes_kq) / "bf16" (three bf16 planes, the round-4 kernels)."""
+        "f16" (two fp16 planes, etch_inter_so3conv_planes_kq)."""
         if not (ops.inter_planes_supported(self.dim_in, self.dim_out, self.n_neighbor) and self.kernel_size == 24):
             return False
-        if ops.INTER_KQ:
-            return "f16"
-        from . import _lib
-        return "bf16" if _lib.has_experiments() else False        # the round-4 planes kernels exist only in an ETCH_BUILD_EXPERIMENTS library (round 6)
+        return "f16" if ops.INTER_KQ else False
 
     def group(self, xyz):
         """functional.py:176-185 inter_spconv_grouping_ball (index part): -> ball_idx, sample_idx, new_xyz.
@@ -245,8 +217,8 @@ class InterSO3Conv(nn.Module):
         else:
             sample_idx, new_xyz = None, xyz
         rk, W, Wp, bias = self._derived()
-        y, stats = ops.inter_so3conv(xyz, new_xyz, inter_idx, x.feats_cl, rk, W, Wp, bias, self.sigma, order=self.order(new_xyz), want_stats=True, Wp32=self._wp32(), Wq=self._wq(),
-                                     Wqn=None if ops.inter_planes_form(self.dim_in) == 32 else self._wqn(), Wq32=self._wq32(), kq=self._kq(), Wqh=self._wqh(), feats_planes=getattr(x, "feats_planes", None))
+        y, stats = ops.inter_so3conv(xyz, new_xyz, inter_idx, x.feats_cl, rk, W, Wp, bias, self.sigma, order=self.order(new_xyz), want_stats=True, Wq=self._wq(),
+                                     kq=self._kq(), Wqh=self._wqh(), feats_planes=getattr(x, "feats_planes", None))
         cloud = SphericalPointCloud(new_xyz, None, self.anchors, feats_cl=y)
         cloud.in_stats = stats          # InstanceNorm (mean, rstd) of the output, a by-product of the conv's epilogue
         return inter_idx, None, sample_idx, cloud

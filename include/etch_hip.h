@@ -158,16 +158,6 @@ int etch_inter_so3conv_ordered(int b, int cin, int cout, int p1, int p2, int nn,
                                const int* ball_idx, const float* feats, const float* rk, const float* W, const float* Wp,
                                const float* bias, float* out, const int* order, double* stat_part, void* stream);
 
-#ifdef ETCH_BUILD_EXPERIMENTS
-/* The same convolution on the 32x32x2 fp32 MFMA (0.986 of the matrix peak on this chip against 0.85 for 16x16x4,
- * profiles/r03_mfma_issue_rate.txt), two output points per workgroup; (cin, cout) in {(32,32), (32,64), (64,64)}, nn <= 64.
- * Wp32[slice = 3 h + g][mt][kp][u][lane][s] = W[32 mt + lane % 32][(32 h + kp * NU + u) * 24 + 8 g + 4 (lane / 32) + s] with
- * NKP = 8 / (cout / 32) K-shares kp of NU = 32 / NKP steps u (etch_amd/ops.py inter_weight_frag32).  order / stat_part as above. */
-int etch_inter_so3conv32(int b, int cin, int cout, int p1, int p2, int nn, float sigma, const float* xyz, const float* new_xyz,
-                         const int* ball_idx, const float* feats, const float* rk, const float* Wp32, const float* bias, float* out,
-                         const int* order, double* stat_part, void* stream);
-#endif
-
 /* The same convolution with its second contraction (W x X1, 1/2 - 2/3 of the flops) on the bf16 matrix cores: every fp32 operand split exactly
  * into three bf16 values (8 + 8 + 8 mantissa bits), the six largest cross products accumulated in fp32 -- the error against fp64 of the fp32
  * MFMA (profiles/r03_bf16x3_split.txt) at 2.3 x its rate.  cin, cout multiples of 16.  Wq: 3 * cout * cin * 24 bf16 =
@@ -176,28 +166,8 @@ int etch_inter_so3conv_split(int b, int cin, int cout, int p1, int p2, int nn, f
                              const int* ball_idx, const float* feats, const float* rk, const void* Wq, const float* bias, float* out,
                              const int* order, double* stat_part, void* stream);
 
-/* 1 if (cin, cout, nn) is a shape the planes kernels (etch_inter_so3conv_planes_kq; with ETCH_BUILD_EXPERIMENTS also the round-4 forms) are built for. */
+/* 1 if (cin, cout, nn) is a shape the planes kernel (etch_inter_so3conv_planes_kq) is built for. */
 int etch_inter_so3conv_planes_supported(int cin, int cout, int nn);
-
-#ifdef ETCH_BUILD_EXPERIMENTS      /* round-4 kernels, retired from the default build in round 6 (a sibling instantiation mis-executed for a cause that was never named: profiles/r05_x32_cin32_root_cause.txt) */
-/* The same convolution with BOTH contractions on the bf16 matrix cores (round 4, etch_amd/csrc/so3conv_x.hip): the neighbour contraction
- * X1[k, c] = sum_n w[a, k, n] F[idx_n, a, c] (functional.py:61-67 with the weights of :286-324 generated in registers) runs as split-operand
- * products too.  The gathered rows come as three bf16 planes written once by their producer: feats_planes (b, p1, 60, 3, cin) bf16 =
- * hi / mid / lo of the fp32 features (exact: hi + mid + lo == value; etch_split3_planes or etch_instnorm_act_add_planes write them), loaded
- * global -> LDS directly and read back as matrix-core fragments with the transposing LDS read.  (cin, cout) in {(32,32), (32,64), (64,64)},
- * nn in {32, 64} (etch_inter_so3conv_planes_supported).  Wq as for etch_inter_so3conv_split but in W's NATURAL column order
- * (etch_amd/ops.py inter_weight_split(natural=True)).  order / stat_part as above.  Same result as the fp32 kernels up to the order of the
- * fp32 sums. */
-int etch_inter_so3conv_planes(int b, int cin, int cout, int p1, int p2, int nn, float sigma, const float* xyz, const float* new_xyz,
-                              const int* ball_idx, const void* feats_planes, const float* rk, const void* Wq, const float* bias, float* out,
-                              const int* order, double* stat_part, void* stream);
-/* The same on v_mfma_f32_32x32x16_bf16, the bf16 shape that issues at the matrix peak on this chip (profiles/r04_mfma_bf16_issue_rates.txt; the 16x16x32
- * shape of the entry above reaches 0.55 - 0.6 of it).  Wq32: 3 * cout * cin * 24 bf16 = [K step of 16][o tile of 32][plane][lane][8] in the kernel's
- * physical contraction order (etch_amd/ops.py inter_weight_split32).  Same shapes, same result up to the order of the fp32 sums. */
-int etch_inter_so3conv_planes32(int b, int cin, int cout, int p1, int p2, int nn, float sigma, const float* xyz, const float* new_xyz,
-                                const int* ball_idx, const void* feats_planes, const float* rk, const void* Wq32, const float* bias, float* out,
-                                const int* order, double* stat_part, void* stream);
-#endif
 
 /* Round 5 (etch_amd/csrc/so3conv_y.hip): the inter conv of functional.py:286-324, :61-67 + modules.py:33-39 rebuilt around three measurements of
  * this round (profiles/r05_inter_conv_latency_bound.txt, r05_f16_two_plane_split.txt):
@@ -210,7 +180,7 @@ int etch_inter_so3conv_planes32(int b, int cin, int cout, int p1, int p2, int nn
  * feats_planes (b, p1, 60, 2, cin) fp16 = etch_split2_planes_f16 / etch_instnorm_act_add_planes_f16 of the fp32 features; kq =
  * etch_inter_kpoint_operand(sigma, rk): [60 anchors][2 K steps][64 lanes][8] bf16 (122 880 bytes), the kernel-point factor in B-fragment order, built
  * once per layer from rk [60][24][3] = anchors @ kernel points (functional.py:296); Wq: 2 * cout * cin * 24 fp16 = the two planes of W, every row (output
- * channel) times the power of two that puts its maximum into [8, 16), in the physical contraction order of etch_inter_so3conv_planes32,
+ * channel) times the power of two that puts its maximum into [8, 16), in the kernel's physical contraction order,
  * [K step of 16][o tile of 32][plane][lane][8]; wsc (cout floats) = the rows' inverse powers (etch_amd/ops.py inter_weight_split32_f16 and its `.wsc`).
  * fsc: NULL (the planes are those of the features as they stand: InstanceNorm outputs, unit scale by construction) or b floats, scan s's outputs
  * (before the bias) are multiplied by fsc[s] (etch_split2_planes_f16_scaled).  Round 6: persistent workgroups (one grid of 2 x CUs workgroups walks the
@@ -282,7 +252,7 @@ int etch_instnorm_stats_workspace_bytes(int b, int C);
  * SeparableSO3ConvBlock.forward (src/models/so3conv.py:178-182).  x2 may be NULL. */
 int etch_instnorm_act_add(int b, int rows, int C, const float* x1, const float* m1, const float* r1, const float* x2,
                           const float* m2, const float* r2, float* out, void* stream);
-/* The same, additionally writing the result as three bf16 planes (b, rows, 3, C) for etch_inter_so3conv_planes (planes may be NULL). */
+/* The same, additionally writing the result as three bf16 planes (b, rows, 3, C), the format of etch_split3_planes (planes may be NULL). */
 /* The same for x1 / x2 / out (b,p,60,C), additionally writing mean (b*p,C) = the mean of out over each point's 60 anchor rows: bitwise what
  * etch_token_mean(b*p, 60, C, out) gives, without re-reading out.  C in {32, 64, 128, 256}; otherwise ETCH_EUNSUPPORTED. */
 int etch_instnorm_act_add_mean(int b, int p, int C, const float* x1, const float* m1, const float* r1, const float* x2, const float* m2, const float* r2,

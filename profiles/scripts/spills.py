@@ -13,7 +13,7 @@ def demangle(n):
 rows = []
 with tempfile.TemporaryDirectory() as tmp:
     for f in sorted(os.listdir(CSRC)):
-        if not f.endswith(".hip") or f == "so3conv32.hip":
+        if not f.endswith(".hip"):
             continue
         out = os.path.join(tmp, f + ".s")
         extra = ["-ffp-contract=off"] if f == "index_ops.hip" else []

@@ -1,5 +1,5 @@
 """Times the three inter convs of the released encoder depth at the bench batch (32 x 5 000 points): round-3 kernel (step 1 on the fp32 MFMA),
-round-4 planes kernels, round-5 kq kernel (weights' pre-activation on the matrix cores).  python profiles/scripts/time_inter_kq.py [reps] [only_kq]"""
+round-5 kq kernel (weights' pre-activation on the matrix cores).  python profiles/scripts/time_inter_kq.py [reps] [only_kq]"""
 import os
 import sys
 
@@ -27,12 +27,10 @@ for name, cin, cout, nn, radius, sigma, xyz, p2 in shapes:
     conv = load_seeded(V.InterSO3Conv(cin, cout, 1, 1, radius, sigma, nn), 3).cuda()
     rk, W, Wp, bias = conv._derived()
     feats = torch.randn(B, xyz.shape[2], 60, cin, generator=g).cuda()
-    planes = ops.split3_planes(feats)
     order = ops.spatial_order(new_xyz)
-    wq32 = ops.inter_weight_split32(W, cin)
     forms = [("kq", dict(Wqh=ops.inter_weight_split32_f16(W, cin), kq=ops.inter_kpoint_operand(rk, sigma), feats_planes=ops.split2_planes_f16(feats)))]
     if not only_kq:
-        forms = [("r03", dict(Wq=conv._wq())), ("r04", dict(Wq32=wq32, feats_planes=planes) if cin == 64 else dict(Wqn=ops.inter_weight_split(W, cin, natural=True), feats_planes=planes))] + forms
+        forms = [("r03", dict(Wq=conv._wq()))] + forms
     res = {}
     for label, kw in forms:
         f = lambda: ops.inter_so3conv(xyz, new_xyz, ball, feats, rk, W, Wp, bias, sigma, order=order, want_stats=True, **kw)
@@ -52,6 +50,6 @@ for name, cin, cout, nn, radius, sigma, xyz, p2 in shapes:
         line.append(f"{name} {res['kq'][0]:.3f} [{cs:012x}]")
     else:
         d = float((res["kq"][1] - res["r03"][1]).abs().max()) / float(res["r03"][1].abs().max())
-        print(f"{name} {cin}->{cout} nn={nn} p2={p2}: r03 {res['r03'][0]:.3f} ms, r04 {res['r04'][0]:.3f} ms, kq {res['kq'][0]:.3f} ms, kq vs r03 max diff / scale {d:.2e}", flush=True)
+        print(f"{name} {cin}->{cout} nn={nn} p2={p2}: r03 {res['r03'][0]:.3f} ms, kq {res['kq'][0]:.3f} ms, kq vs r03 max diff / scale {d:.2e}", flush=True)
 if only_kq:
     print(" ".join(line), f"sum {tot:.3f}", flush=True)

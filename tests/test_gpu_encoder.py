@@ -350,29 +350,3 @@ def experiments():
     with _lib.experiments_library():
         assert _lib.has_experiments()
         yield
-
-
-@pytest.mark.parametrize("cin,cout,nn", [(32, 32, 32), (32, 64, 64), (64, 64, 20)])
-def test_inter_conv_32x32x2_variant_matches(cin, cout, nn, experiments):
-    """The opt-in two-points-per-workgroup kernel on v_mfma_f32_32x32x2_f32 (etch_inter_so3conv32, ETCH_INTER_MFMA32=1;
-    profiles/r03_inter_conv32_and_valu_overlap.txt) computes the same convolution; odd point counts leave its second point empty."""
-    from etch_amd import ops
-    from etch_amd import vgtk_so3conv as V
-    g = torch.Generator().manual_seed(cin + nn)
-    b, p1, p2 = 2, 211, 101
-    xyz = (torch.randn(b, 3, p1, generator=g) * 0.2).cuda()
-    new_xyz = xyz[:, :, :p2].contiguous()
-    ball = ops.ball_query(new_xyz, xyz, 0.25, nn)
-    conv = load_seeded(V.InterSO3Conv(cin, cout, 1, 2, 0.25, 0.03, nn), 3).cuda()
-    rk, W, Wp, bias = conv._derived()
-    feats = torch.randn(b, p1, 60, cin, generator=g).cuda()
-    ref, (m0, r0) = ops.inter_so3conv(xyz, new_xyz, ball, feats, rk, W, Wp, bias, conv.sigma, want_stats=True)
-    saved = ops.INTER_MFMA32
-    ops.INTER_MFMA32 = True
-    try:
-        out, (m, r) = ops.inter_so3conv(xyz, new_xyz, ball, feats, rk, W, Wp, bias, conv.sigma, want_stats=True, Wp32=conv._wp32(), order=ops.spatial_order(new_xyz))
-        assert torch.equal(out, ops.inter_so3conv(xyz, new_xyz, ball, feats, rk, W, Wp, bias, conv.sigma, Wp32=conv._wp32()))
-    finally:
-        ops.INTER_MFMA32 = saved
-    assert float((out - ref).abs().max()) < 2e-6 * float(ref.abs().max())
-    assert rel_err(m.cpu().numpy(), m0.cpu().numpy()) < 2e-6 and rel_err(r.cpu().numpy(), r0.cpu().numpy()) < 2e-6

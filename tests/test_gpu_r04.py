@@ -1,10 +1,9 @@
-"""Round-4 GPU tests: the inter conv with both contractions on the bf16 matrix cores (csrc/so3conv_x.hip), the bf16-plane producers."""
+"""Round-4 GPU tests: the bf16-plane producers, the encoder with and without them."""
 import numpy as np
 import pytest
 import torch
 
 from etch_amd.utils.weights import load_seeded
-from tests.test_gpu_encoder import _inter_conv_fp64, experiments, rel_err  # noqa: F401  (experiments: fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -26,45 +25,6 @@ def test_split3_planes_are_exact_and_match_the_host_split():
     out = ops.instnorm_act_add(x, m, r, x2, m2, r2)
     out_p, pl = ops.instnorm_act_add(x, m, r, x2, m2, r2, want_planes=True)
     assert torch.equal(out, out_p) and torch.equal(pl, ops.split3_planes(out))
-
-
-@pytest.mark.parametrize("form", [32, 16])
-@pytest.mark.parametrize("cin,cout,nn,p1,p2", [(32, 32, 32, 301, 149), (32, 64, 64, 211, 60), (64, 64, 32, 211, 101), (32, 32, 64, 130, 1),
-                                                (32, 64, 32, 97, 97), (64, 64, 64, 150, 33)])
-def test_inter_conv_planes_matches_the_fp32_kernel_and_fp64(cin, cout, nn, p1, p2, form, experiments):
-    """etch_inter_so3conv_planes32 / etch_inter_so3conv_planes (32x32x16 / 16x16x32 MFMA form; BOTH contractions on the bf16 matrix cores: fp32 operands split exactly into three bf16 values, six cross
-    products each; gathered rows as producer-written planes through LDS-direct loads + transposing LDS reads) against the fp32-MFMA kernel
-    (the same sums in another order) and the fp64 formula under the entitled-error rule; bitwise reproducible, schedule-independent;
-    padded neighbourhoods (radius smaller than the cloud: cyclic padding) included."""
-    from etch_amd import ops
-    from etch_amd import vgtk_so3conv as V
-    assert ops.inter_planes_supported(cin, cout, nn)
-    g = torch.Generator().manual_seed(cin + nn + p2)
-    b = 2
-    xyz = (torch.randn(b, 3, p1, generator=g) * 0.2).cuda()
-    new_xyz = xyz[:, :, :p2].contiguous()
-    ball = ops.ball_query(new_xyz, xyz, 0.25, nn)
-    conv = load_seeded(V.InterSO3Conv(cin, cout, 1, 2, 0.25, 0.03, nn), 3).cuda()
-    rk, W, Wp, bias = conv._derived()
-    if form == 32 and cin != 64:
-        # the 32x32x16 form is instantiated for 64 input channels only: this width takes the 16x16x32 form, and no operand of the other is made
-        assert ops.inter_planes_form(cin) == 16 and conv._wq32() is None and conv._wqn() is not None
-        return
-    wkw = dict(Wq32=conv._wq32()) if form == 32 else dict(Wqn=conv._wqn())
-    assert all(v is not None for v in wkw.values())
-    feats = torch.randn(b, p1, 60, cin, generator=g).cuda()
-    planes = ops.split3_planes(feats)
-    f32, (m0, r0) = ops.inter_so3conv(xyz, new_xyz, ball, feats, rk, W, Wp, bias, conv.sigma, want_stats=True)
-    new, (m1, r1) = ops.inter_so3conv(xyz, new_xyz, ball, feats, rk, W, Wp, bias, conv.sigma, want_stats=True, feats_planes=planes,
-                                      order=ops.spatial_order(new_xyz), **wkw)
-    again = ops.inter_so3conv(xyz, new_xyz, ball, feats, rk, W, Wp, bias, conv.sigma, **wkw)        # planes made on the fly, plain order
-    assert torch.equal(new, again)
-    scale = float(f32.abs().max())
-    assert float((new - f32).abs().max()) < 2e-6 * scale, float((new - f32).abs().max()) / scale
-    assert rel_err(m1.cpu().numpy(), m0.cpu().numpy()) < 2e-6 and rel_err(r1.cpu().numpy(), r0.cpu().numpy()) < 2e-6
-    ref = _inter_conv_fp64(xyz, new_xyz, ball, feats, rk, W, bias, conv.sigma)
-    e_new, e_f32 = float((new.double() - ref).abs().max()), float((f32.double() - ref).abs().max())
-    assert e_f32 < 3e-6 * scale and e_new <= 2.0 * e_f32 + 1e-7 * scale, (e_new, e_f32)
 
 
 def test_encoder_with_plane_producers_equals_encoder_without(monkeypatch):

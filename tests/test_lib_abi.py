@@ -144,6 +144,23 @@ def test_every_kernel_source_includes_the_header():
     assert exporting >= 20
 
 
+def test_every_called_name_is_declared_in_the_header():
+    """Every literal name the package passes to _lib.call() is a function the product library has (include/etch_hip.h as the product build reads it):
+    no call of a retired symbol survives on a path no GPU test reaches.  The fused block kernels are the one exception, by name: ops.pt_block_k1
+    raises (ops._need_experiments) unless the experiments library is the one loaded, and run_blocks reaches pt_block_k2 only behind it."""
+    import re
+    root = os.path.dirname(os.path.abspath(_lib.__file__))
+    declared = set(_lib.prototypes())
+    called = {}
+    for dp, _, fs in os.walk(root):
+        for f in fs:
+            if f.endswith(".py"):
+                for n in re.findall(r"\bcall\(\s*\"(etch_\w+)\"", open(os.path.join(dp, f)).read()):
+                    called.setdefault(n, os.path.join(dp, f))
+    assert len(called) >= 100, len(called)                 # the pattern still finds the package's calls
+    assert {n for n in called if n not in declared} == {"etch_pt_block_k1", "etch_pt_block_k2"}
+
+
 def test_no_hand_written_prototypes_or_pointer_helpers_in_the_package():
     import re
     root = os.path.dirname(os.path.abspath(_lib.__file__))
