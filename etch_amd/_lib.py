@@ -3,7 +3,6 @@ missing or a symbol is absent this raises, loudly.
 
 include/etch_hip.h is the one description of the C ABI: prototypes() parses it, _load() types every exported function from the parse, and
 call() is the one way the package calls the library."""
-import contextlib
 import ctypes
 import os
 import re
@@ -18,12 +17,6 @@ _lib = None
 
 class EtchHipError(RuntimeError):
     status = None             # the C function's return value, when that is what raised
-
-
-def has_experiments():
-    """True if the loaded library was built with ETCH_BUILD_EXPERIMENTS=1 (the opt-in kernels measured slower than the default path:
-    etch_pt_block_k1 / _k2)."""
-    return hasattr(lib()._cdll, "etch_pt_block_k1")
 
 
 # Every spelling of a return or parameter type in include/etch_hip.h.  Pointers of any kind travel as addresses.
@@ -42,12 +35,9 @@ def _ctype(spelling, where):
     return CTYPES[spelling]
 
 
-def prototypes(experiments=False, text=None):
-    """{name: (return ctype, [(ctype, parameter name), ...])} of every function declared in include/etch_hip.h, in header order; the
-    `#ifdef ETCH_BUILD_EXPERIMENTS` sections only on request."""
+def prototypes(text=None):
+    """{name: (return ctype, [(ctype, parameter name), ...])} of every function declared in include/etch_hip.h, in header order."""
     txt = open(HEADER).read() if text is None else text
-    if not experiments:
-        txt = re.sub(r"#ifdef ETCH_BUILD_EXPERIMENTS.*?#endif", "", txt, flags=re.S)
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     out = {}
     for ret, name, params in _PROTOTYPE.findall(txt):
@@ -61,9 +51,9 @@ def prototypes(experiments=False, text=None):
     return out
 
 
-def declared_symbols(experiments=False):
-    """Every etch_* function declared in include/etch_hip.h; the `#ifdef ETCH_BUILD_EXPERIMENTS` sections only on request."""
-    return sorted(n for n in prototypes(experiments) if n.startswith("etch_"))
+def declared_symbols():
+    """Every etch_* function declared in include/etch_hip.h."""
+    return sorted(n for n in prototypes() if n.startswith("etch_"))
 
 
 def declared_launchers():
@@ -93,7 +83,7 @@ def _load(path, how):
         raise EtchHipError(f"{path} is missing: build it with {how} (hipcc, gfx950). etch_amd has no CPU fallback.")
     cdll = ctypes.CDLL(path)
     sigs = {}
-    for name, (ret, params) in prototypes(experiments=hasattr(cdll, "etch_pt_block_k1")).items():
+    for name, (ret, params) in prototypes().items():
         fn = getattr(cdll, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = ret
         fn.argtypes = [t for t, _ in params]
@@ -107,25 +97,6 @@ def lib():
     if _lib is None:
         _lib = _load(LIB_PATH, "`python -m etch_amd.build`")
     return _lib
-
-
-EXP_LIB_PATH = os.path.join(_HERE, "lib", "libetch_hip_exp.so")
-_exp_lib = None
-
-
-@contextlib.contextmanager
-def experiments_library():
-    """Tests of the opt-in experiment kernels (measured slower than the default path, absent from the product library): every call of etch_amd
-    goes through libetch_hip_exp.so (etch_amd.build.build_experiments(), run by build()) inside the block, through the product library again after it."""
-    global _lib, _exp_lib
-    if _exp_lib is None:
-        _exp_lib = _load(EXP_LIB_PATH, "`etch_amd.build.build_experiments()`")
-    prev = lib()
-    _lib = _exp_lib
-    try:
-        yield _exp_lib
-    finally:
-        _lib = prev
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -147,10 +118,11 @@ def call(name, *args):
     for NULL; a prototype that ends in `void* stream` gets the current stream unless the caller passes one.  The tensors stay referenced until the C call
     has returned, so a temporary (`x.contiguous()`) is passed as it is.  Raises EtchHipError before the call on a wrong number of arguments and after it
     on a failed status; a host-only function (no stream) returns its count or size (negative: the same error)."""
+    L = lib()
     try:
-        fn, nparams, pointers, streamed = (_lib or lib())._sigs[name]
+        fn, nparams, pointers, streamed = L._sigs[name]
     except KeyError:
-        raise EtchHipError(f"{name} is not declared in include/etch_hip.h (or only in a section this library was built without)") from None
+        raise EtchHipError(f"{name} is not declared in include/etch_hip.h") from None
     raw = list(args)
     if streamed and len(raw) == nparams - 1:
         raw.append(stream())
@@ -160,7 +132,7 @@ def call(name, *args):
         a = raw[i]
         if a is not None and isinstance(a, _Tensor):
             raw[i] = a.data_ptr()
-    prof = _lib.profiler
+    prof = L.profiler
     try:
         status = fn(*raw) if prof is None else prof(name, tuple(raw), fn)
     except ctypes.ArgumentError as e:

@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
-OBJDIR = os.path.join(LIBDIR, "obj_exp" if os.environ.get("ETCH_BUILD_EXPERIMENTS", "0") == "1" else "obj")
+OBJDIR = os.path.join(LIBDIR, "obj")
 LIB = os.path.join(LIBDIR, "libetch_hip.so")
 ARCH = "gfx950"
 BASE = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-I", CSRC,
@@ -30,13 +30,6 @@ def hipcc():
     raise RuntimeError("hipcc not found")
 
 
-EXPERIMENTS = os.environ.get("ETCH_BUILD_EXPERIMENTS", "0") == "1"    # the opt-in kernels measured slower than the default path: the `#ifdef ETCH_BUILD_EXPERIMENTS` part of pt.hip
-
-
-EXP_OBJDIR = os.path.join(LIBDIR, "obj_exp")
-EXP_LIB = os.path.join(LIBDIR, "libetch_hip_exp.so")      # the library WITH the experiment kernels, beside the product's (tests of those kernels only)
-
-
 def sources():
     return sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
 
@@ -49,32 +42,17 @@ def _stale(target, deps):
 
 
 def build(force=False, verbose=False):
-    """libetch_hip.so: the product library (ETCH_BUILD_EXPERIMENTS=1: with the experiment kernels, linked to the same file)."""
-    return _build(OBJDIR, EXPERIMENTS, LIB, force, verbose, stamp=True)
-
-
-def build_experiments(force=False, verbose=False):
-    """libetch_hip_exp.so: every source with the experiment kernels (-DETCH_BUILD_EXPERIMENTS) as a library of its own.  The product
-    never loads it; the tests of those kernels run through it (_lib.experiments_library())."""
-    return _build(EXP_OBJDIR, True, EXP_LIB, force, verbose, stamp=False)
-
-
-def _compile_jobs(objdir, experiments, force):
+    """libetch_hip.so: every source of csrc/ compiled into lib/obj (only what is stale, unless `force`) and linked."""
+    os.makedirs(OBJDIR, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     headers.append(os.path.join(os.path.dirname(HERE), "include", "etch_hip.h"))
     cc = hipcc()
     jobs, objs = [], []
     for src in sources():
-        obj = os.path.join(objdir, src.replace(".hip", ".o"))
+        obj = os.path.join(OBJDIR, src.replace(".hip", ".o"))
         objs.append(obj)
         if force or _stale(obj, [os.path.join(CSRC, src)] + headers + [os.path.abspath(__file__)]):
-            jobs.append([cc] + BASE + (["-DETCH_BUILD_EXPERIMENTS"] if experiments else []) + EXTRA.get(src, []) + ["-c", os.path.join(CSRC, src), "-o", obj])
-    return cc, jobs, objs
-
-
-def _build(objdir, experiments, lib, force, verbose, stamp):
-    os.makedirs(objdir, exist_ok=True)
-    cc, jobs, objs = _compile_jobs(objdir, experiments, force)
+            jobs.append([cc] + BASE + EXTRA.get(src, []) + ["-c", os.path.join(CSRC, src), "-o", obj])
 
     def run(cmd):
         if verbose:
@@ -87,20 +65,9 @@ def _build(objdir, experiments, lib, force, verbose, stamp):
 
     with ThreadPoolExecutor(max_workers=4) as ex:
         list(ex.map(run, jobs))
-    if not stamp:
-        if force or jobs or _stale(lib, objs):
-            run([cc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib] + objs)
-        return lib
-    # both variants (default / ETCH_BUILD_EXPERIMENTS=1) link to the same libetch_hip.so from their own object directories: the variant last linked is
-    # recorded next to the library, and a request for the other one relinks even when no source changed
-    stamp = lib + ".variant"
-    variant = "experiments" if experiments else "default"
-    linked = open(stamp).read().strip() if os.path.exists(stamp) else None
-    if force or jobs or _stale(lib, objs) or linked != variant:
-        run([cc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib] + objs)
-        with open(stamp, "w") as f:
-            f.write(variant + "\n")
-    return lib
+    if force or jobs or _stale(LIB, objs):
+        run([cc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB] + objs)
+    return LIB
 
 
 if __name__ == "__main__":

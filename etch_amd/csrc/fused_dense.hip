@@ -219,13 +219,9 @@ __global__ void __launch_bounds__(512) linear_relu_dot_bx_kernel(long R, int G, 
 #pragma unroll
                     for (int pl = 0; pl < 3; ++pl) a[i][pl] = *reinterpret_cast<const bf16x8*>(Xp + pl * PLANE + (rh * (FD_ROWS / 2) + i * 16 + fr) * SB + t * 32 + fg * 8);
                 // smallest cross products first; term-major: consecutive MFMAs are independent
-#if defined(LRD_ABL) && (LRD_ABL & 1)
-#define FD_T(PA, PB) _Pragma("unroll") for (int i = 0; i < RT; ++i) asm volatile("" :: "v"(a[i][PA]), "v"(b[0][PB]), "v"(b[1][PB]));
-#else
 #define FD_T(PA, PB) _Pragma("unroll") for (int i = 0; i < RT; ++i) { \
         acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][PA], b[0][PB], acc[i][0], 0, 0, 0); \
         acc[i][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][PA], b[1][PB], acc[i][1], 0, 0, 0); }
-#endif
                 FD_T(2, 0) FD_T(0, 2) FD_T(1, 1) FD_T(1, 0) FD_T(0, 1) FD_T(0, 0)
 #undef FD_T
             }
@@ -240,11 +236,7 @@ __global__ void __launch_bounds__(512) linear_relu_dot_bx_kernel(long R, int G, 
                 for (int i = 0; i < RT; ++i)
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-#if defined(LRD_ABL) && (LRD_ABL & 2)
-                        const float s = acc[i][s2][q] + bs + ww;       // timing experiment: no row sums
-#else
                         const float s = fd_row_sum16(fmaxf(acc[i][s2][q] + bs, 0.f) * ww);
-#endif
                         if (fr == ((i * 4 + q) & 15)) rp[i * 16 + fg * 4 + q] = s;    // spread the stores over the row's lanes
                     }
             }

@@ -139,11 +139,7 @@ __global__ void __launch_bounds__(256, BX ? INTER_BX_WPE(CIN, COUT) : 2) inter_s
         a = a < NA ? a : NA - 1;
         const float* Fa = Fb + (size_t)a * CIN + (it_ % NCC) * CCH;         // wave-uniform base + 32-bit lane offset
 #pragma unroll
-#ifdef BX_ABL_NOGATHER
-        for (int s = 0; s < 4; ++s) dst[s] = *reinterpret_cast<const VecT*>(Fa + (unsigned)(VEC * fr) + 0 * noff[16 * t + 4 * fg + s]);      // timing experiment: every gather hits one row
-#else
         for (int s = 0; s < 4; ++s) dst[s] = *reinterpret_cast<const VecT*>(Fa + (noff[16 * t + 4 * fg + s] + (unsigned)(VEC * fr)));
-#endif
     };
     auto issue_rk = [&](int a) {
         a = a < NA ? a : NA - 1;
@@ -183,7 +179,6 @@ __global__ void __launch_bounds__(256, BX ? INTER_BX_WPE(CIN, COUT) : 2) inter_s
                 issue_rk(j < 3 ? a + 1 : ((it + 1) / NCC) * 16 + wave * 4);                // next anchor's kernel points
             }
             {
-                constexpr int dummy = 0; (void)dummy;
                 const int nc = cs + PD;
                 if (nc < NCS) issue(it, nc, ring[nc % NRING]);
                 else if (it < 4 * NCC - 1) issue(it + 1, nc - NCS, ring[nc % NRING]);     // wave-uniform
@@ -198,12 +193,8 @@ __global__ void __launch_bounds__(256, BX ? INTER_BX_WPE(CIN, COUT) : 2) inter_s
 #pragma unroll
                     for (int mi = 0; mi < MT1; ++mi) {
                         const float av = cur[s][mi];
-#ifdef BX_ABL_NOS1MFMA
-                        asm volatile("" :: "v"(w0), "v"(w1), "v"(av));      // timing experiment: step 1 without its MFMAs
-#else
                         acc[mi][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0, av, acc[mi][0], 0, 0, 0);      // D[k][c]: weights as the row operand
                         acc[mi][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1, av, acc[mi][1], 0, 0, 0);
-#endif
                     }
                 }
             }
@@ -285,11 +276,7 @@ __global__ void __launch_bounds__(256, BX ? INTER_BX_WPE(CIN, COUT) : 2) inter_s
                     const float* xr = &X1s[fr * S + t * 32 + fg * 8];
                     bf16x8 bq[3];
                     split3_pack8(*reinterpret_cast<const float4*>(xr), *reinterpret_cast<const float4*>(xr + 4), bq[0], bq[1], bq[2]);
-#ifdef BX_ABL_SAMEW
-                    const int tg = 0;       // timing experiment: every chunk reads the same fragments (L1 hits)
-#else
                     const int tg = (cc * HALVES + h) * (KH / 32) + t;
-#endif
                     constexpr int MB = MT2 > 2 ? 2 : MT2;       // o tiles at a time: 2 x 3 planes x 4 registers of W fragments
 #pragma unroll
                     for (int m0 = 0; m0 < MT2; m0 += MB) {
@@ -298,11 +285,7 @@ __global__ void __launch_bounds__(256, BX ? INTER_BX_WPE(CIN, COUT) : 2) inter_s
                         for (int mt = 0; mt < MB; ++mt)
 #pragma unroll
                             for (int pl = 0; pl < 3; ++pl) aq[mt][pl] = Wq[(((size_t)tg * MT2 + m0 + mt) * 3 + pl) * 64 + lane];
-#ifdef BX_ABL_NOMFMA
-#define BX_TERM(PA, PB) _Pragma("unroll") for (int mt = 0; mt < MB; ++mt) asm volatile("" :: "v"(aq[mt][PA]), "v"(bq[PB]));
-#else
 #define BX_TERM(PA, PB) _Pragma("unroll") for (int mt = 0; mt < MB; ++mt) y[m0 + mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[mt][PA], bq[PB], y[m0 + mt], 0, 0, 0);
-#endif
                         BX_TERM(2, 0) BX_TERM(0, 2) BX_TERM(1, 1) BX_TERM(1, 0) BX_TERM(0, 1) BX_TERM(0, 0)
 #undef BX_TERM
                     }
@@ -783,7 +766,6 @@ __global__ void __launch_bounds__(256) intra_so3conv32_kernel(int npts_total, in
         for (int i = 0; i < SPT; ++i) {
             const int q = i % PF;
             const int t = tap * SPT + i;
-            constexpr int dummy = 0; (void)dummy;
             const bool tail = LAST && i + PF - 1 >= SPT;               // compile-time per unrolled step: the last PF - 1 steps issue no load
             if (!tail) avq[(q + PF - 1) % PF] = intra32_wload(&Wp[(((size_t)(t + PF - 1) * MT + mt) * 64 + lane) * 4]);
             float4 bv[WPP];

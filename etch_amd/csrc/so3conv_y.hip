@@ -80,11 +80,7 @@ struct H32Step2 {
     f32x4 ra[RD][2];
     __device__ __forceinline__ void issue(int i, const bf16x8* __restrict__ Wq, int wave, int lane) {
         const int h = i / NB, c = (i % NB) / MT2, mt = i % MT2;
-#ifdef Y_ABL_WCACHED
-        const char* b0 = reinterpret_cast<const char*>(Wq) + (size_t)(i & 1) * 2 * 1024;      // timing experiment: every W fragment is one of two cached ones
-#else
         const char* b0 = reinterpret_cast<const char*>(Wq) + ((size_t)(h * (KH / 16) + wave + 4 * c) * MT2 + mt) * 2 * 1024;
-#endif
         const unsigned vo = (unsigned)lane * 16u;
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl) x_wload_s(ra[i % RD][pl], vo, b0, pl);
@@ -258,11 +254,7 @@ __global__ void __launch_bounds__(256, INTER_Y_WPE(CIN)) inter_so3conv_y_kernel(
     unsigned roff[NCH][NRB];
     auto read_roff = [&](int t, const unsigned* tab) {       // row offsets of chunk position t from a slot of the offset table
 #pragma unroll
-#ifdef Y_ABL_SAMEROW
-        for (int rb = 0; rb < NRB; ++rb) roff[t][rb] = 0 * tab[32 * t + RPI * rb + rl] + pieceoff;     // timing experiment: every gather hits one row (cache-resident)
-#else
         for (int rb = 0; rb < NRB; ++rb) roff[t][rb] = tab[32 * t + RPI * rb + rl] + pieceoff;
-#endif
     };
 #pragma unroll
     for (int t = 0; t < NCH; ++t) read_roff(t, noffs);
@@ -312,20 +304,13 @@ __global__ void __launch_bounds__(256, INTER_Y_WPE(CIN)) inter_so3conv_y_kernel(
     // are clamped by the loaders: harmless repeats of anchor 59, the pipeline stays branch-free)
     auto anchor_of = [&](int q) { const int qq = q & (NG * NJ - 1); const int a = (qq / NJ) * AG + wave * NJ + (qq % NJ); return a < NA ? a : NA - 1; };
     auto issue_kp = [&](int q, bf16x8 (&dst)[2]) {
-#ifdef Y_ABL_NOPRE
-        return;
-#endif
         const bf16x8* src = kq + (size_t)anchor_of(q) * 128 + lane;
         dst[0] = src[0]; dst[1] = src[64];
     };
     // piece k = (plane, row block) of chunk gl of the pass that starts at global step G0 (gl >= NSTEP: the next pass, whose rows are `base`'s)
     auto load_piece = [&](int G0, int gl, const char* base, int k, f32x4& dst) {
         const char* src = base + (size_t)anchor_of((G0 + gl) / NCH) * ROWB + roff[gl % NCH][k % NRB] + (k / NRB) * CIN * 2;
-#ifdef Y_ABL_NOLOAD
-        asm volatile("" : "=v"(dst) : "v"(src));
-#else
         dst = *reinterpret_cast<const f32x4*>(src);
-#endif
     };
     auto stage_piece = [&](int k, const f32x4& v) { *reinterpret_cast<f32x4*>(stg_w + (k / NRB) * PLB + (k % NRB) * 1024) = v; };
     auto read_frag = [&](int r, f16x8 (&dst)[NT32][2][2]) {      // fragment r = (K step h2, plane, channel tile), in the order the MFMAs want them
@@ -336,14 +321,8 @@ __global__ void __launch_bounds__(256, INTER_Y_WPE(CIN)) inter_so3conv_y_kernel(
     };
     const f32x16 zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     auto gen_pre = [&](int t, const bf16x8 (&kpa)[2]) {          // pre-activations of one (anchor, chunk): P[v] = row 8 (v / 4) + 4 kg + v % 4 of column kp
-#ifdef Y_ABL_NOPRE
-        f32x16 P = zero16;
-        asm volatile("" : "+v"(P) : "v"(kpa[0]));
-        return P;
-#else
         f32x16 P = __builtin_amdgcn_mfma_f32_32x32x16_bf16(geo_r[GEO_RES ? t : 0][0], kpa[0], zero16, 0, 0, 0);
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(geo_r[GEO_RES ? t : 0][1], kpa[1], P, 0, 0, 0);
-#endif
     };
     // clamp to [0, 1] (the weight's mathematical range) + two-plane fp16 split of the pair k = (P[2 k], P[2 k + 1]) as a software pipeline over the
     // pairs: tick tau runs stage 1 of pair tau (clamp), stage 2 of pair tau - 1 (h = fp16 pair), stage 3 of pair tau - 2 (l = w - h:
@@ -356,10 +335,6 @@ __global__ void __launch_bounds__(256, INTER_Y_WPE(CIN)) inter_so3conv_y_kernel(
     struct Split { float w[16]; unsigned h[8]; float l[16]; };
     constexpr int NTICK = 11;
     auto split_tick = [&](int k, const f32x16& P, Split& S_, y_u32x4 (&aw)[2][2]) {
-#ifdef Y_ABL_NOSPLIT
-        if (k == 0) asm volatile("" :: "v"(P));
-        return;
-#endif
         if (k < 8) {
             S_.w[2 * k] = __builtin_amdgcn_fmed3f(P[2 * k], 0.0f, 1.0f);
             S_.w[2 * k + 1] = __builtin_amdgcn_fmed3f(P[2 * k + 1], 0.0f, 1.0f);
@@ -371,14 +346,9 @@ __global__ void __launch_bounds__(256, INTER_Y_WPE(CIN)) inter_so3conv_y_kernel(
         }
         if (k >= 2 && k < 10) {
             const int pr = k - 2;
-#ifdef Y_NO_FMA_MIX
-            const f16x2 h = __builtin_bit_cast(f16x2, S_.h[pr]);
-            S_.l[2 * pr] = S_.w[2 * pr] - (float)h[0]; S_.l[2 * pr + 1] = S_.w[2 * pr + 1] - (float)h[1];
-#else
             // l = fp16-half * (-1) + w in one instruction (exact: w - h has at most 13 significant bits)
             asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(S_.l[2 * pr]) : "v"(S_.h[pr]), "v"(S_.w[2 * pr]));
             asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(S_.l[2 * pr + 1]) : "v"(S_.h[pr]), "v"(S_.w[2 * pr + 1]));
-#endif
         }
         if (k >= 3) {
             const int pr = k - 3;
@@ -536,24 +506,13 @@ __global__ void __launch_bounds__(256, INTER_Y_WPE(CIN)) inter_so3conv_y_kernel(
                 for (int i = 0; i < NMF; ++i) {
                     {
                         const int ct = i % NT32, term = (i / NT32) % 3, h2 = i / (3 * NT32);
-#ifndef Y_ABL_NOMFMA1
                         acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf[sp][ct][h2][PB[term]], __builtin_bit_cast(f16x8, aws[sp][h2][PA[term]]),
                                                                          (t == 0 && i < NT32) ? zero16 : acc[ct], 0, 0, 0);
-#else
-                        asm volatile("" :: "v"(aws[sp][h2][PA[term]]), "v"(bf[sp][ct][h2][PB[term]]));
-                        if (t == 0 && i < NT32) acc[ct] = zero16;
-#endif
                     }
                     // chunk g + 1: ring -> staging tile (two pieces per slot), then its fragments (one per slot); the freed registers take chunk g + 1 + D
-#ifndef Y_ABL_NOSTAGE
                     if (i < NW) { stage_piece(2 * i, ring[rs][2 * i]); stage_piece(2 * i + 1, ring[rs][2 * i + 1]); }
-#else
-                    if (i < NW) asm volatile("" :: "v"(ring[rs][2 * i]), "v"(ring[rs][2 * i + 1]));
-#endif
                     if (i >= NW && i < NW + NL) load_piece(G0, g + 1 + D, g + 1 + D >= NSTEP ? Fb_np : Fb, i - NW, ring[rs][i - NW]);
-#ifndef Y_ABL_NOFRAG
                     if (i >= NW && i < NW + NF) read_frag(i - NW, bf[sp ^ 1]);
-#endif
                     // the next step's weights
                     if (NT32 == 2) { if (i >= 1 && i < 1 + NTICK) split_tick(i - 1, P, S_, aws[sp ^ 1]); }
                     else { split_tick(2 * i, P, S_, aws[sp ^ 1]); if (2 * i + 1 < NTICK) split_tick(2 * i + 1, P, S_, aws[sp ^ 1]); }
@@ -574,14 +533,12 @@ __global__ void __launch_bounds__(256, INTER_Y_WPE(CIN)) inter_so3conv_y_kernel(
         for (int mt = 0; mt < MT2; ++mt)
 #pragma unroll
             for (int v = 0; v < 16; ++v) y[mt][v] = 0.f;
-#ifndef Y_ABL_NOSTEP2
         H32Step2<CIN, COUT, Y_PAD(CIN), Y_S2_DEPTH(CIN)> s2;
         const bf16x8* Wq_g = Wq;
         asm volatile("" : "+s"(Wq_g));
         s2.prime(Wq_g, wave, lane);
         __syncthreads();
         s2.template half<0>(y, X1s, Wq_g, wave, lane);
-#endif
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
@@ -589,9 +546,7 @@ __global__ void __launch_bounds__(256, INTER_Y_WPE(CIN)) inter_so3conv_y_kernel(
             for (int q4 = 0; q4 < NKR / 4; ++q4) x1_store(j, q4, keep[j][4 * q4], keep[j][4 * q4 + 1], keep[j][4 * q4 + 2], keep[j][4 * q4 + 3]);
         }
         __syncthreads();
-#ifndef Y_ABL_NOSTEP2
         s2.template half<1>(y, X1s, Wq_g, wave, lane);
-#endif
         __syncthreads();                                // every wave finished reading X1s: the partial table may overwrite it
         // y[mt][v] = 2^kw(o) Y[o = 32 mt + 8 (v / 4) + 4 kg + v % 4][anchor column = lane % 32]
 #pragma unroll

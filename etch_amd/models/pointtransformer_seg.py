@@ -1,8 +1,6 @@
 """MI355X counterpart of /root/reference/src/models/pointtransformer_seg.py: identical module tree and
 state-dict keys; Linear(+BN+ReLU) layers run as one fp32-MFMA GEMM with a fused epilogue, the kNN
 vector-attention core is one kernel per layer, FPS / kNN are the HIP index kernels."""
-import os
-
 import torch
 import torch.nn as nn
 
@@ -207,19 +205,6 @@ class PointTransformerBlock(nn.Module):
         self.relu = nn.ReLU(inplace=True)
         self._d = _Derived()
 
-    # run_blocks: True = the K1 / K2 fused kernels (2 launches per block, blocks of a level chained: 1 + b launches per level); False = 4
-    # kernels per block.  Default OFF: measured on the bench workload the fused form is 1.0 - 3.4x SLOWER per level (a 16-point tile
-    # re-streams every c x c weight from L2 and its GEMM chain is latency-bound; profiles/r03_pt_block_fusion.txt).  ETCH_PT_FUSED=1 enables it.
-    fused = os.environ.get("ETCH_PT_FUSED", "0") == "1"       # (needs a library built with ETCH_BUILD_EXPERIMENTS=1: ops.pt_block_k1 raises otherwise)
-
-    def _fused_params(self):
-        """Argument sets of the fused block kernels (etch_pt_block_k1 / _k2), rebuilt when a parameter changes."""
-        bns = (self.bn1, self.bn2, self.bn3)
-        f = self._d.get([t for m in bns for t in (m.weight, m.bias, m.running_mean, m.running_var)], lambda: [fold_bn(m) for m in bns])
-        wqkv, bqkv, params, mlp = self.transformer2._derived()
-        return dict(k1=(self.linear1.weight.detach(), f[0][0], f[0][1], wqkv, bqkv), attn=params + [f[1][0], f[1][1]], w2=mlp[0],
-                    w3=self.linear3.weight.detach(), s3=f[2][0], t3=f[2][1])
-
     def forward(self, pxo):
         p, x, o = pxo
         bns = (self.bn1, self.bn2, self.bn3)
@@ -231,26 +216,10 @@ class PointTransformerBlock(nn.Module):
 
 
 def run_blocks(blocks, pxo):
-    """A run of consecutive PointTransformerBlocks of one level (pointtransformer_seg.py:101-122 each) with the fused block kernels:
-    1 + len(blocks) launches (K1 of the first block; K2 of every block, carrying the next block's K1) instead of 4 per block.  Falls back
-    to the blocks' own forward for shapes the fused kernels are not built for."""
-    blocks = list(blocks)
+    """A run of consecutive PointTransformerBlocks of one level (pointtransformer_seg.py:101-122 each)."""
     p, x, o = pxo
-    if not blocks:
-        return [p, x, o]
-    b0 = blocks[0]
-    c, ns = b0.transformer2.out_planes, b0.transformer2.nsample
-    if not (PointTransformerBlock.fused and x.is_cuda and (c, ns) in ops.PT_BLOCK_SHAPES and x.shape[1] == c and
-            all(b.transformer2.out_planes == c and b.transformer2.nsample == ns for b in blocks)):
-        for b in blocks:
-            p, x, o = b([p, x, o])
-        return [p, x, o]
-    idx = pointops.knnquery(ns, p, p, o, o)[0]
-    der = [b._fused_params() for b in blocks]
-    qkv = ops.pt_block_k1(x, *der[0]["k1"])
-    for i, d in enumerate(der):
-        nxt = der[i + 1]["k1"] if i + 1 < len(der) else None
-        x, qkv = ops.pt_block_k2(p, qkv, c, idx, d["attn"], ns, d["w2"], d["w3"], d["s3"], d["t3"], x, next_k1=nxt)
+    for b in blocks:
+        p, x, o = b([p, x, o])
     return [p, x, o]
 
 
@@ -287,7 +256,7 @@ class _PointTransformerBase(nn.Module):
             x0 = torch.cat((p0, x0) + ((x0.new_zeros((x0.shape[0], pad)),) if pad else ()), 1)
         else:
             x0 = p0
-        enc = lambda m, pxo_: run_blocks(m[1:], m[0](pxo_))            # TransitionDown, then the level's blocks (fused kernels)
+        enc = lambda m, pxo_: run_blocks(m[1:], m[0](pxo_))            # TransitionDown, then the level's blocks
         p1, x1, o1 = enc(self.enc1, [p0, x0, o0])
         p2, x2, o2 = enc(self.enc2, [p1, x1, o1])
         p3, x3, o3 = enc(self.enc3, [p2, x2, o2])

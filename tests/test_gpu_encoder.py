@@ -340,13 +340,3 @@ def test_intra_conv_weight_stationary_split_matches_the_fp32_kernel_and_fp64(c, 
     ref = torch.einsum("bpatc,oct->bpao", gathered, W3) + bias.double()
     e_new, e_f32 = float((new.double() - ref).abs().max()), float((f32.double() - ref).abs().max())
     assert e_f32 < 3e-6 * scale and e_new <= 2.0 * e_f32 + 1e-7 * scale, (e_new, e_f32)
-
-
-@pytest.fixture
-def experiments():
-    """The opt-in experiment kernels (measured slower than the default path) live in their own library, libetch_hip_exp.so (built by build()):
-    the test runs through it, the product library is back in place afterwards."""
-    from etch_amd import _lib
-    with _lib.experiments_library():
-        assert _lib.has_experiments()
-        yield

@@ -132,7 +132,6 @@ def test_pt_block_vs_fp64(c, ns, n):
     linear3 + bn3 + residual + ReLU through res_mode = 1) against oracle pt_block."""
     from etch_amd.models import pointtransformer_seg as P
     from oracle import stage1 as S1
-    assert not P.PointTransformerBlock.fused
     segs = [5, (n - 5) // 2, n - 5 - (n - 5) // 2]
     p, x, o = Y.cloud(segs, c, 7 * c + n)
     mod = P.PointTransformerBlock(c, c, 8, ns)

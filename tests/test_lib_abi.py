@@ -74,35 +74,24 @@ NAME_PATTERNS = (r"\bint\s+etch_\w+\(", r"\bvoid\s+\w+_launcher\(",
                  r"\blong\s+etch_\w+\(")           # the one size that does not fit an int: etch_smpl_lm_split_workspace_bytes
 
 
-def _header_text(experiments):
-    import re
-    txt = open(_lib.HEADER).read()
-    if not experiments:
-        txt = re.sub(r"#ifdef ETCH_BUILD_EXPERIMENTS.*?#endif", "", txt, flags=re.S)
-    return re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-
-
 def test_parse_finds_every_prototype_and_maps_every_type():
     import ctypes
     import re
 
     import pytest
-    counts = {}
-    for experiments in (False, True):
-        protos = _lib.prototypes(experiments=experiments)
-        txt = _header_text(experiments)
-        counts[experiments] = len(protos)
-        assert len(protos) == sum(len(re.findall(p, txt)) for p in NAME_PATTERNS)
-        assert len(re.findall(NAME_PATTERNS[2], txt)) == 1
-        known = set(_lib.CTYPES.values())
-        for name, (ret, params) in protos.items():
-            assert ret in (None, ctypes.c_int, ctypes.c_long), name
-            assert (ret is None) == name.endswith("_launcher"), name
-            for ctype, pname in params:
-                assert ctype in known and ctype is not None and pname.isidentifier(), (name, pname)
-        assert sorted(n for n in protos if n.startswith("etch_")) == _lib.declared_symbols(experiments)
-        assert sorted(n for n in protos if n.endswith("_launcher")) == _lib.declared_launchers()
-    assert counts[True] > counts[False] >= 150
+    protos = _lib.prototypes()
+    txt = re.sub(r"/\*.*?\*/", "", open(_lib.HEADER).read(), flags=re.S)
+    assert len(protos) == sum(len(re.findall(p, txt)) for p in NAME_PATTERNS)
+    assert len(re.findall(NAME_PATTERNS[2], txt)) == 1
+    known = set(_lib.CTYPES.values())
+    for name, (ret, params) in protos.items():
+        assert ret in (None, ctypes.c_int, ctypes.c_long), name
+        assert (ret is None) == name.endswith("_launcher"), name
+        for ctype, pname in params:
+            assert ctype in known and ctype is not None and pname.isidentifier(), (name, pname)
+    assert sorted(n for n in protos if n.startswith("etch_")) == _lib.declared_symbols()
+    assert sorted(n for n in protos if n.endswith("_launcher")) == _lib.declared_launchers()
+    assert len(protos) >= 150
     ret, params = _lib.prototypes()["etch_linear"]
     assert ret is ctypes.c_int and len(params) == 21 and params[4] == (ctypes.c_long, "ldx") and params[-1] == (ctypes.c_void_p, "stream")
     assert _lib.prototypes()["etch_smpl_lm_split_workspace_bytes"][0] is ctypes.c_long
@@ -125,13 +114,13 @@ def _exported(path):
 
 
 def test_header_and_libraries_agree_on_the_symbol_set():
-    for path, experiments in ((B.build(), False), (B.build_experiments(), True)):
-        assert _exported(path) == set(_lib.prototypes(experiments=experiments)), path
+    path = B.build()
+    assert _exported(path) == set(_lib.prototypes()), path
 
 
 def test_every_kernel_source_includes_the_header():
     import re
-    names = set(_lib.prototypes(experiments=True))
+    names = set(_lib.prototypes())
     csrc = os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "csrc")
     exporting = 0
     for f in sorted(os.listdir(csrc)):
@@ -145,9 +134,8 @@ def test_every_kernel_source_includes_the_header():
 
 
 def test_every_called_name_is_declared_in_the_header():
-    """Every literal name the package passes to _lib.call() is a function the product library has (include/etch_hip.h as the product build reads it):
-    no call of a retired symbol survives on a path no GPU test reaches.  The fused block kernels are the one exception, by name: ops.pt_block_k1
-    raises (ops._need_experiments) unless the experiments library is the one loaded, and run_blocks reaches pt_block_k2 only behind it."""
+    """Every literal name the package passes to _lib.call() is a function the library has (declared in include/etch_hip.h): no call of a
+    retired symbol survives on a path no GPU test reaches."""
     import re
     root = os.path.dirname(os.path.abspath(_lib.__file__))
     declared = set(_lib.prototypes())
@@ -158,7 +146,7 @@ def test_every_called_name_is_declared_in_the_header():
                 for n in re.findall(r"\bcall\(\s*\"(etch_\w+)\"", open(os.path.join(dp, f)).read()):
                     called.setdefault(n, os.path.join(dp, f))
     assert len(called) >= 100, len(called)                 # the pattern still finds the package's calls
-    assert {n for n in called if n not in declared} == {"etch_pt_block_k1", "etch_pt_block_k2"}
+    assert {n for n in called if n not in declared} == set()
 
 
 def test_no_hand_written_prototypes_or_pointer_helpers_in_the_package():
