@@ -1340,13 +1340,19 @@ __global__ void __launch_bounds__(256) smpl_lbs_kernel(LbsConsts C, int NJ, int 
 }
 
 // ---------------------------------------------------------------------------------------------- markers
+// float -> unsigned that keeps the order of torch.max / torch.topk: every NaN, of either sign, is the one greatest key (above +inf; NaNs tie),
+// -0 and +0 share a key, everything else in numeric order.  Integer tests only, so the denormal mode has no say.  The smallest key is -inf's,
+// 0x007FFFFF: no value maps to 0.
 __device__ __forceinline__ unsigned sortable_f32(float f) {
-    const unsigned u = __float_as_uint(f);
+    unsigned u = __float_as_uint(f);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0xFFFFFFFFu;
+    if ((u << 1) == 0u) u = 0u;
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-// One wave per (scan, label): top-3 confidences among the points carrying that label (ties -> lower index),
-// weights conf^20, weighted centre.  labels int64 (argmax output), conf (B,K,1).
+// One wave per (scan, label): top-3 confidences among the points carrying that label (a NaN confidence is the greatest, as for torch.topk, and
+// makes the centre NaN; -0 == +0; ties -> lower index), weights conf^20, weighted centre.  labels int64 (argmax output), conf (B,K,1).
+// A real point's key is never 0 (sortable_f32 > 0), so 0 can stand for an empty place in the lists.
 __global__ void __launch_bounds__(64) get_markers_kernel(int K, int M, const float* __restrict__ pts, const long long* __restrict__ labels,
                                                          const float* __restrict__ conf, float* __restrict__ markers,
                                                          float* __restrict__ valid_f, unsigned char* __restrict__ valid_b) {
@@ -1414,7 +1420,7 @@ __global__ void __launch_bounds__(64) marker_status_kernel(int M, const float* _
     if (lane == 0) status[b] = (bad ? 1 : 0) | (any ? 0 : 2);
 }
 
-// labels[r] = argmax_g logits[r, g] (first maximum), int64 like torch.max
+// labels[r] = argmax_g logits[r, g], int64 like torch.max: the first maximum, -0 == +0, a NaN of either sign above +inf (the first NaN wins)
 __global__ void __launch_bounds__(256) argmax_rows_kernel(long R, int G, const float* __restrict__ logits, long long* __restrict__ out) {
     const int lane = threadIdx.x & 63;
     for (long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6); r < R; r += (long)gridDim.x * 4) {

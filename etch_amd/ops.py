@@ -893,7 +893,7 @@ def softmax_dot(logits, v):
 
 # ------------------------------------------------------------------ stage 2
 def argmax_rows(logits):
-    """(..., G) float32 -> (...) int64, first maximum (torch.max semantics)."""
+    """(..., G) float32 -> (...) int64, first maximum (torch.max semantics: -0 == +0, any NaN greatest, the first NaN wins)."""
     _need(logits, torch.float32, "logits")
     G = logits.shape[-1]
     R = logits.numel() // G

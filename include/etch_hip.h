@@ -546,7 +546,8 @@ int etch_instnorm_act_backward(int b, int rows, int C, const float* x, const flo
 
 /* ---- stage 2: markers + SMPL Levenberg-Marquardt fit ------------------------------------------------------ */
 
-/* torch.max(part_labels, -1) of predict_smpl (src/inference_demo.py:52-53): logits (R,G) -> int64 labels (R). */
+/* torch.max(part_labels, -1) of predict_smpl (src/inference_demo.py:52-53): logits (R,G) -> int64 labels (R).
+ * The first maximum; -0 == +0; a NaN of either sign is the greatest value and the first NaN wins. */
 int etch_argmax_rows(long R, int G, const float* logits, long long* out, void* stream);
 
 /* pred_inner_points = points - direction * magnitude / scale_magnitude (src/inference_demo.py:58-59): (n,3),(n,3),(n) -> (n,3). */
@@ -554,7 +555,8 @@ int etch_inner_points(long n, const float* pts, const float* dir, const float* m
 
 /* get_markers (src/models/fit_SMPL.py:17-62): pts (B,K,3), labels (B,K) i64, conf (B,K,1) -> markers (B,M,3),
  * valid as float (B,M) and/or as bool bytes (B,M) (either may be NULL).  Per (scan,label): top-3 confidences,
- * weights conf^20, weighted centre; empty label -> zeros + invalid. */
+ * weights conf^20, weighted centre; empty label -> zeros + invalid.  The confidences are ordered as by torch.topk where that defines an
+ * order (a NaN of either sign greatest -- the marker is then NaN and etch_marker_status flags it -- and -0 == +0); equal ones go to the lower index. */
 int etch_get_markers(int B, int K, int M, const float* pts, const long long* labels, const float* conf, float* markers,
                      float* valid_f, unsigned char* valid_b, void* stream);
 
