@@ -1,0 +1,341 @@
+"""Raw point clouds as input: cleaning and evening out a cloud a scanner, photogrammetry or a depth sensor delivered, and
+handing it to the pipeline.
+
+    pack(list_of_arrays) -> Cloud                              a ragged batch of (n,3) arrays as depth.Cloud (index = the original row)
+    knn_mean_distance(cloud, k, cell=None, brute=False)        mean distance of every point to its k nearest neighbours (exact grid kNN)
+    remove_statistical_outliers(cloud, k=16, ratio=2.0)        keep m_i <= mean + ratio * std over the cloud
+    remove_radius_outliers(cloud, radius, min_neighbours)      keep the points with enough neighbours within radius
+    voxel_downsample(cloud, voxel)                             one centroid per occupied cell, in spatial (ix, iy, iz) order
+    prepare(cloud, N, keys, voxel=, stat=, radius=)            filters, voxel grid, bounding-box centre, stratified pick: the network's input
+
+    python -m etch_amd.cloud --cloud_path scan.ply [--voxel V] [--outlier_k K --outlier_ratio R] [--outlier_radius r --outlier_min_neighbours m]
+
+Neighbours are rows of the same cloud only.  The kernels (csrc/cloud_filter.hip) are exact and defined in fp64; there is no CPU path."""
+import argparse
+import math
+import os
+
+import numpy as np
+
+from . import _lib
+from .depth import Cloud
+
+STATUS_NONFINITE, STATUS_RANGE, STATUS_EMPTY = 1, 2, 4
+MAX_K = 32
+
+
+def pack(arrays, device="cuda"):
+    """A list of (n,3) arrays -> Cloud(points (M,3) fp64, index (M) int32 = the row inside its own array, offsets (B+1) int32, count (B)
+    int32, depth None) on the device.  An array may be empty; non-finite coordinates are reported by the call that meets them."""
+    import torch
+    arrays = [np.asarray(a) for a in ([arrays] if isinstance(arrays, np.ndarray) and arrays.ndim == 2 else arrays)]
+    if not arrays:
+        raise ValueError("no cloud to pack")
+    for k, a in enumerate(arrays):
+        if a.ndim != 2 or a.shape[1] != 3 or a.dtype.kind not in "fiu":
+            raise ValueError(f"cloud {k}: needs an (n,3) array of numbers, got {a.dtype} {a.shape}")
+    n = np.array([len(a) for a in arrays], np.int64)
+    if n.sum() >= 2 ** 31 // 3:
+        raise ValueError("the batch is too large for 32-bit offsets: filter it in parts")
+    dev = torch.device(device)
+    pts = np.ascontiguousarray(np.concatenate([a.astype(np.float64) for a in arrays]))
+    off = np.concatenate([[0], np.cumsum(n)]).astype(np.int32)
+    idx = np.concatenate([np.arange(m, dtype=np.int32) for m in n])
+    return Cloud(torch.from_numpy(pts).to(dev), torch.from_numpy(idx).to(dev), torch.from_numpy(off).to(dev), torch.from_numpy(n.astype(np.int32)).to(dev), None)
+
+
+def _offsets(cloud):
+    """The host's copy of a cloud's offsets, checked: bad offsets raise before any launch."""
+    o = cloud.offsets.cpu().numpy().astype(np.int64)
+    M = cloud.points.shape[0]
+    if cloud.points.dim() != 2 or cloud.points.shape[1] != 3 or o.ndim != 1 or len(o) < 2:
+        raise ValueError(f"a cloud is points (M,3) and offsets (B+1) with B >= 1, got {tuple(cloud.points.shape)} and {tuple(cloud.offsets.shape)}")
+    if o[0] != 0 or (np.diff(o) < 0).any() or o[-1] > M:
+        raise ValueError(f"offsets must start at 0, not decrease and end within the {M} rows, got {o.tolist() if len(o) <= 9 else o[:9].tolist()}")
+    if cloud.index.shape != (M,):
+        raise ValueError(f"index must be ({M},), got {tuple(cloud.index.shape)}")
+    return o
+
+
+def _check_k(k):
+    if int(k) != k or not 1 <= int(k) <= MAX_K:
+        raise ValueError(f"k must be an integer in 1 .. {MAX_K}, got {k}")
+    return int(k)
+
+
+def _check_positive(x, name):
+    if not (float(x) > 0.0 and math.isfinite(float(x))):
+        raise ValueError(f"{name} must be positive and finite, got {x}")
+    return float(x)
+
+
+def _raise_status(what, status):
+    status = np.asarray(status)
+    if status.any():
+        b = int(np.flatnonzero(status)[0])
+        s = int(status[b])
+        why = ("a coordinate is not finite" if s & STATUS_NONFINITE else "an axis has more than 2^21 voxels: the voxel size is too small for the cloud's extent"
+               if s & STATUS_RANGE else "the cloud has no point")
+        raise _lib.EtchHipError(f"{what}: cloud {b}: {why}")
+
+
+def _ops(cloud):
+    import torch
+
+    from . import ops
+    return torch, ops, torch.cuda.device(cloud.points.device)
+
+
+def knn_mean_distance(cloud, k, cell=None, brute=False):
+    """m_i = the mean distance from row i to its min(k, n - 1) nearest other rows of its cloud (0 where the cloud has one row), (M) fp64 on the
+    device.  The cell size is internal (ops.cloud_cell_grid states the rule); cell= overrides it and brute=True scans every cloud whole for every
+    query -- the bits are the same in every form.  ValueError for k outside 1 .. 32 or bad offsets, before any launch; EtchHipError naming the
+    cloud that holds a non-finite coordinate, after the one status readback."""
+    k = _check_k(k)
+    if cell is not None:
+        _check_positive(cell, "cell")
+    o = _offsets(cloud)
+    torch, ops, ctx = _ops(cloud)
+    with ctx:
+        mean, status = ops.cloud_knn_mean(cloud.points, cloud.offsets, k, cell=cell, brute=brute)
+    _raise_status("knn_mean_distance", status.cpu().numpy())
+    return mean[:int(o[-1])]
+
+
+def radius_neighbour_count(cloud, radius, brute=False):
+    """c_i = the number of other rows of its cloud within `radius` of row i (d2 <= radius * radius), (M) int32 on the device."""
+    radius = _check_positive(radius, "radius")
+    o = _offsets(cloud)
+    torch, ops, ctx = _ops(cloud)
+    with ctx:
+        count, status = ops.cloud_radius_count(cloud.points, cloud.offsets, radius, brute=brute)
+    _raise_status("radius_neighbour_count", status.cpu().numpy())
+    return count[:int(o[-1])]
+
+
+def _compact(ops, cloud, keep):
+    kept, offsets, index, points = ops.cloud_compact(cloud.points, cloud.index, cloud.offsets, keep)
+    return Cloud(points, index, offsets, kept, None)
+
+
+def _trim(cloud, total):
+    cloud.points, cloud.index = cloud.points[:total], cloud.index[:total]
+    return cloud
+
+
+def _stat(ops, cloud, k, ratio):
+    mean, status = ops.cloud_knn_mean(cloud.points, cloud.offsets, k)
+    keep, stats = ops.cloud_stat_keep(mean, cloud.offsets, ratio, status)
+    return keep, stats, status
+
+
+def _check_stat(k, ratio):
+    if not math.isfinite(float(ratio)):
+        raise ValueError(f"ratio must be finite, got {ratio}")
+    return _check_k(k), float(ratio)
+
+
+def _check_radius(radius, min_neighbours):
+    if int(min_neighbours) != min_neighbours or int(min_neighbours) < 0:
+        raise ValueError(f"min_neighbours must be a non-negative integer, got {min_neighbours}")
+    return _check_positive(radius, "radius"), int(min_neighbours)
+
+
+def remove_statistical_outliers(cloud, k=16, ratio=2.0, return_stats=False):
+    """Statistical outlier removal per cloud: keep_i = m_i <= mu + ratio s with mu, s the mean and the (n - 1) standard deviation of the m_i of
+    knn_mean_distance.  -> (Cloud of the kept rows in row order, keep (M) bool on the device) [, stats (B,2) fp64 = mu, s]."""
+    k, ratio = _check_stat(k, ratio)
+    o = _offsets(cloud)
+    torch, ops, ctx = _ops(cloud)
+    with ctx:
+        keep, stats, status = _stat(ops, cloud, k, ratio)
+        out = _compact(ops, cloud, keep)
+        host = torch.cat([status, out.offsets]).cpu().numpy()              # the one readback
+    B = len(o) - 1
+    _raise_status("remove_statistical_outliers", host[:B])
+    out = _trim(out, int(host[-1]))
+    keep = keep[:int(o[-1])].bool()
+    return (out, keep, stats) if return_stats else (out, keep)
+
+
+def remove_radius_outliers(cloud, radius, min_neighbours):
+    """Radius outlier removal: keep the rows with at least min_neighbours other rows of their cloud within radius.  -> (Cloud, keep (M) bool)."""
+    radius, min_neighbours = _check_radius(radius, min_neighbours)
+    o = _offsets(cloud)
+    torch, ops, ctx = _ops(cloud)
+    with ctx:
+        count, status = ops.cloud_radius_count(cloud.points, cloud.offsets, radius)
+        keep = (count >= min_neighbours).to(torch.int32)
+        out = _compact(ops, cloud, keep)
+        host = torch.cat([status, out.offsets]).cpu().numpy()
+    B = len(o) - 1
+    _raise_status("remove_radius_outliers", host[:B])
+    return _trim(out, int(host[-1])), keep[:int(o[-1])].bool()
+
+
+def _voxel(ops, cloud, voxel):
+    offsets, centroid, count, lowest, cell, status = ops.cloud_voxel_grid(cloud.points, cloud.offsets, voxel)
+    out = Cloud(centroid, lowest, offsets, offsets[1:] - offsets[:-1], None)
+    out.cell = cell
+    return out, count, status
+
+
+def voxel_downsample(cloud, voxel):
+    """Voxel-grid down-sampling: cell = floor((p - o) / voxel) with o the cloud's bounding-box minimum; one output row per occupied cell in
+    ascending (ix, iy, iz) order = the centroid of its rows.  -> (Cloud whose index is the cell's lowest row and whose .cell (., 3) int32 are
+    the cell coordinates, count (.) int32 = the rows of each cell).  EtchHipError naming the cloud where an axis has more than 2^21 cells."""
+    voxel = _check_positive(voxel, "voxel")
+    o = _offsets(cloud)
+    torch, ops, ctx = _ops(cloud)
+    with ctx:
+        out, count, status = _voxel(ops, cloud, voxel)
+        host = torch.cat([status, out.offsets]).cpu().numpy()
+    B = len(o) - 1
+    _raise_status("voxel_downsample", host[:B])
+    total = int(host[-1])
+    out.cell = out.cell[:total]
+    return _trim(out, total), count[:total]
+
+
+def prepare(cloud, N, keys, voxel=None, stat=None, radius=None, center=True):
+    """A raw cloud -> the network's input: the statistical filter (stat = (k, ratio)), the radius filter (radius = (r, min_neighbours)), the voxel
+    grid (voxel = the cell size), ops.bbox_center of what is left, and depth.pick's stratified pick of N points per cloud under `keys` -- with
+    a voxel grid the pick walks the cells in spatial order.  -> points (B,N,3) fp32, centres (B,3) fp64 (None without center), the cleaned
+    Cloud, which also carries .keep ((M) bool over the given rows: what the filters kept) and .stages (rows per cloud after each stage, a dict of
+    numpy arrays).  One readback for all stages; errors as in the single calls."""
+    from . import depth, mesh_io
+    o = _offsets(cloud)
+    B = len(o) - 1
+    if stat is not None:
+        stat = _check_stat(*stat)
+    if radius is not None:
+        radius = _check_radius(*radius)
+    if voxel is not None:
+        voxel = _check_positive(voxel, "voxel")
+    mesh_io._keys(keys, B)
+    if int(N) < 0:
+        raise ValueError("N must not be negative")
+    torch, ops, ctx = _ops(cloud)
+    dev = cloud.points.device
+    words, names, cur = [], [], cloud
+    keep = torch.ones((cloud.points.shape[0],), dtype=torch.bool, device=dev)
+    with ctx:
+        if stat is not None:
+            k1, _, status = _stat(ops, cur, *stat)
+            keep = k1.bool()
+            cur = _compact(ops, cur, k1)
+            words += [status, cur.offsets]
+            names.append("statistical")
+        if radius is not None:
+            count, status = ops.cloud_radius_count(cur.points, cur.offsets, radius[0])
+            k2 = (count >= radius[1]).to(torch.int32)
+            if stat is not None:                                     # a kept row's rank among the kept rows is its row in the compacted cloud
+                rank = (torch.cumsum(keep.to(torch.int64), 0) - 1).clamp_(min=0)
+                keep = keep & k2.bool()[rank]
+            else:
+                keep = k2.bool()
+            cur = _compact(ops, cur, k2)
+            words += [status, cur.offsets]
+            names.append("radius")
+        if voxel is not None:
+            cur, _, status = _voxel(ops, cur, voxel)
+            words += [status, cur.offsets]
+            names.append("voxel")
+        c = ops.bbox_center(cur.points, cur.offsets) if center else None
+        p64, p32, pixel, pstatus = depth._pick(cur, N, keys, c, dev)
+        host = torch.cat(words + [pstatus]).cpu().numpy()            # the one readback
+    stages = {"input": np.diff(o)}
+    for i, name in enumerate(names):
+        part = host[i * (2 * B + 1):(i + 1) * (2 * B + 1)]
+        _raise_status(f"prepare ({name})", part[:B])
+        stages[name] = np.diff(part[B:].astype(np.int64))
+    if host[-B:].any():
+        raise _lib.EtchHipError(f"prepare: cloud {int(np.flatnonzero(host[-B:])[0])}: no point is left to pick from")
+    total = int(host[-B - 1]) if names else int(o[-1])
+    if names:
+        if hasattr(cur, "cell"):
+            cur.cell = cur.cell[:total]
+        cur = _trim(cur, total)
+    else:
+        cur = Cloud(cloud.points[:total], cloud.index[:total], cloud.offsets, cloud.count, None)
+    cur.keep, cur.stages, cur.picked = keep[:int(o[-1])], stages, pixel             # picked (B,N) int32: the index of every picked row
+    return p32, c, cur
+
+
+# ---------------------------------------------------------------------------------------------------------------- the command
+def add_filter_flags(p):
+    """The cleaning flags python -m etch_amd.cloud and python -m etch_amd.depth share; all default to off."""
+    p.add_argument("--outlier_k", type=int, default=0, help="statistical outlier removal: neighbours per point (1 .. 32); 0 = off")
+    p.add_argument("--outlier_ratio", type=float, default=2.0, help="statistical outlier removal: keep m_i <= mean + RATIO * std")
+    p.add_argument("--outlier_radius", type=float, default=0.0, help="radius outlier removal: the radius in metres; 0 = off")
+    p.add_argument("--outlier_min_neighbours", type=int, default=2, help="radius outlier removal: neighbours a point needs within the radius")
+
+
+def check_filter_flags(p, a):
+    if a.outlier_k and not 1 <= a.outlier_k <= MAX_K:
+        p.error(f"--outlier_k must lie in 1 .. {MAX_K}")
+    if not math.isfinite(a.outlier_ratio):
+        p.error("--outlier_ratio must be finite")
+    if a.outlier_radius < 0.0 or not math.isfinite(a.outlier_radius) or a.outlier_min_neighbours < 0:
+        p.error("--outlier_radius must be positive and finite, --outlier_min_neighbours not negative")
+
+
+def filter_args(a):
+    """The flags as prepare()'s stat= and radius=."""
+    return ((a.outlier_k, a.outlier_ratio) if a.outlier_k else None, (a.outlier_radius, a.outlier_min_neighbours) if a.outlier_radius > 0.0 else None)
+
+
+def build_parser():
+    from .inference_demo import add_flags
+    p = argparse.ArgumentParser(prog="python -m etch_amd.cloud", description="Fit SMPL to a raw point cloud", conflict_handler="resolve")
+    p.add_argument("--cloud_path", type=str, required=True, help="the cloud: .ply, .obj (vertices), .npy / .npz ((M,3)), .xyz / .txt (three columns)")
+    p.add_argument("--voxel", type=float, default=0.0, help="voxel-grid down-sampling before the pick: the cell size in metres; 0 = off")
+    add_filter_flags(p)
+    add_flags(p)
+    p.add_argument("--chamfer_refine", type=str, nargs="?", const="partial", default="none", choices=["none", "both", "partial", "clutter"],
+                   help="refine the body against the whole cleaned cloud after the marker fit; without a value: partial")
+    return p
+
+
+def parse_args(argv=None):
+    p = build_parser()
+    a = p.parse_args(argv)
+    check_filter_flags(p, a)
+    if a.voxel < 0.0 or not math.isfinite(a.voxel):
+        p.error("--voxel must be positive and finite")
+    if a.num_point < 1:
+        p.error("--num_point must be at least 1")
+    return a
+
+
+def main(argv=None):
+    from . import inference_demo as demo
+    from . import mesh_io
+    from .models.fit_SMPL import Mesh
+    args = parse_args(argv)
+    raw = mesh_io.read_cloud(args.cloud_path)                         # a malformed file raises before the model is loaded
+    model = demo.prepare_common(args)
+    export = Mesh.export
+    if getattr(args, "ingest", "host") == "device":
+        export = mesh_io.write_obj
+    stat, radius = filter_args(args)
+    p32, c, clean = prepare(pack([raw], args.device), args.num_point, [args.seed], voxel=args.voxel if args.voxel > 0.0 else None, stat=stat, radius=radius)
+    points, center, cleaned = p32[0].cpu().numpy(), c[0].cpu().numpy(), clean.points.cpu().numpy()
+    name = os.path.splitext(os.path.basename(args.cloud_path))[0]
+    stages = {f"rows_{k}": v for k, v in clean.stages.items()}
+    np.savez(os.path.join(args.output_folder, f"{name}_cloud.npz"), keep=clean.keep.cpu().numpy(), center=center, points=points,
+             removed=np.int64(len(raw) - int(clean.keep.sum())), rows_output=np.array([len(cleaned)]), **stages)
+    if args.chamfer_refine != "none":
+        demo._refine_and_save(args, model, points, Mesh(cleaned - center, np.zeros((0, 3), np.int64)), center, name, export)
+    else:
+        pred, info = demo.predict_smpl(args, model, points, args.gender)
+        final = pred.copy()
+        final.vertices = pred.vertices + center
+        export(final, os.path.join(args.output_folder, f"{name}_pred_smpl.obj"))
+        np.savez(os.path.join(args.output_folder, f"{name}_output_smpl_info.npz"), body_pose=info[0][0, :21, :], hand_pose=info[0][0, 21:23, :],
+                 betas=info[1][0], global_orient=info[2][0], transl=info[3][0], joints=info[4][0])
+    print(f"Predicted SMPL mesh, smpl info and the cleaning report saved under {args.output_folder}")
+
+
+if __name__ == "__main__":
+    main()

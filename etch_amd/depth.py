@@ -10,6 +10,7 @@
 
     python -m etch_amd.depth --depth_path D.npy --intrinsics FX FY CX CY [...]      fit a real depth frame
     python -m etch_amd.depth --scan_path S.obj --view_azimuth DEG [...]             fit a virtual view of a mesh
+    ... --outlier_k K --outlier_ratio R / --outlier_radius r --outlier_min_neighbours m   drop flying pixels first (etch_amd.cloud, section 19)
 
 The kernels are bit-defined; there is no CPU path."""
 import argparse
@@ -328,6 +329,8 @@ def build_parser():
     p.add_argument("--view_fov", type=float, default=45.0, help="vertical field of view in degrees")
     p.add_argument("--view_size", type=int, nargs=2, metavar=("H", "W"), default=(512, 512))
     add_flags(p)
+    from .cloud import add_filter_flags
+    add_filter_flags(p)                                          # flying pixels: clean the back-projected cloud before the pick (section 19)
     # the same flag with a default mode: a single view is a partial scan, so a bare --chamfer_refine is the one-sided scan -> body refinement
     p.add_argument("--chamfer_refine", type=str, nargs="?", const="partial", default="none", choices=["none", "both", "partial", "clutter"],
                    help="refine the body against the whole visible cloud after the marker fit; without a value: partial")
@@ -359,6 +362,8 @@ def parse_args(argv=None):
             p.error("--view_elevation must lie inside (-90, 90), --view_distance be positive, --view_fov inside (0, 180), --view_size at least 1 1")
     if a.num_point < 1:
         p.error("--num_point must be at least 1")
+    from .cloud import check_filter_flags
+    check_filter_flags(p, a)
     return a
 
 
@@ -367,7 +372,10 @@ def view_points(args, device):
     float64 numpy (uncentred), the depth map (H,W) float64 numpy, the Camera, picked pixels (N), name."""
     import torch
 
+    from . import cloud as C
     from . import mesh_io, ops
+    stat, radius = C.filter_args(args) if hasattr(args, "outlier_k") else (None, None)
+    filtered = stat is not None or radius is not None
     if args.depth_path is not None:
         frame = load_depth(args.depth_path, args.depth_scale)
         R, t = load_extrinsics(args.extrinsics) if args.extrinsics else (None, None)
@@ -375,20 +383,31 @@ def view_points(args, device):
         near, far = args.depth_range if args.depth_range is not None else (0.0, math.inf)
         depth = torch.from_numpy(frame[None]).to(device)
         cloud = _unproject(depth, cam.row()[None], near, far, device)
-        with torch.cuda.device(device):
-            c = ops.bbox_center(cloud.points, cloud.offsets)
-        p64, p32, pixel, status = _pick(cloud, args.num_point, [args.seed], c, device)
-        host = torch.cat([status, cloud.offsets]).cpu().numpy()
-        if host[0]:
-            raise _lib.EtchHipError(f"{args.depth_path}: no pixel of the frame is valid (check --depth_scale and --depth_range)")
-        pts, vis = p32, cloud.points[:int(host[-1])]
+        if filtered:
+            # the outlier filters run on the back-projected cloud; its index (the pixel) travels through the compaction
+            pts, c, clean = C.prepare(cloud, args.num_point, [args.seed], stat=stat, radius=radius)
+            vis, pixel = clean.points, clean.picked
+        else:
+            with torch.cuda.device(device):
+                c = ops.bbox_center(cloud.points, cloud.offsets)
+            p64, p32, pixel, status = _pick(cloud, args.num_point, [args.seed], c, device)
+            host = torch.cat([status, cloud.offsets]).cpu().numpy()
+            if host[0]:
+                raise _lib.EtchHipError(f"{args.depth_path}: no pixel of the frame is valid (check --depth_scale and --depth_range)")
+            pts, vis = p32, cloud.points[:int(host[-1])]
         name = os.path.splitext(os.path.basename(args.depth_path))[0]
     else:
         mesh = mesh_io.read_obj(args.scan_path)
         cam = Camera.orbit(bbox_mid(mesh.vertices), args.view_distance, math.radians(args.view_azimuth), math.radians(args.view_elevation), args.view_fov,
                            int(args.view_size[0]), int(args.view_size[1]))
-        pv = partial_view_points([mesh], [cam], args.num_point, [args.seed], center=True, device=device)
-        pts, c, vis, depth, pixel = pv.points, pv.centers, pv.cloud.points, pv.cloud.depth, pv.pixel
+        if filtered:
+            (depth, _, _, _, rstatus, _), rows, dev = _render([mesh], [cam], None, False, 0.05, device)
+            _raise_status("render", rstatus.cpu().numpy())
+            pts, c, clean = C.prepare(_unproject(depth, rows, 0.05, math.inf, dev), args.num_point, [args.seed], stat=stat, radius=radius)
+            vis, pixel = clean.points, clean.picked
+        else:
+            pv = partial_view_points([mesh], [cam], args.num_point, [args.seed], center=True, device=device)
+            pts, c, vis, depth, pixel = pv.points, pv.centers, pv.cloud.points, pv.cloud.depth, pv.pixel
         name = os.path.splitext(os.path.basename(args.scan_path))[0]
     return (pts[0].cpu().numpy(), c[0].cpu().numpy(), vis.cpu().numpy(), depth[0].cpu().numpy(), cam, pixel[0].cpu().numpy(), name)
 

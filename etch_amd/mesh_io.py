@@ -5,8 +5,11 @@ sampler (csrc/mesh_sample.hip).  Opt-in counterparts of inference_demo.load_obj,
     read_objs(paths) -> [Mesh]       the same on a thread pool (ctypes releases the GIL during the parse)
     write_obj(mesh, path)            the bytes Mesh.export writes
     sample_surface(meshes, N, keys)  N area-weighted points on each mesh of a ragged batch, one call, on the device
+    read_ply(path) -> PlyData        PLY 1.0 (ascii, binary little / big endian): vertices, fanned faces, normals and colours when present
+    write_ply(points_or_mesh, path)  binary (default) or ascii; a float64 round trip is exact
+    read_cloud(path) -> (M,3)        the points of a .ply, .obj, .npy, .npz, .xyz or .txt file
 
-The reader and the writer are host code and need no GPU; the sampler has no CPU path."""
+The readers and the writers are host code and need no GPU; the sampler has no CPU path."""
 import ctypes
 import os
 from concurrent.futures import ThreadPoolExecutor
@@ -77,6 +80,283 @@ def write_obj(mesh, path):
     data = format_obj(mesh)
     with open(path, "wb") as fh:
         fh.write(data)
+
+
+# ---------------------------------------------------------------------------------------------------------------- PLY and raw clouds (host code)
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2", "int": "i4",
+              "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+_PLY_MAX_COUNT = 2 ** 31 - 1
+
+
+class PlyData:
+    """What read_ply returns: vertices (V,3) float64, faces (F,3) int64 (fanned polygons; (0,3) where the file has none), normals (V,3) float64
+    or None, colors (V,3 or 4) in the file's type or None."""
+
+    def __init__(self, vertices, faces, normals=None, colors=None):
+        self.vertices, self.faces, self.normals, self.colors = vertices, faces, normals, colors
+
+
+def _ply_type(name, path):
+    if name not in _PLY_TYPES:
+        raise ValueError(f"{path}: unknown type `{name}` in the header")
+    return _PLY_TYPES[name]
+
+
+def _ply_header(data, path):
+    """-> format, [(element name, count, [(property name, type) or (property name, count type, item type)])], offset of the body."""
+    if not data.startswith(b"ply"):
+        raise ValueError(f"{path}: not a PLY file (no `ply` magic)")
+    end = data.find(b"end_header")
+    nl = data.find(b"\n", end) if end >= 0 else -1
+    if end < 0 or nl < 0:
+        raise ValueError(f"{path}: the header has no end_header line")
+    fmt, elements = None, []
+    for line in data[:end].decode("ascii", "replace").splitlines()[1:]:
+        tok = line.split()
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "format":
+            if len(tok) != 3 or tok[1] not in ("ascii", "binary_little_endian", "binary_big_endian") or tok[2] != "1.0":
+                raise ValueError(f"{path}: unsupported format line `{line.strip()}`")
+            fmt = tok[1]
+        elif tok[0] == "element":
+            try:
+                count = int(tok[2])
+            except (IndexError, ValueError):
+                raise ValueError(f"{path}: element line `{line.strip()}`: the count does not fit") from None
+            if not 0 <= count <= _PLY_MAX_COUNT:
+                raise ValueError(f"{path}: element {tok[1]}: the count {count} does not fit")
+            elements.append((tok[1], count, []))
+        elif tok[0] == "property":
+            if not elements:
+                raise ValueError(f"{path}: a property line in front of the first element")
+            if len(tok) == 5 and tok[1] == "list":
+                ct, it = _ply_type(tok[2], path), _ply_type(tok[3], path)
+                if ct[0] == "f":
+                    raise ValueError(f"{path}: list property {tok[4]}: the count type must be an integer type")
+                elements[-1][2].append((tok[4], ct, it))
+            elif len(tok) == 3:
+                elements[-1][2].append((tok[2], _ply_type(tok[1], path)))
+            else:
+                raise ValueError(f"{path}: malformed property line `{line.strip()}`")
+        else:
+            raise ValueError(f"{path}: unknown header line `{line.strip()}`")
+    if fmt is None:
+        raise ValueError(f"{path}: the header has no format line")
+    return fmt, elements, nl + 1
+
+
+class _PlyBinary:
+    """Reads elements off a binary body, in file order."""
+
+    def __init__(self, data, pos, endian, path):
+        self.data, self.pos, self.e, self.path = data, pos, endian, path
+
+    def _need(self, nbytes, name):
+        if self.pos + nbytes > len(self.data):
+            raise ValueError(f"{self.path}: truncated body: element {name} needs {nbytes} more bytes, {len(self.data) - self.pos} are left")
+
+    def scalars(self, name, count, props):
+        dt = np.dtype([(f"f{i}", self.e + t) for i, (_, t) in enumerate(props)])
+        self._need(count * dt.itemsize, name)
+        rows = np.frombuffer(self.data, dt, count, self.pos)
+        self.pos += count * dt.itemsize
+        return {p[0]: rows[f"f{i}"] for i, p in enumerate(props)}
+
+    def lists(self, name, count, props):
+        """The general walk: -> {list property name: [array per row]}; scalar properties between the lists are skipped."""
+        out = {p[0]: [] for p in props if len(p) == 3}
+        if count and len(props) == 1:                # the usual face element: try rows of one length first
+            pname, ct, it = props[0]
+            self._need(np.dtype(ct).itemsize, name)
+            c = int(np.frombuffer(self.data, self.e + ct, 1, self.pos)[0])
+            dt = np.dtype([("n", self.e + ct), ("i", self.e + it, (max(c, 0),))])
+            if c > 0 and self.pos + count * dt.itemsize <= len(self.data):
+                rows = np.frombuffer(self.data, dt, count, self.pos)
+                if (rows["n"] == c).all():
+                    self.pos += count * dt.itemsize
+                    out[pname] = rows["i"]
+                    return out
+        for _ in range(count):
+            for p in props:
+                if len(p) == 2:
+                    self._need(np.dtype(p[1]).itemsize, name)
+                    self.pos += np.dtype(p[1]).itemsize
+                    continue
+                pname, ct, it = p
+                self._need(np.dtype(ct).itemsize, name)
+                c = int(np.frombuffer(self.data, self.e + ct, 1, self.pos)[0])
+                self.pos += np.dtype(ct).itemsize
+                if c < 0:
+                    raise ValueError(f"{self.path}: element {name}: a list count of {c} does not fit")
+                self._need(c * np.dtype(it).itemsize, name)
+                out[pname].append(np.frombuffer(self.data, self.e + it, c, self.pos))
+                self.pos += c * np.dtype(it).itemsize
+        return out
+
+
+class _PlyAscii:
+    def __init__(self, data, pos, path):
+        self.tok, self.pos, self.path = data[pos:].split(), 0, path
+
+    def _take(self, n, name):
+        if self.pos + n > len(self.tok):
+            raise ValueError(f"{self.path}: truncated body: element {name} needs {n} more values, {len(self.tok) - self.pos} are left")
+        out = self.tok[self.pos:self.pos + n]
+        self.pos += n
+        return out
+
+    def _convert(self, tokens, t, name):
+        try:
+            a = np.array(tokens, dtype="S").astype("U")
+            return a.astype("f8").astype(t) if t[0] == "f" else np.array([int(x) for x in a], dtype="i8" if t != "u8" else "u8").astype(t)
+        except (ValueError, OverflowError):
+            raise ValueError(f"{self.path}: element {name}: a value is no number of its type") from None
+
+    def scalars(self, name, count, props):
+        flat = np.array(self._take(count * len(props), name), dtype=object).reshape(count, len(props))
+        return {p[0]: self._convert(list(flat[:, i]), p[1], name) for i, p in enumerate(props)}
+
+    def lists(self, name, count, props):
+        out = {p[0]: [] for p in props if len(p) == 3}
+        for _ in range(count):
+            for p in props:
+                if len(p) == 2:
+                    self._take(1, name)
+                    continue
+                c = int(self._convert(self._take(1, name), "i8", name)[0])
+                if c < 0:
+                    raise ValueError(f"{self.path}: element {name}: a list count of {c} does not fit")
+                out[p[0]].append(self._convert(self._take(c, name), p[2], name))
+        return out
+
+
+def _fan(rows, nv, path):
+    """Index lists -> (F,3) int64 triangles, polygons fanned (i0, ik, ik+1) and shorter rows dropped as read_obj does; every index checked."""
+    if isinstance(rows, np.ndarray):
+        polys = rows.astype(np.int64)
+        tris = np.stack([np.repeat(polys[:, :1], polys.shape[1] - 2, 1), polys[:, 1:-1], polys[:, 2:]], 2).reshape(-1, 3) if polys.shape[1] >= 3 \
+            else np.zeros((0, 3), np.int64)
+    else:
+        out = []
+        for r in rows:
+            r = r.astype(np.int64)
+            if len(r) >= 3:
+                out.append(np.stack([np.full(len(r) - 2, r[0]), r[1:-1], r[2:]], 1))
+        tris = np.concatenate(out) if out else np.zeros((0, 3), np.int64)
+    if tris.size and (tris.min() < 0 or tris.max() >= nv):
+        bad = tris[(tris < 0) | (tris >= nv)][0]
+        raise ValueError(f"{path}: a face index {int(bad)} is out of range [0, {nv})")
+    return np.ascontiguousarray(tris)
+
+
+def parse_ply(data, path="<buffer>"):
+    data = bytes(data)
+    fmt, elements, pos = _ply_header(data, path)
+    rd = _PlyAscii(data, pos, path) if fmt == "ascii" else _PlyBinary(data, pos, "<" if fmt == "binary_little_endian" else ">", path)
+    vert, face_rows = None, None
+    for name, count, props in elements:
+        if any(len(p) == 3 for p in props):
+            got = rd.lists(name, count, props)
+            if name == "face":
+                key = next((k for k in ("vertex_indices", "vertex_index") if k in got), None)
+                if key is None:
+                    raise ValueError(f"{path}: element face has no vertex_indices list")
+                it = next(p[2] for p in props if p[0] == key)
+                if it[0] == "f":
+                    raise ValueError(f"{path}: element face: vertex indices must be of an integer type")
+                face_rows = got[key]
+        else:
+            got = rd.scalars(name, count, props) if props else {}
+        if name == "vertex":
+            vert = got
+    if vert is None:
+        raise ValueError(f"{path}: no element vertex")
+    for a in "xyz":
+        if a not in vert:
+            raise ValueError(f"{path}: element vertex has no property {a} (missing {a})")
+    pick = lambda names: np.stack([np.asarray(vert[n]) for n in names], 1) if all(n in vert for n in names) else None
+    v = np.ascontiguousarray(pick("xyz").astype(np.float64))
+    normals = pick(("nx", "ny", "nz"))
+    colors = pick(("red", "green", "blue", "alpha")) if "alpha" in vert else pick(("red", "green", "blue"))
+    faces = _fan(face_rows, len(v), path) if face_rows is not None else np.zeros((0, 3), np.int64)
+    return PlyData(v, faces, None if normals is None else normals.astype(np.float64), colors)
+
+
+def read_ply(path):
+    """A PLY 1.0 file (ascii, binary_little_endian, binary_big_endian) -> PlyData.  Element vertex: scalar properties in any order and of any
+    PLY type; x y z are required and widen to float64 exactly, nx ny nz and red green blue [alpha] are returned when present, everything else
+    is skipped.  Element face (optional): a list property vertex_indices or vertex_index of any integer types, polygons fanned as read_obj
+    fans them.  Other elements are skipped, lists included.  ValueError naming the file and the defect on a malformed file."""
+    with open(path, "rb") as fh:
+        return parse_ply(fh.read(), str(path))
+
+
+def format_ply(points_or_mesh, binary=True):
+    v = getattr(points_or_mesh, "vertices", points_or_mesh)
+    f = getattr(points_or_mesh, "faces", None)
+    v = np.asarray(v)
+    if v.ndim != 2 or v.shape[1] != 3 or v.dtype.kind not in "fiu":
+        raise ValueError(f"write_ply: points must be (M,3) numbers, got {v.dtype} {v.shape}")
+    t = "float" if v.dtype == np.float32 else "double"
+    v = np.ascontiguousarray(v, np.float32 if t == "float" else np.float64)
+    f = np.zeros((0, 3), np.int64) if f is None else np.asarray(f)
+    if f.ndim != 2 or f.shape[1] != 3 or (len(f) and (f.min() < 0 or f.max() >= len(v))):
+        raise ValueError("write_ply: faces must be (F,3) indices into the vertices")
+    head = [b"ply", b"format binary_little_endian 1.0" if binary else b"format ascii 1.0", b"element vertex %d" % len(v)]
+    head += [b"property %s %s" % (t.encode(), a) for a in (b"x", b"y", b"z")]
+    if len(f):
+        head += [b"element face %d" % len(f), b"property list uchar int vertex_indices"]
+    head = b"\n".join(head + [b"end_header"]) + b"\n"
+    if binary:
+        body = v.astype("<" + v.dtype.str[1:]).tobytes()
+        if len(f):
+            rows = np.empty(len(f), np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
+            rows["n"], rows["i"] = 3, f
+            body += rows.tobytes()
+    else:
+        body = "".join(f"{repr(float(a))} {repr(float(b))} {repr(float(c))}\n" for a, b, c in v.astype(np.float64)).encode()
+        body += "".join(f"3 {int(a)} {int(b)} {int(c)}\n" for a, b, c in f).encode()
+    return head + body
+
+
+def write_ply(points_or_mesh, path, binary=True):
+    """Points (M,3) or a mesh (vertices, faces) as PLY: float32 points stay `float`, everything else is written as `double`, so a float64
+    round trip is exact in both forms (the ascii form writes the shortest text that reads back to the same double)."""
+    data = format_ply(points_or_mesh, binary)
+    with open(path, "wb") as fh:
+        fh.write(data)
+
+
+def read_cloud(path):
+    """The points of a file as (M,3) float64: .ply, .obj (its vertices), .npy / .npz (an (M,3) array; a .npz holds one array, or one named
+    `points`) and .xyz / .txt (three columns, further columns ignored)."""
+    ext = os.path.splitext(str(path))[1].lower()
+    if ext == ".ply":
+        p = read_ply(path).vertices
+    elif ext == ".obj":
+        p = read_obj(path).vertices
+    elif ext == ".npy":
+        p = np.load(path)
+    elif ext == ".npz":
+        with np.load(path) as z:
+            names = list(z.keys())
+            if "points" not in names and len(names) != 1:
+                raise ValueError(f"{path}: holds {names}; name the cloud `points`")
+            p = z["points" if "points" in names else names[0]]
+    elif ext in (".xyz", ".txt"):
+        try:
+            p = np.loadtxt(path, dtype=np.float64, ndmin=2, comments="#")
+        except ValueError as e:
+            raise ValueError(f"{path}: {e}") from None
+        if p.ndim == 2 and p.shape[1] >= 3:
+            p = p[:, :3]
+    else:
+        raise ValueError(f"{path}: a cloud is a .ply, .obj, .npy, .npz, .xyz or .txt file")
+    p = np.asarray(p)
+    if p.ndim != 2 or p.shape[1] != 3 or p.dtype.kind not in "fiu":
+        raise ValueError(f"{path}: a cloud is an (M,3) array of numbers, got {p.dtype} {p.shape}")
+    return np.ascontiguousarray(p, np.float64)
 
 
 def pack_meshes(meshes):

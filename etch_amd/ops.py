@@ -2023,3 +2023,111 @@ def depth_pick(offsets, index, points, keys, num_points, center=None):
     if NV:
         _lib.call("etch_depth_pick", int(NV), N, offsets, index, points, keys, center, p64, p32, pixel, status)
     return p64, p32, pixel, status
+
+
+# ------------------------------------------------------------------ raw point clouds (csrc/cloud_filter.hip)
+CLOUD_MAX_K = 32
+
+
+def _cloud_args(points, offsets, what):
+    _need(points, torch.float64, "points"), _need(offsets, torch.int32, "offsets")
+    if points.dim() != 2 or points.shape[1] != 3 or offsets.dim() != 1 or offsets.numel() < 2:
+        raise _lib.EtchHipError(f"{what}: points must be (M,3) and offsets (B+1) with B >= 1, got {tuple(points.shape)} and {tuple(offsets.shape)}")
+    if points.shape[0] >= 2 ** 31 // 3:
+        raise _lib.EtchHipError(f"{what}: the batch is too large for 32-bit offsets: filter it in parts")
+    return offsets.numel() - 1, points.shape[0]
+
+
+def cloud_cell_grid(points, offsets, mode, k=1, cell=0.0, sort=True):
+    """etch_cloud_cell_keys and the stable sort of the rows by (cloud, cell key): mode 0 = kNN (cell 0 = the rule of the header), 1 = radius
+    (cell = r), 2 = voxel.  -> grid (B,4) fp64, status (B) int32, and with sort: sorted_points (M,3), sorted_keys (M) int64, order (M) int32
+    (None without: a brute-force query needs the status alone)."""
+    B, M = _cloud_args(points, offsets, "cloud_cell_grid")
+    dev = points.device
+    grid = torch.empty((B, 4), dtype=torch.float64, device=dev)
+    keys = torch.empty((M,), dtype=torch.int64, device=dev)
+    cloud = torch.empty((M,), dtype=torch.int32, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    _lib.call("etch_cloud_cell_keys", int(B), int(M), int(mode), int(k), float(cell), points, offsets, grid, keys, cloud, status)
+    if not sort:
+        return grid, status, None, None, None
+    skeys, order = torch.sort(keys, stable=True)
+    if B > 1:                                                   # a second stable sort, by cloud: every cloud's rows are one segment again
+        _, second = torch.sort(cloud[order], stable=True)
+        order, skeys = order[second], skeys[second]
+    return grid, status, points[order].contiguous(), skeys.contiguous(), order.to(torch.int32).contiguous()
+
+
+def cloud_knn_mean(points, offsets, k, cell=None, brute=False):
+    """Mean distance of every row to its min(k, n - 1) nearest other rows of its cloud (0 for a cloud of one row), exact for any cell size.
+    -> mean (M) fp64 (zeros for a cloud with a status bit), status (B) int32, both still on the device."""
+    B, M = _cloud_args(points, offsets, "cloud_knn_mean")
+    if not 1 <= int(k) <= CLOUD_MAX_K:
+        raise _lib.EtchHipError(f"cloud_knn_mean: k must lie in 1 .. {CLOUD_MAX_K}, got {k}")
+    if cell is not None and not (float(cell) > 0.0 and math.isfinite(float(cell))):
+        raise _lib.EtchHipError(f"cloud_knn_mean: cell must be positive and finite, got {cell}")
+    grid, status, sp, sk, order = cloud_cell_grid(points, offsets, 0, k, 0.0 if cell is None else float(cell), sort=not brute)
+    mean = torch.zeros((M,), dtype=torch.float64, device=points.device)
+    _lib.call("etch_cloud_knn_mean", int(B), int(M), int(k), int(bool(brute)), points if brute else sp, sk, order, offsets, grid, status, mean)
+    return mean, status
+
+
+def cloud_radius_count(points, offsets, radius, brute=False):
+    """The number of other rows of its cloud within `radius` of every row (d2 <= radius * radius).  -> count (M) int32, status (B) int32."""
+    B, M = _cloud_args(points, offsets, "cloud_radius_count")
+    if not (float(radius) > 0.0 and math.isfinite(float(radius))):
+        raise _lib.EtchHipError(f"cloud_radius_count: radius must be positive and finite, got {radius}")
+    _, status, sp, sk, order = cloud_cell_grid(points, offsets, 1, 1, float(radius), sort=not brute)
+    count = torch.zeros((M,), dtype=torch.int32, device=points.device)
+    _lib.call("etch_cloud_radius_count", int(B), int(M), float(radius), int(bool(brute)), points if brute else sp, sk, order, offsets, status, count)
+    return count, status
+
+
+def cloud_stat_keep(mean, offsets, ratio, status):
+    """keep_i = m_i <= mu + ratio s per cloud.  -> keep (M) int32, stats (B,2) fp64 = mu, s; ETCH_CLOUD_STATUS_EMPTY is ORed into status."""
+    _need(mean, torch.float64, "mean"), _need(offsets, torch.int32, "offsets"), _need(status, torch.int32, "status")
+    B = offsets.numel() - 1
+    if B < 1 or status.shape != (B,) or mean.dim() != 1 or not math.isfinite(float(ratio)):
+        raise _lib.EtchHipError("cloud_stat_keep: mean must be (M,), status (B,) and ratio finite")
+    keep = torch.zeros((mean.numel(),), dtype=torch.int32, device=mean.device)
+    stats = torch.zeros((B, 2), dtype=torch.float64, device=mean.device)
+    _lib.call("etch_cloud_stat_keep", int(B), float(ratio), mean, offsets, status, stats, keep)
+    return keep, stats
+
+
+def cloud_compact(points, index, offsets, keep):
+    """The rows with keep != 0, in row order.  -> kept (B) int32, new offsets (B+1) int32, new index (M) int32 and new points (M,3) fp64 whose
+    first new_offsets[B] rows are written."""
+    B, M = _cloud_args(points, offsets, "cloud_compact")
+    _need(index, torch.int32, "index"), _need(keep, torch.int32, "keep")
+    if index.shape != (M,) or keep.shape != (M,):
+        raise _lib.EtchHipError(f"cloud_compact: index and keep must be ({M},)")
+    dev = points.device
+    kept = torch.empty((B,), dtype=torch.int32, device=dev)
+    new_offsets = torch.empty((B + 1,), dtype=torch.int32, device=dev)
+    new_index = torch.empty((M,), dtype=torch.int32, device=dev)
+    new_points = torch.empty((M, 3), dtype=torch.float64, device=dev)
+    _lib.call("etch_cloud_compact", int(B), keep, offsets, points, index, _byte_workspace("etch_cloud_scan_workspace", dev, int(B)), kept, new_offsets,
+              new_index, new_points)
+    return kept, new_offsets, new_index, new_points
+
+
+def cloud_voxel_grid(points, offsets, voxel):
+    """One row per occupied cell of size `voxel` (origin: the cloud's bounding-box minimum), in ascending (ix, iy, iz) order.  -> offsets (B+1)
+    int32, centroid (M,3) fp64, count (M) int32, lowest (M) int32 = the cell's lowest row, local to its cloud, cell (M,3) int32, whose first
+    offsets[B] rows are written, and status (B) int32."""
+    B, M = _cloud_args(points, offsets, "cloud_voxel_grid")
+    if not (float(voxel) > 0.0 and math.isfinite(float(voxel))):
+        raise _lib.EtchHipError(f"cloud_voxel_grid: voxel must be positive and finite, got {voxel}")
+    _, status, sp, sk, order = cloud_cell_grid(points, offsets, 2, 1, float(voxel))
+    dev = points.device
+    cells = torch.empty((B,), dtype=torch.int32, device=dev)
+    out_offsets = torch.empty((B + 1,), dtype=torch.int32, device=dev)
+    centroid = torch.empty((M, 3), dtype=torch.float64, device=dev)
+    count = torch.zeros((M,), dtype=torch.int32, device=dev)
+    lowest = torch.zeros((M,), dtype=torch.int32, device=dev)
+    key = torch.zeros((M,), dtype=torch.int64, device=dev)
+    _lib.call("etch_cloud_voxel_grid", int(B), sp, sk, order, offsets, status, _byte_workspace("etch_cloud_scan_workspace", dev, int(B)), cells, out_offsets,
+              centroid, count, lowest, key)
+    cell = torch.stack([key >> 42, (key >> 21) & (2 ** 21 - 1), key & (2 ** 21 - 1)], 1).to(torch.int32)
+    return out_offsets, centroid, count, lowest, cell, status

@@ -972,6 +972,51 @@ int etch_depth_compact(int NV, int H, int W, const double* depth, const double* 
 int etch_depth_pick(int NV, int N, const int* offsets, const int* index, const double* points, const unsigned long long* keys, const double* center,
                     double* out64, float* out32, int* pixel, int* status, void* stream);
 
+/* ---- raw point clouds: exact grid kNN outlier filters, compaction, voxel grid (csrc/cloud_filter.hip) --------------- */
+
+/* Bits of the per-cloud status words of the etch_cloud_* calls. */
+#define ETCH_CLOUD_STATUS_NONFINITE 1    /* a coordinate of the cloud is not finite: nothing of that cloud is written */
+#define ETCH_CLOUD_STATUS_RANGE 2        /* voxel grid: an axis of the cloud has more than 2^21 cells */
+#define ETCH_CLOUD_STATUS_EMPTY 4        /* the cloud has no row where a result needs one (voxel origin, mean and deviation) */
+#define ETCH_CLOUD_MAX_K 32              /* the largest k of etch_cloud_knn_mean */
+#define ETCH_CLOUD_MAX_RINGS 4           /* rings of cells a kNN query examines before it scans its whole cloud instead */
+/* A packed batch is points (M,3) fp64 and offsets (B+1) int32 that start at 0, do not decrease and end at or below M (the calls cannot check device
+ * memory); M may exceed offsets[B]: the rows behind the last cloud are no cloud's, they are never read and sort behind all.
+ * Bounding box, status and cell size per cloud, and the cell key of every row: grid (B,4) fp64 = the cloud's bounding-box minimum
+ * and its cell size h, keys (M) int64 = (ix << 42) | (iy << 21) | iz with i = floor((p - origin) / h) clamped into [0, 2^21), cloud (M) int32 =
+ * the cloud of each row, status (B) int32 = ETCH_CLOUD_STATUS_* (written, not ORed).  mode 0 (kNN): h = cell where cell > 0, else
+ * max(sqrt(k S / n), L k / n) with S = ex ey + ey ez + ez ex and L = the largest of the extents ex, ey, ez; mode 1 (radius): h = cell (1 + 2^-20),
+ * cell = r; both raised to L / 2^20 where smaller, and 1 where every point coincides.  mode 2 (voxel): h = cell; a row beyond 2^21 cells sets
+ * ETCH_CLOUD_STATUS_RANGE.  The caller then sorts the rows by (cloud, key) with a STABLE sort: order (M) int32 = the sorted rows,
+ * sorted_keys = keys[order], sorted_points = points[order]. */
+int etch_cloud_cell_keys(int B, int M, int mode, int k, double cell, const double* points, const int* offsets, double* grid, long long* keys,
+                         int* cloud, int* status, void* stream);
+/* mean (M) fp64, by original row: (sum_j sqrt(s_j)) / k_eff over the k_eff = min(k, n - 1) smallest d2 = ((dx dx + dy dy) + dz dz) from the row to
+ * the OTHER rows of its cloud (coincident ones count), summed in ascending order; 0 where n == 1.  Exact for any cell size.  brute != 0: every
+ * query scans its whole cloud; sorted_points is then the unsorted points and sorted_keys, order, grid may be NULL.  Rows of a cloud with
+ * ETCH_CLOUD_STATUS_NONFINITE are not written.  1 <= k <= ETCH_CLOUD_MAX_K. */
+int etch_cloud_knn_mean(int B, int M, int k, int brute, const double* sorted_points, const long long* sorted_keys, const int* order,
+                        const int* offsets, const double* grid, const int* status, double* mean, void* stream);
+/* count (M) int32, by original row: the OTHER rows of the cloud with d2 <= radius radius (the product rounded once).  Needs the mode 1 keys of the
+ * same radius; brute as above. */
+int etch_cloud_radius_count(int B, int M, double radius, int brute, const double* sorted_points, const long long* sorted_keys, const int* order,
+                            const int* offsets, const int* status, int* count, void* stream);
+/* Statistical filter per cloud: mu = (sum m_i) / n, s = sqrt(sum (m_i - mu)^2 / (n - 1)) (0 for n < 2), keep_i = m_i <= mu + ratio s.  The sums run in an
+ * order n alone fixes (no float atomics).  stats (B,2) fp64 = mu, s; keep (M) int32; n == 0 ORs ETCH_CLOUD_STATUS_EMPTY into status. */
+int etch_cloud_stat_keep(int B, double ratio, const double* mean, const int* offsets, int* status, double* stats, int* keep, void* stream);
+/* Workspace bytes of etch_cloud_compact and etch_cloud_voxel_grid for B clouds. */
+int etch_cloud_scan_workspace(int B, long long* bytes);
+/* The rows with keep != 0, in row order: kept (B) int32 = their number per cloud, new_offsets (B+1) int32, new_index = index of the kept rows,
+ * new_points their coordinates (room for M rows is always enough).  workspace: etch_cloud_scan_workspace(B) bytes. */
+int etch_cloud_compact(int B, const int* keep, const int* offsets, const double* points, const int* index, void* workspace, int* kept,
+                       int* new_offsets, int* new_index, double* new_points, void* stream);
+/* Voxel grid from the mode 2 keys, sorted: one output row per occupied cell in ascending (ix, iy, iz) order, cloud after cloud.  cells (B) int32,
+ * out_offsets (B+1) int32, centroid (.,3) fp64 = (sum of the cell's rows in ascending row order) / count, count, lowest = the cell's lowest row
+ * (local to its cloud), cell_key its key (room for M rows is always enough).  A cloud with a status bit set gets no cell.  workspace: etch_cloud_scan_workspace(B)
+ * bytes. */
+int etch_cloud_voxel_grid(int B, const double* sorted_points, const long long* sorted_keys, const int* order, const int* offsets, const int* status,
+                          void* workspace, int* cells, int* out_offsets, double* centroid, int* count, int* lowest, long long* cell_key, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
