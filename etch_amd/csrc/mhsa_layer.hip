@@ -480,6 +480,21 @@ __global__ void __launch_bounds__(256) interp_schedule_kernel(int B, int N, int 
     sched[2 * slot + 1] = make_int4(__float_as_int(wgt[pt * 3]), __float_as_int(wgt[pt * 3 + 1]), __float_as_int(wgt[pt * 3 + 2]), 0);
 }
 
+// The same records for a LIST of points: sel (B, P) = global point rows b N + n, slot = position in the list, output row = the slot (the layer's
+// output is compact: one 60 x 64 tile per slot).  An empty slot (-1; any row outside [0, B N) counts as one) gets the record of point 0 of the
+// slot's scan: every slot computes on real data, nothing uninitialised is read, and its output row is simply never used.
+__global__ void __launch_bounds__(256) interp_schedule_list_kernel(int B, int P, int N, int S, const int* __restrict__ sel,
+                                                                   const int* __restrict__ idx, const float* __restrict__ wgt,
+                                                                   int4* __restrict__ sched) {
+    const long slot = (long)blockIdx.x * 256 + threadIdx.x;
+    if (slot >= (long)B * P) return;
+    const long g = sel[slot];
+    const long pt = (g >= 0 && g < (long)B * N) ? g : (slot / P) * N;
+    const int cb = (int)((pt / N) * S);
+    sched[2 * slot] = make_int4((int)slot, cb + idx[pt * 3], cb + idx[pt * 3 + 1], cb + idx[pt * 3 + 2]);
+    sched[2 * slot + 1] = make_int4(__float_as_int(wgt[pt * 3]), __float_as_int(wgt[pt * 3 + 1]), __float_as_int(wgt[pt * 3 + 2]), 0);
+}
+
 // out[b,n] = X + att Wc^T + bc with X = blend of three rows of F (B,S,60,64), sched from interp_schedule_kernel.  Grid = multiple of 8
 // workgroups.  Per scan point: its three coarse token rows were requested during the previous point (12 float4 in registers) and are
 // blended when the previous point's layer ends (16 registers across the barrier instead of 48; the tile's maximum is taken there), then staged
@@ -675,6 +690,19 @@ extern "C" int etch_mhsa_layer(long T, const float* X, const float* Wq, const fl
     return ETCH_EINVAL;
 }
 
+// workgroups per compute unit of mhsa_interp_layer_kernel (its dynamic LDS is asked for on the first call); < 0: the HIP error
+static int interp_layer_per_cu() {
+    static int per_cu = 0;
+    if (per_cu == 0) {
+        hipError_t e = hipFuncSetAttribute((const void*)mhsa_interp_layer_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ML_INTERP_LDS);
+        if (e != hipSuccess) return -(int)e;
+        int n = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)mhsa_interp_layer_kernel, 256, ML_INTERP_LDS) != hipSuccess || n < 1) n = 2;
+        per_cu = n;
+    }
+    return per_cu;
+}
+
 extern "C" int etch_mhsa_interp_layer(int B, int N, int S, const float* F, const int* idx, const float* weight,
                                       const int* order, const float* Wq, const float* Wk, const float* Wv, const float* Wc, const float* bc,
                                       float* out, int* sched, void* stream) {
@@ -683,18 +711,33 @@ extern "C" int etch_mhsa_interp_layer(int B, int N, int S, const float* F, const
     if ((long)B * N > 0x7fffffffL || (long)B * S > 0x7fffffffL) return ETCH_EUNSUPPORTED;
     if (((uintptr_t)F | (uintptr_t)Wq | (uintptr_t)Wk | (uintptr_t)Wv | (uintptr_t)Wc | (uintptr_t)bc | (uintptr_t)out | (uintptr_t)sched) & 15)
         return ETCH_EINVAL;
-    static int per_cu = 0;
-    if (per_cu == 0) {
-        hipError_t e = hipFuncSetAttribute((const void*)mhsa_interp_layer_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ML_INTERP_LDS);
-        if (e != hipSuccess) return (int)e;
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)mhsa_interp_layer_kernel, 256, ML_INTERP_LDS) != hipSuccess || n < 1) n = 2;
-        per_cu = n;
-    }
+    const int per_cu = interp_layer_per_cu();
+    if (per_cu < 0) return -per_cu;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(interp_schedule_kernel, dim3((unsigned)(((long)B * N + 255) / 256)), dim3(256), 0, st, B, N, S, idx, weight, order,
                        reinterpret_cast<int4*>(sched));
     hipLaunchKernelGGL(mhsa_interp_layer_kernel, dim3((unsigned)(((etch_cu_count() + 7) / 8) * 8 * per_cu)), dim3(256), ML_INTERP_LDS, st, B, N, S, F, sched, Wq, Wk, Wv, Wc, bc, out, etch_work_counter_slot(st));
+    ETCH_RETURN_IF_LAUNCH_FAILED();
+    return ETCH_OK;
+}
+
+// The same layer at a list of points: sel (B, P) int32 global point rows b N + n (or -1), out (B*P*60, 64) = the tile of slot k at rows 60 k ...
+// The layer kernel is the dense one's, launched over B P slots: it takes everything about a point from its record.
+extern "C" int etch_mhsa_interp_layer_list(int B, int P, int N, int S, const float* F, const int* sel, const int* idx, const float* weight,
+                                           const float* Wq, const float* Wk, const float* Wv, const float* Wc, const float* bc, float* out,
+                                           int* sched, void* stream) {
+    if (B <= 0 || P <= 0) return ETCH_OK;
+    if (N <= 0 || S <= 0 || !F || !sel || !Wq || !idx || !weight || !Wk || !Wv || !Wc || !out || !sched) return ETCH_EINVAL;
+    if ((long)B * P > 0x7fffffffL || (long)B * N > 0x7fffffffL || (long)B * S > 0x7fffffffL) return ETCH_EUNSUPPORTED;
+    if (((uintptr_t)F | (uintptr_t)Wq | (uintptr_t)Wk | (uintptr_t)Wv | (uintptr_t)Wc | (uintptr_t)bc | (uintptr_t)out | (uintptr_t)sched) & 15)
+        return ETCH_EINVAL;
+    const int per_cu = interp_layer_per_cu();
+    if (per_cu < 0) return -per_cu;
+    hipStream_t st = (hipStream_t)stream;
+    const int T = B * P;
+    hipLaunchKernelGGL(interp_schedule_list_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, B, P, N, S, sel, idx, weight,
+                       reinterpret_cast<int4*>(sched));
+    hipLaunchKernelGGL(mhsa_interp_layer_kernel, dim3((unsigned)(((etch_cu_count() + 7) / 8) * 8 * per_cu)), dim3(256), ML_INTERP_LDS, st, 1, T, S, F, sched, Wq, Wk, Wv, Wc, bc, out, etch_work_counter_slot(st));
     ETCH_RETURN_IF_LAUNCH_FAILED();
     return ETCH_OK;
 }

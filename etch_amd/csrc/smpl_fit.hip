@@ -1350,15 +1350,10 @@ __device__ __forceinline__ unsigned sortable_f32(float f) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-// One wave per (scan, label): top-3 confidences among the points carrying that label (a NaN confidence is the greatest, as for torch.topk, and
-// makes the centre NaN; -0 == +0; ties -> lower index), weights conf^20, weighted centre.  labels int64 (argmax output), conf (B,K,1).
-// A real point's key is never 0 (sortable_f32 > 0), so 0 can stand for an empty place in the lists.
-__global__ void __launch_bounds__(64) get_markers_kernel(int K, int M, const float* __restrict__ pts, const long long* __restrict__ labels,
-                                                         const float* __restrict__ conf, float* __restrict__ markers,
-                                                         float* __restrict__ valid_f, unsigned char* __restrict__ valid_b) {
-    const int b = blockIdx.y, m = blockIdx.x, lane = threadIdx.x;
-    const long long* lb = labels + (size_t)b * K;
-    const float* cf = conf + (size_t)b * K;
+// The selection of one (scan, label) by one wave: top-3 confidences among the points carrying that label (a NaN confidence is the greatest, as for
+// torch.topk; -0 == +0; ties -> lower index).  sel[r] = index in the scan of rank r (descending key), -1 beyond min(total, 3); returns `total`, the
+// number of points with the label.  A real point's key is never 0 (sortable_f32 > 0), so 0 can stand for an empty place in the lists.
+__device__ __forceinline__ int marker_top3(int K, int m, const long long* __restrict__ lb, const float* __restrict__ cf, int lane, int sel[3]) {
     unsigned long long top[3] = {0ull, 0ull, 0ull};
     int cnt = 0;
     for (int i = lane; i < K; i += 64) {
@@ -1375,7 +1370,7 @@ __global__ void __launch_bounds__(64) get_markers_kernel(int K, int M, const flo
     }
     int total = cnt;
     for (int off = 32; off >= 1; off >>= 1) total += __shfl_xor(total, off, 64);
-    int sel[3] = {-1, -1, -1};
+    sel[0] = sel[1] = sel[2] = -1;
     for (int r = 0; r < 3; ++r) {
         const unsigned long long best = etch_wave_max_u64(top[0]);
         if (best != 0ull) {
@@ -1383,24 +1378,89 @@ __global__ void __launch_bounds__(64) get_markers_kernel(int K, int M, const flo
             if (top[0] == best) { top[0] = top[1]; top[1] = top[2]; top[2] = 0ull; }
         }
     }
+    return total;
+}
+
+// Weighted centre of a label's tk (<= 3) ranked points, accumulated in rank order: weights conf^20 (fit_SMPL.py:52-57; 0/0 = NaN when every weight
+// underflows).  conf_of(r) = the confidence of rank r, coord_of(r, a) = coordinate a of its point.  tk == 0 -> (0, 0, 0).
+template <class ConfOf, class CoordOf>
+__device__ __forceinline__ void marker_centre(int tk, ConfOf conf_of, CoordOf coord_of, float c[3]) {
+    c[0] = c[1] = c[2] = 0.f;
+    if (tk > 0) {
+        float wsum = 0.f, acc[3] = {0.f, 0.f, 0.f};
+        for (int r = 0; r < tk; ++r) {
+            const float w = powf(conf_of(r), 20.0f);
+            const float p0 = coord_of(r, 0), p1 = coord_of(r, 1), p2 = coord_of(r, 2);
+            acc[0] += p0 * w; acc[1] += p1 * w; acc[2] += p2 * w;
+            wsum += w;
+        }
+        c[0] = acc[0] / wsum; c[1] = acc[1] / wsum; c[2] = acc[2] / wsum;
+    }
+}
+
+// One wave per (scan, label): marker_top3, then the weighted centre of the selected points.  labels int64 (argmax output), conf (B,K,1).
+__global__ void __launch_bounds__(64) get_markers_kernel(int K, int M, const float* __restrict__ pts, const long long* __restrict__ labels,
+                                                         const float* __restrict__ conf, float* __restrict__ markers,
+                                                         float* __restrict__ valid_f, unsigned char* __restrict__ valid_b) {
+    const int b = blockIdx.y, m = blockIdx.x, lane = threadIdx.x;
+    const float* cf = conf + (size_t)b * K;
+    int sel[3];
+    const int total = marker_top3(K, m, labels + (size_t)b * K, cf, lane, sel);
     if (lane == 0) {
         const size_t o = (size_t)b * M + m;
-        float c[3] = {0.f, 0.f, 0.f};
-        if (total > 0) {
-            float wsum = 0.f, acc[3] = {0.f, 0.f, 0.f};
-            const int tk = total < 3 ? total : 3;
-            for (int r = 0; r < tk; ++r) {
-                const float w = powf(cf[sel[r]], 20.0f);
-                const float* p = pts + ((size_t)b * K + sel[r]) * 3;
-                acc[0] += p[0] * w; acc[1] += p[1] * w; acc[2] += p[2] * w;
-                wsum += w;
-            }
-            c[0] = acc[0] / wsum; c[1] = acc[1] / wsum; c[2] = acc[2] / wsum;
-        }
+        float c[3];
+        marker_centre(total < 3 ? total : 3, [&](int r) { return cf[sel[r]]; },
+                      [&](int r, int a) { return pts[((size_t)b * K + sel[r]) * 3 + a]; }, c);
         markers[o * 3] = c[0]; markers[o * 3 + 1] = c[1]; markers[o * 3 + 2] = c[2];
         if (valid_f) valid_f[o] = total > 0 ? 1.f : 0.f;
         if (valid_b) valid_b[o] = total > 0 ? 1 : 0;
     }
+}
+
+// The selection half of get_markers_kernel alone, one wave per (scan, label): sel (B,M,3) = global point rows b K + i in rank order, -1 beyond
+// cnt (B,M) = min(total, 3).  What the direction head has to be evaluated at (markers_from_selected_kernel does the other half).
+__global__ void __launch_bounds__(64) marker_select_kernel(int K, int M, const long long* __restrict__ labels, const float* __restrict__ conf,
+                                                           int* __restrict__ sel_out, int* __restrict__ cnt_out) {
+    const int b = blockIdx.y, m = blockIdx.x, lane = threadIdx.x;
+    int sel[3];
+    const int total = marker_top3(K, m, labels + (size_t)b * K, conf + (size_t)b * K, lane, sel);
+    if (lane == 0) {
+        const size_t o = (size_t)b * M + m;
+        for (int r = 0; r < 3; ++r) sel_out[o * 3 + r] = sel[r] >= 0 ? b * K + sel[r] : -1;
+        cnt_out[o] = total < 3 ? total : 3;
+    }
+}
+
+// inner = points - (direction * magnitude) / scale      (src/inference_demo.py:58-59), one coordinate
+__device__ __forceinline__ float inner_coord(float p, float d, float mag, float scale) {
+#pragma clang fp contract(off)
+    return p - (d * mag) / scale;
+}
+
+// The centre half of get_markers_kernel on the selected points only, one thread per (scan, label): the inner point of slot (b, m, r) is formed
+// here from the point sel[b,m,r] and the COMPACT direction dir (B*M*3, 3) of that slot (inner_points_kernel's expression), then blended as
+// get_markers_kernel blends the dense inner points: the same bits.  A slot beyond cnt is not read.
+__global__ void __launch_bounds__(64) markers_from_selected_kernel(long BM, long rows, const int* __restrict__ sel, const int* __restrict__ cnt,
+                                                                   const float* __restrict__ pts, const float* __restrict__ conf,
+                                                                   const float* __restrict__ mag, float scale, const float* __restrict__ dir,
+                                                                   float* __restrict__ markers, float* __restrict__ valid_f,
+                                                                   unsigned char* __restrict__ valid_b) {
+    const long o = (long)blockIdx.x * 64 + threadIdx.x;
+    if (o >= BM) return;
+    int tk = cnt[o];
+    tk = tk < 0 ? 0 : (tk > 3 ? 3 : tk);
+    long g[3] = {0, 0, 0};
+    for (int r = 0; r < tk; ++r) {
+        const long v = sel[o * 3 + r];
+        if (v < 0 || v >= rows) { tk = r; break; }         // (a list that does not come from marker_select_kernel: never read out of bounds)
+        g[r] = v;
+    }
+    float c[3];
+    marker_centre(tk, [&](int r) { return conf[g[r]]; },
+                  [&](int r, int a) { return inner_coord(pts[g[r] * 3 + a], dir[(o * 3 + r) * 3 + a], mag[g[r]], scale); }, c);
+    markers[o * 3] = c[0]; markers[o * 3 + 1] = c[1]; markers[o * 3 + 2] = c[2];
+    if (valid_f) valid_f[o] = tk > 0 ? 1.f : 0.f;
+    if (valid_b) valid_b[o] = tk > 0 ? 1 : 0;
 }
 
 // scan_status[b]: bit 0 = some valid marker of the scan is non-finite (conf**20 underflowed to 0 for every one of a label's top-3
@@ -1434,13 +1494,10 @@ __global__ void __launch_bounds__(256) argmax_rows_kernel(long R, int G, const f
     }
 }
 
-// inner = points - (direction * magnitude) / scale      (src/inference_demo.py:58-59)
+// inner = points - (direction * magnitude) / scale for every point (inner_coord)
 __global__ void __launch_bounds__(256) inner_points_kernel(long n, const float* __restrict__ pts, const float* __restrict__ dir,
                                                            const float* __restrict__ mag, float scale, float* __restrict__ out) {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n * 3; i += (long)gridDim.x * 256) {
-#pragma clang fp contract(off)
-        out[i] = pts[i] - (dir[i] * mag[i / 3]) / scale;
-    }
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n * 3; i += (long)gridDim.x * 256) out[i] = inner_coord(pts[i], dir[i], mag[i / 3], scale);
 }
 
 // the split fit's arrival counters (one 256-byte line per scan) cleared before every fit.  A kernel and not hipMemsetAsync: replayed from a
@@ -1542,6 +1599,26 @@ int etch_get_markers(int B, int K, int M, const float* pts, const long long* lab
                      float* valid_f, unsigned char* valid_b, void* stream) {
     if (B <= 0 || M <= 0) return ETCH_OK;
     hipLaunchKernelGGL(get_markers_kernel, dim3(M, B), dim3(64), 0, (hipStream_t)stream, K, M, pts, labels, conf, markers, valid_f, valid_b);
+    ETCH_RETURN_IF_LAUNCH_FAILED();
+    return ETCH_OK;
+}
+
+int etch_marker_select(int B, int K, int M, const long long* labels, const float* conf, int* sel, int* cnt, void* stream) {
+    if (B <= 0 || M <= 0) return ETCH_OK;
+    if (K < 0 || !labels || !conf || !sel || !cnt) return ETCH_EINVAL;
+    if ((long)B * K > 0x7fffffffL) return ETCH_EUNSUPPORTED;
+    hipLaunchKernelGGL(marker_select_kernel, dim3(M, B), dim3(64), 0, (hipStream_t)stream, K, M, labels, conf, sel, cnt);
+    ETCH_RETURN_IF_LAUNCH_FAILED();
+    return ETCH_OK;
+}
+
+int etch_markers_from_selected(int B, int K, int M, const int* sel, const int* cnt, const float* pts, const float* conf, const float* mag,
+                               float scale, const float* dir, float* markers, float* valid_f, unsigned char* valid_b, void* stream) {
+    if (B <= 0 || M <= 0) return ETCH_OK;
+    if (K < 0 || !sel || !cnt || !pts || !conf || !mag || !dir || !markers) return ETCH_EINVAL;
+    const long BM = (long)B * M;
+    hipLaunchKernelGGL(markers_from_selected_kernel, dim3((unsigned)((BM + 63) / 64)), dim3(64), 0, (hipStream_t)stream, BM, (long)B * K, sel, cnt,
+                       pts, conf, mag, scale, dir, markers, valid_f, valid_b);
     ETCH_RETURN_IF_LAUNCH_FAILED();
     return ETCH_OK;
 }

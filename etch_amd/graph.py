@@ -1,7 +1,7 @@
 """The hot path of one fixed batch shape as ONE HIP graph (hipGraph through torch.cuda.CUDAGraph).
 
 A latency-bound caller (a single scan: BASELINE configs[0], the reference's inference_demo.py:41-66) spends its time in ~430 small
-dependent launches on five streams; captured once, the whole stage 1 -> labels / inner points -> marker fit -> LBS chain is replayed
+dependent launches on five streams; captured once, the whole stage 1 -> labels / markers -> marker fit -> LBS chain is replayed
 with one host call.  Everything the eager path does is capturable as is: every op launches through the C ABI on the current stream,
 outputs come from torch's caching allocator (graph-private pool).  The capture runs the model on ONE stream (no index-op or head side
 streams: the schedule of `bench.py --serial`), so the graph is a single chain of kernel nodes: replaying the multi-branch graph that the
@@ -14,8 +14,7 @@ queues (GPU_MAX_HW_QUEUES, default 4); a process that also runs the eager multi-
 and both paths slow down by 30 - 40 % -- use one or the other in a process, or raise GPU_MAX_HW_QUEUES."""
 import torch
 
-from . import ops
-from .models.fit_SMPL import fit_smpl_device, fit_smpl_finalize
+from .models.fit_SMPL import fit_smpl_finalize, stage2_from_stage1
 
 
 class GraphedHotPath:
@@ -48,10 +47,8 @@ class GraphedHotPath:
 
     def _device_part(self):
         pts = self.static_in
-        results, _ = self.model(pts, pred_items=["confidence", "direction", "magnitude"], direction_mode="standard_vector")
-        labels = ops.argmax_rows(results["part_labels"])
-        inner = ops.inner_points(pts, results["direction"], results["magnitude"], float(self.args.scale_magnitude))
-        dev = fit_smpl_device(self.args, inner, labels, results["confidences"], self.gender, **self.fit_kwargs)
+        results, ctx = self.model.forward_for_fit(pts)
+        dev = stage2_from_stage1(self.args, self.model, pts, results, ctx, self.gender, **self.fit_kwargs)
         dev["results"] = results
         return dev
 

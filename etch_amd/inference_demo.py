@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .models.fit_SMPL import Mesh, fit_smpl
+from .models.fit_SMPL import Mesh, fit_smpl, stage2_from_stage1
 from .models.models_pointcloud import GT_network_equiv
 
 
@@ -69,11 +69,14 @@ def predict_smpl_batch(args, model, points_tensor, gender="neutral", inner_out=N
     if getattr(args, "fit_pose_prior", None) is not None:       # --pose_prior (main): the marker fit under the mixture prior
         fit_kwargs.setdefault("pose_prior", args.fit_pose_prior)
     with torch.no_grad():
+        if inner_out is None:
+            # nobody asks for all inner points: the direction head runs at the markers' points only (fit_SMPL.markers_from_stage1; same bits)
+            results, ctx = model.forward_for_fit(points_tensor)
+            return stage2_from_stage1(args, model, points_tensor, results, ctx, gender, fit=fit_smpl, **fit_kwargs)
         results, _ = model(points_tensor, pred_items=["confidence", "direction", "magnitude"], direction_mode="standard_vector")
         labels = ops.argmax_rows(results["part_labels"])
         inner = ops.inner_points(points_tensor.contiguous(), results["direction"], results["magnitude"], float(args.scale_magnitude))
-        if inner_out is not None:
-            inner_out["inner"] = inner
+        inner_out["inner"] = inner
         return fit_smpl(args, inner, labels, results["confidences"], gender, **fit_kwargs)
 
 

@@ -94,8 +94,31 @@ def get_markers(args, inner_points, part_labels, confidences):
     return markers, valid_b
 
 
+def markers_from_stage1(args, model, ctx, points, results):
+    """Stage-1 outputs -> (markers (B,M,3), valid_f, valid_b) with the direction head evaluated at the marker points only.  results / ctx from
+    model.forward_for_fit(points).  The same bits as get_markers on the dense inner points: the labels' top-3 points are picked first
+    (ops.marker_select), the head runs on that fixed list of B*M*3 slots (empty ones compute on a real point and are ignored: shapes do not depend
+    on the data, so the chain stays graph-capturable), and ops.markers_from_selected forms the inner points of the slots and blends them."""
+    conf = results["confidences"].contiguous()
+    labels = ops.argmax_rows(results["part_labels"])
+    sel, cnt = ops.marker_select(labels, conf, len(args.markerset))
+    direction = model.direction_at(ctx, sel)
+    return ops.markers_from_selected(sel, cnt, points.contiguous(), conf, results["magnitude"].contiguous(), float(args.scale_magnitude), direction)
+
+
+def stage2_from_stage1(args, model, points, results, ctx, gender, fit=None, **fit_kwargs):
+    """Everything behind the two nets, on the current stream (a pipelined caller has joined them there): labels, markers, `fit` (fit_smpl_device
+    unless given).  results / ctx from model.forward_for_fit(points); ctx None = the dense head ran: inner points of all points, get_markers."""
+    fit = fit or fit_smpl_device
+    if ctx is not None:
+        return fit(args, None, None, None, gender, markers=markers_from_stage1(args, model, ctx, points, results), **fit_kwargs)
+    labels = ops.argmax_rows(results["part_labels"])
+    inner = ops.inner_points(points.contiguous(), results["direction"], results["magnitude"], float(args.scale_magnitude))
+    return fit(args, inner, labels, results["confidences"], gender, **fit_kwargs)
+
+
 def fit_smpl_device(args, inner_points, part_labels, confidences, gender, steps_stage0=30, steps_stage1=50, lr_stage0=5e-1, lr_stage1=2e-1,
-                    want_trace=False, markers_override=None, init=None, prior=None, pose_prior=None):
+                    want_trace=False, markers_override=None, init=None, prior=None, pose_prior=None, markers=None):
     """Device-side part of fit_smpl: every kernel is enqueued on the current HIP stream, nothing is copied to the host.
     Returns a dict of device tensors (markers, valid, x, x_stage0, err_trace, verts, joints) + the face array.
     markers_override = (markers (B,M,3), valid_f (B,M) float, valid_b (B,M) bool): measurement aid of bench.py -- get_markers still runs
@@ -103,12 +126,17 @@ def fit_smpl_device(args, inner_points, part_labels, confidences, gender, steps_
     fit that freezes early; see bench.py `well_posed_fit`).
     init (B,DOF) / prior = (mean, weight), each (B,DOF): warm start and diagonal Gaussian prior of ops.smpl_lm_fit (steps_stage0 may be 0:
     stage 1 then starts at `init`); absent, the fit is the reference's.
-    pose_prior: an ops.PosePrior (utils.prior.MaxMixturePrior.as_fit_prior): max-mixture GMM / joint-angle terms in both stages."""
+    pose_prior: an ops.PosePrior (utils.prior.MaxMixturePrior.as_fit_prior): max-mixture GMM / joint-angle terms in both stages.
+    markers = (markers, valid_f, valid_b) already aggregated from the network's output (markers_from_stage1): get_markers is not run, and
+    inner_points / part_labels / confidences are not read (may be None)."""
     M = len(args.markerset)
     vids = list(args.markerset.values())
     bm = _resolve_body_model(args, gender)
-    db = _device_body(bm, vids, inner_points.device)
-    markers, valid_f, valid_b = ops.get_markers(inner_points.contiguous(), part_labels.contiguous(), confidences.contiguous(), M)
+    db = _device_body(bm, vids, markers[0].device if markers is not None else inner_points.device)
+    if markers is not None:
+        markers, valid_f, valid_b = markers
+    else:
+        markers, valid_f, valid_b = ops.get_markers(inner_points.contiguous(), part_labels.contiguous(), confidences.contiguous(), M)
     if markers_override is not None:
         markers, valid_f, valid_b = markers_override
     # stage 0: damping 0.01 (fit_SMPL.py:200); stage 1: Theseus default damping 1e-3 (:249)
@@ -153,11 +181,11 @@ def fit_smpl_finalize(dev):
 
 
 def fit_smpl(args, inner_points, part_labels, confidences, gender, steps_stage0=30, steps_stage1=50, lr_stage0=5e-1, lr_stage1=2e-1,
-             return_trace=False, markers_override=None, init=None, prior=None, pose_prior=None):
+             return_trace=False, markers_override=None, init=None, prior=None, pose_prior=None, markers=None):
     """fit_SMPL.py:68-269.  Returns (list of meshes, pred_markers_position (B,M,3), valid_mask (B,M) bool,
     [pose (B,23,3), shape (B,10), global_orient (B,3), translation (B,3), joints (B,45,3)] as numpy)."""
     dev = fit_smpl_device(args, inner_points, part_labels, confidences, gender, steps_stage0, steps_stage1, lr_stage0, lr_stage1, return_trace,
-                          markers_override=markers_override, init=init, prior=prior, pose_prior=pose_prior)
+                          markers_override=markers_override, init=init, prior=prior, pose_prior=pose_prior, markers=markers)
     out = fit_smpl_finalize(dev)
     if return_trace:
         return out + (dev,)

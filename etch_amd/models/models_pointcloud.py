@@ -107,16 +107,21 @@ class GT_network_equiv(nn.Module):
         return (self.fuse_direction_interp and self.fold_linear_chains and len(layers) >= 2 and layers[0].embedding_dim == 64
                 and layers[0].value_dim == 64)
 
-    def anchor_weights(self, tokens, interp=None):
+    def anchor_weights(self, tokens, interp=None, sel=None):
         """tokens [T, 60, C] -> anc_w [T, 60]: direction_encoder -> direction_predictor -> so3_reg (models_pointcloud.py:115-117).
         interp = (coarse tokens (B,S,60,C), idx (B,N,3), w (B,N,3), order) instead of `tokens`: the 3-NN interpolation of :181-183 is
-        done inside the first attention layer's kernel; the interpolated tokens are never written out."""
+        done inside the first attention layer's kernel; the interpolated tokens are never written out.
+        sel (B,P) int32 with `interp`: only the listed points (global rows b*N + n, -1 = empty slot) -> anc_w [B*P, 60], slot by slot."""
         layers = self.direction_encoder.self_attention_layers
         if interp is not None:
             feats_cl, idx3, w3, order = interp
             l0 = layers[0]
-            x = ops.mhsa_interp_layer(feats_cl, idx3, w3, l0.query_transform.weight.detach(), l0.key_transform.weight.detach(),
-                                      l0.value_transform.weight.detach(), l0.head_combine.weight.detach(), l0.head_combine.bias.detach(), order=order)
+            l0w = (l0.query_transform.weight.detach(), l0.key_transform.weight.detach(), l0.value_transform.weight.detach(),
+                   l0.head_combine.weight.detach(), l0.head_combine.bias.detach())
+            if sel is not None:
+                x = ops.mhsa_interp_layer_list(feats_cl, sel, idx3, w3, *l0w)
+            else:
+                x = ops.mhsa_interp_layer(feats_cl, idx3, w3, *l0w, order=order)
             T = x.shape[0] // 60
             x = x.view(T, 60, l0.value_dim)
             first = 1
@@ -155,6 +160,43 @@ class GT_network_equiv(nn.Module):
         assert iv == [0.0, 0.0, 1.0], "only direction_mode='standard_vector' is implemented (as in the reference, :198-208)"
         d, _, _ = ops.so3_mean_dir(anc_w, anchors.contiguous())
         return d.view(B, N, 3)
+
+    # ------------------------------------------------------------------------------------------------ the fit paths: direction at the marker points
+    # The marker fit reads the direction of at most 3 points per (scan, label) (fit_SMPL.py:17-62: top-3 confidences of each label), and the head is
+    # independent per point from the encoder output onwards.  forward_for_fit runs the encoder and the two nets and hands back what the head needs;
+    # the caller picks the points (ops.marker_select) and asks for their directions (direction_at): bitwise the dense head's at those points.
+    # forward() itself always returns the dense `direction`.
+    _want_direction_context = False
+    direction_context = None
+
+    def sparse_direction_ok(self, hitpts):
+        layers = self.direction_encoder.self_attention_layers
+        return (os.environ.get("ETCH_SPARSE_DIRECTION", "1") != "0" and hitpts.is_cuda and self._can_fuse_interp() and self.fuse_direction_tail
+                and layers[-1].embedding_dim == 64 and not self.wants_grad())
+
+    def forward_for_fit(self, hitpts, direction_mode="standard_vector"):
+        """Stage 1 for a caller that builds the markers: -> (results, ctx).  ctx = (coarse tokens, idx3, w3, anchors) for direction_at and `results`
+        has no "direction" -- or, where the list form does not apply (sparse_direction_ok), ctx is None and `results` is forward()'s, dense."""
+        if not self.sparse_direction_ok(hitpts):
+            results, _ = self(hitpts, pred_items=["confidence", "direction", "magnitude"], direction_mode=direction_mode)
+            return results, None
+        if direction_mode != "standard_vector":
+            raise AssertionError("Not implemented")
+        self._want_direction_context, self.direction_context = True, None
+        try:
+            results, _ = self(hitpts, pred_items=["confidence", "magnitude"], direction_mode=direction_mode)
+            ctx = self.direction_context
+        finally:
+            self._want_direction_context, self.direction_context = False, None
+        assert ctx is not None
+        return results, ctx
+
+    def direction_at(self, ctx, sel):
+        """ctx of forward_for_fit, sel (B, ...) int32 global point rows (-1: empty slot, its row is to be ignored) -> direction (sel.numel(), 3)."""
+        feats_cl, idx3, w3, anchors = ctx
+        anc_w = self.anchor_weights(None, interp=(feats_cl, idx3, w3, None), sel=sel.reshape(sel.shape[0], -1))
+        d, _, _ = ops.so3_mean_dir(anc_w, anchors.contiguous())
+        return d
 
     # ------------------------------------------------------------------------------------------------ differentiable path
     # Which path forward() takes:
@@ -438,6 +480,8 @@ class GT_network_equiv(nn.Module):
                 cmean = ops.token_mean(r.feats_cl.view(Bc * S, na, C))
             _, point_inv_feat = ops.prop_interp(cmean.view(Bc, S, 1, C), idx3, w3, order=order)
             point_equiv_cl, interp = None, (r.feats_cl, idx3, w3, order)
+            if self._want_direction_context:
+                self.direction_context = (r.feats_cl, idx3, w3, so3_anchors)
         else:
             point_equiv_cl, point_inv_feat = propagate_cl(hitpts, r.xyz, r.feats_cl, order=order)
         results = {}

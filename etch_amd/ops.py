@@ -690,6 +690,23 @@ def mhsa_interp_layer(feats_cl, idx, w, wq, wk, wv, wc, bc, order=None):
     return out
 
 
+def mhsa_interp_layer_list(feats_cl, sel, idx, w, wq, wk, wv, wc, bc):
+    """mhsa_interp_layer at a list of points: sel (B, P) int32 global point rows b*N + n (or -1: an empty slot, whose output is to be ignored)
+    -> (B*P*60, 64), slot k at rows 60 k ...; bitwise the rows of those points in mhsa_interp_layer's output."""
+    for t, n in ((feats_cl, "feats"), (w, "w"), (wq, "wq"), (wk, "wk"), (wv, "wv"), (wc, "wc")):
+        _need(t, torch.float32, n)
+    _need(idx, torch.int32, "idx"), _need(sel, torch.int32, "sel")
+    if bc is not None:
+        _need(bc, torch.float32, "bc")
+    B, S, A, C = feats_cl.shape
+    assert (A, C) == (60, 64) and idx.shape[0] == B and idx.shape == w.shape and sel.dim() == 2 and sel.shape[0] == B
+    N, P = idx.shape[1], sel.shape[1]
+    out = torch.empty((B * P * 60, 64), dtype=torch.float32, device=feats_cl.device)
+    sched = torch.empty((B * P, 8), dtype=torch.int32, device=feats_cl.device)      # workspace: one record per slot
+    _lib.call("etch_mhsa_interp_layer_list", B, P, N, S, feats_cl, sel, idx, w, wq, wk, wv, wc, bc, out, sched)
+    return out
+
+
 def token_mean(x):
     """x (T, A, C) -> mean over the A tokens (T, C)."""
     _need(x, torch.float32, "x")
@@ -909,6 +926,34 @@ def get_markers(points, labels, conf, num_markers):
     valid_f = torch.empty((B, num_markers), dtype=torch.float32, device=points.device)
     valid_b = torch.empty((B, num_markers), dtype=torch.bool, device=points.device)
     _lib.call("etch_get_markers", B, K, num_markers, points, labels, conf, markers, valid_f, valid_b)
+    return markers, valid_f, valid_b
+
+
+def marker_select(labels, conf, num_markers):
+    """The selection half of get_markers: labels (B,K) int64, conf (B,K,1) -> sel (B,M,3) int32 = global point rows b*K + i of each label's
+    top-3 confidences in rank order (-1 beyond cnt), cnt (B,M) int32 = min(points carrying the label, 3)."""
+    _need(labels, torch.int64, "labels"), _need(conf, torch.float32, "conf")
+    B, K = labels.shape
+    assert conf.numel() == B * K
+    sel = torch.empty((B, num_markers, 3), dtype=torch.int32, device=labels.device)
+    cnt = torch.empty((B, num_markers), dtype=torch.int32, device=labels.device)
+    _lib.call("etch_marker_select", B, K, num_markers, labels, conf, sel, cnt)
+    return sel, cnt
+
+
+def markers_from_selected(sel, cnt, points, conf, magnitude, scale, direction):
+    """The other half: direction (B*M*3, 3) = the direction at every slot of sel -> (markers (B,M,3), valid_f, valid_b), bitwise
+    get_markers(inner_points(points, dense direction, magnitude, scale), labels, conf, M)."""
+    _need(sel, torch.int32, "sel"), _need(cnt, torch.int32, "cnt")
+    for t, n in ((points, "points"), (conf, "conf"), (magnitude, "magnitude"), (direction, "direction")):
+        _need(t, torch.float32, n)
+    B, M, _ = sel.shape
+    K = points.shape[1]
+    assert points.shape == (B, K, 3) and conf.numel() == B * K and magnitude.numel() == B * K and direction.numel() == B * M * 9 and cnt.shape == (B, M)
+    markers = torch.empty((B, M, 3), dtype=torch.float32, device=points.device)
+    valid_f = torch.empty((B, M), dtype=torch.float32, device=points.device)
+    valid_b = torch.empty((B, M), dtype=torch.bool, device=points.device)
+    _lib.call("etch_markers_from_selected", B, K, M, sel, cnt, points, conf, magnitude, float(scale), direction, markers, valid_f, valid_b)
     return markers, valid_f, valid_b
 
 

@@ -5,8 +5,7 @@ index stream) start as soon as its points are resident.  Results are identical t
 in-flight batches besides the (read-only) weights and body-model tables."""
 import torch
 
-from . import ops
-from .models.fit_SMPL import fit_smpl_device, fit_smpl_finalize, fit_smpl_stage_host
+from .models.fit_SMPL import fit_smpl_finalize, fit_smpl_stage_host, stage2_from_stage1
 
 
 def limit_host_threads(n=None):
@@ -130,7 +129,7 @@ class HotPathPipeline:
                 self.model.defer_join = True          # the heads on side streams are joined on s2 below, not on s1
                 self.model.keepalive = keep
                 try:
-                    results, _ = self.model(points, pred_items=["confidence", "direction", "magnitude"], direction_mode="standard_vector")
+                    results, ctx = self.model.forward_for_fit(points)
                 finally:
                     self.model.input_producer, self.model.defer_join, self.model.keepalive = None, False, None
                 joins = self.model.pending_join or []
@@ -138,14 +137,21 @@ class HotPathPipeline:
                 ready = torch.cuda.Event(enable_timing=timing)
                 ready.record(s1)
             conf = results["confidences"]
-            keep += [conf, results["part_labels"], results["direction"], results["magnitude"]]
+            keep += [conf, results["part_labels"], results["magnitude"]]
+            # the direction head's tail runs on s2 behind the nets (at the markers' points only): what it reads was made on s1
+            if ctx is None:
+                keep.append(results["direction"])
+            else:
+                # (the coarse tokens, 0.6 GB at 32 x 5 000 points, are the one large tensor among them: held on the ticket they stay allocated for
+                # every batch in flight, peak 6.38 GiB against 5.23; one record_stream per batch hands the block back once s2 has passed this
+                # batch's tail and costs the enqueue thread nothing measurable, profiles/sparse_direction_head.txt)
+                ctx[0].record_stream(self.s2)
+                keep += list(ctx[1:])
             with torch.cuda.stream(self.s2):
                 self.s2.wait_event(ready)
                 for ev in joins:
                     self.s2.wait_event(ev)
-                labels = ops.argmax_rows(results["part_labels"])
-                inner = ops.inner_points(points.contiguous(), results["direction"], results["magnitude"], float(self.args.scale_magnitude))
-                fit = fit_smpl_device(self.args, inner, labels, conf, self.gender, **self.fit_kwargs)
+                fit = stage2_from_stage1(self.args, self.model, points, results, ctx, self.gender, **self.fit_kwargs)
                 # device -> host copies ride on s2 right behind this batch's fit (pinned, reused buffers): result() must
                 # not enqueue anything on s2, where it would queue behind the NEXT batch's fit
                 fit_smpl_stage_host(fit, self._pinned[self._n % len(self._pinned)])

@@ -317,6 +317,11 @@ int etch_mhsa_layer_dirtail(long T, const float* X, const float* Wq, const float
 int etch_mhsa_interp_layer(int B, int N, int S, const float* F, const int* idx, const float* weight, const int* order, const float* Wq,
                            const float* Wk, const float* Wv, const float* Wc, const float* bc, float* out, int* sched, void* stream);
 int etch_token_mean(long T, int A, int C, const float* X, float* mean, void* stream);
+/* etch_mhsa_interp_layer at a LIST of points (the fit paths evaluate the direction head at the marker points only): sel (B,P) int32 = global
+ * point rows b*N + n, or -1 for an empty slot (computed on point 0 of the slot's scan; its output is to be ignored) -> out (B*P*60, 64), slot k at
+ * rows 60 k ...; bitwise the rows of that point in etch_mhsa_interp_layer's output.  sched: workspace of B*P*8 int32 (16-byte aligned). */
+int etch_mhsa_interp_layer_list(int B, int P, int N, int S, const float* F, const int* sel, const int* idx, const float* weight, const float* Wq,
+                                const float* Wk, const float* Wv, const float* Wc, const float* bc, float* out, int* sched, void* stream);
 
 /* y[r] = x[r,:K] . w + bias: so3_reg Conv1d(128,1,1) (src/models/models_pointcloud.py:54,117). */
 int etch_rowdot(long R, int K, const float* x, long ldx, const float* w, float bias, float* y, void* stream);
@@ -559,6 +564,14 @@ int etch_inner_points(long n, const float* pts, const float* dir, const float* m
  * order (a NaN of either sign greatest -- the marker is then NaN and etch_marker_status flags it -- and -0 == +0); equal ones go to the lower index. */
 int etch_get_markers(int B, int K, int M, const float* pts, const long long* labels, const float* conf, float* markers,
                      float* valid_f, unsigned char* valid_b, void* stream);
+/* get_markers in two halves, for callers that know the inner points only at the selected points:
+ * etch_marker_select: labels (B,K) i64, conf (B,K,1) -> sel (B,M,3) i32 = global point rows b*K + i of the label's top-3 confidences in rank
+ *   order (confidence descending, then lower index), -1 beyond cnt (B,M) i32 = min(points with the label, 3).
+ * etch_markers_from_selected: pts (B,K,3), conf, mag (B,K,1), scale and dir (B*M*3, 3) = the direction of every slot of sel -> markers (B,M,3),
+ *   valid (cnt > 0) as float and/or bool bytes: bitwise etch_get_markers of etch_inner_points(pts, dense direction, mag, scale). */
+int etch_marker_select(int B, int K, int M, const long long* labels, const float* conf, int* sel, int* cnt, void* stream);
+int etch_markers_from_selected(int B, int K, int M, const int* sel, const int* cnt, const float* pts, const float* conf, const float* mag,
+                               float scale, const float* dir, float* markers, float* valid_f, unsigned char* valid_b, void* stream);
 
 /* Per-scan status of the aggregated markers (NaN check on the marker weights at the boundary): status (B) i32,
  * bit 0 = a valid marker of the scan is non-finite -- every one of a label's top-3 confidences underflowed in conf**20, so the
