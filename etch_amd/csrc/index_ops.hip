@@ -579,23 +579,13 @@ __device__ __forceinline__ void knn_literal_query(int q, int start, int end, int
 // k = 1).  The SET of results evolves exactly like the reference's heap; its ascending output order is unique unless two results
 // have equal distances, and exactly then the query is redone by the literal heap scan above, so the output is the reference's in
 // every case.
-__global__ void __launch_bounds__(KNNW_WAVES * 64) knn_wave_kernel(int nsample, int nseg, const float* __restrict__ xyz,
-                                                                    const float* __restrict__ new_xyz, const int* __restrict__ offset,
-                                                                    const int* __restrict__ new_offset, int m_total, int* __restrict__ idx,
-                                                                    float* __restrict__ dist2, int write_sqrt) {
-    extern __shared__ __attribute__((aligned(16))) float smem_f[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float* hd = smem_f + wave * 2 * nsample;          // heap distances [k]   (literal path)
-    int* hi = (int*)(hd + nsample);                   // heap indices   [k]
-    float* cand_d = smem_f + KNNW_WAVES * 2 * nsample + wave * 128;   // candidates of the current chunk
-    int* cand_i = (int*)(cand_d + 64);
-    for (int q = blockIdx.x * KNNW_WAVES + wave; q < m_total; q += gridDim.x * KNNW_WAVES) {
-        int seg = 0;
-        while (seg < nseg - 1 && q >= new_offset[seg]) ++seg;
-        const int start = seg == 0 ? 0 : offset[seg - 1], end = offset[seg];
+// the full scan of ONE query by one wave: what knn_wave_kernel does per query, and what the grid kernel falls back to
+__device__ __forceinline__ void knn_wave_query(int q, int start, int end, int nsample, int lane, const float* __restrict__ xyz,
+                                               const float* __restrict__ new_xyz, float* hd, int* hi, float* cand_d, int* cand_i,
+                                               int* __restrict__ idx, float* __restrict__ dist2, int write_sqrt) {
         if (nsample > 16) {
             knn_literal_query(q, start, end, nsample, lane, xyz, new_xyz, hd, hi, cand_d, cand_i, idx, dist2, write_sqrt);
-            continue;
+            return;
         }
         const float qx = new_xyz[(size_t)q * 3], qy = new_xyz[(size_t)q * 3 + 1], qz = new_xyz[(size_t)q * 3 + 2];
         float bd = 1e10f;                             // lane l < k: l-th smallest distance so far (heap initialisation: (1e10, start))
@@ -634,12 +624,316 @@ __global__ void __launch_bounds__(KNNW_WAVES * 64) knn_wave_kernel(int nsample, 
         const bool tie = lane > 0 && lane < nsample && bd == prev && bi != previ;
         if (ambiguous || __ballot(tie) != 0ull) {
             knn_literal_query(q, start, end, nsample, lane, xyz, new_xyz, hd, hi, cand_d, cand_i, idx, dist2, write_sqrt);
-            continue;
+            return;
         }
         if (lane < nsample) {
             idx[(size_t)q * nsample + lane] = bi;
             dist2[(size_t)q * nsample + lane] = write_sqrt ? sqrtf(bd) : bd;
         }
+}
+
+__global__ void __launch_bounds__(KNNW_WAVES * 64) knn_wave_kernel(int nsample, int nseg, const float* __restrict__ xyz,
+                                                                    const float* __restrict__ new_xyz, const int* __restrict__ offset,
+                                                                    const int* __restrict__ new_offset, int m_total, int* __restrict__ idx,
+                                                                    float* __restrict__ dist2, int write_sqrt) {
+    extern __shared__ __attribute__((aligned(16))) float smem_f[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float* hd = smem_f + wave * 2 * nsample;          // heap distances [k]   (literal path)
+    int* hi = (int*)(hd + nsample);                   // heap indices   [k]
+    float* cand_d = smem_f + KNNW_WAVES * 2 * nsample + wave * 128;   // candidates of the current chunk
+    int* cand_i = (int*)(cand_d + 64);
+    for (int q = blockIdx.x * KNNW_WAVES + wave; q < m_total; q += gridDim.x * KNNW_WAVES) {
+        int seg = 0;
+        while (seg < nseg - 1 && q >= new_offset[seg]) ++seg;
+        const int start = seg == 0 ? 0 : offset[seg - 1], end = offset[seg];
+        knn_wave_query(q, start, end, nsample, lane, xyz, new_xyz, hd, hi, cand_d, cand_i, idx, dist2, write_sqrt);
+    }
+}
+
+// ------------------------------------------------------------------------------------ kNN on a per-segment cell grid
+// The same results as knn_wave_kernel, bit for bit, from the points of a few cells around the query instead of the whole segment.
+//
+// Any-order rule.  knn_wave_query's sorted register list, fed with ANY superset of the true neighbours in ANY order, ends as the
+// reference's output unless a distance tied on the way: (a) a candidate is turned away with cd == top at its turn, (b) an eviction
+// happens while bd[k-2] == top and the two last entries are different points, (c) two adjacent final entries have equal distance and
+// are different points.  Each raises `ambiguous`, and an ambiguous query is redone by knn_wave_query (the full scan).
+//
+// Stop rule.  A point's cell on an axis is floor(u), u = fl(fl(x - origin) * inv_h), clamped into 0 .. dim-1.  u is monotone in x
+// (a subtraction and a multiplication by a positive constant, each rounded once), so every support point has 0 <= u and floor(u) <=
+// dim-1 (dim = floor(u(max)) + 1): only a QUERY is ever clamped.  Let every cell within Chebyshev ring rho of the query's cell be
+// visited and p an unvisited point: on some axis its cell differs from the query's by >= rho + 1.  Above: u_p >= c_q + rho + 1 and
+// u_q < c_q + 1 (a query clamped from below has u_q < 0; one clamped from above cannot have a cell above it), so u_p - u_q > rho.
+// Below: u_p < c_p + 1 <= c_q - rho and u_q >= c_q (clamped from above: u_q >= dim > c_q), so again u_q - u_p > rho.  Against the
+// real quotient t = (x - origin) / h, u is off by three roundings, |u - t| <= 3 * 2^-24 * |t|; where the bound is used |t| <= dim + 1
+// <= 1025 (a clamped query is only moved TOWARDS the box, which shrinks the bound), so |u - t| < 2^-13 for the point and the query
+// each: |x_p - x_q| > (rho - 2^-12) h.  KNNG_DELTA = 2^-8 leaves a factor 16.  etch_sqdist rounds dx once (relative 2^-24, 2^-23
+// after squaring), the square once and the two sums once each: computed d2 >= real d2 * (1 - 2^-21); the bound itself takes three
+// roundings; KNNG_MARGIN = 1 - 2^-10 covers all of it 1000 times over.  So: stop once top < fl(((rho - delta) h)^2 margin) --
+// strictly, so that no unvisited point can even tie with the k-th -- and never before rho = 1.  h lies in [1e-15, 1e15] (else the
+// segment is not eligible), so none of these squares leaves the normal range.
+#define KNNG_MAX_CELLS 16384
+#define KNNG_MAX_DIM 1024
+#define KNNG_MAX_POINTS 16384
+#define KNNG_RMAX 7
+#define KNNG_HDR 16                       // words per segment: origin[3], h, inv_h (f32); dims[3], eligible, cells (i32)
+#define KNNG_DELTA 0.00390625f            // 2^-8
+#define KNNG_MARGIN 0.9990234375f         // 1 - 2^-10
+#define KNNG_BUILD_THREADS 1024
+
+__device__ __forceinline__ int knng_cell(float x, float o, float inv_h, int dim) {
+    const float u = (x - o) * inv_h;
+    return (int)fminf(fmaxf(floorf(u), 0.f), (float)(dim - 1));     // fmaxf drops a NaN: the index stays in the table
+}
+
+// inclusive prefix sum over the wave on the VALU (DPP row shifts + row broadcasts, as etch_wave_max_u64_dpp)
+__device__ __forceinline__ int knng_wave_scan(int v) {
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);      // row_shr:1 (out-of-row lanes read 0)
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);      // row_shr:2
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);      // row_shr:4
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);      // row_shr:8 -> the prefix within each row of 16
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);     // row_bcast:15 into rows 1 and 3
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);     // row_bcast:31 into rows 2 and 3
+    return v;
+}
+
+// One workgroup per segment: bounding box, cell size, counting sort of the points by linear cell id (z fastest).
+__global__ void __launch_bounds__(KNNG_BUILD_THREADS) knn_grid_build_kernel(int min_points, int cell_stride, const float* __restrict__ xyz,
+                                                                            const int* __restrict__ offset, float4* __restrict__ pts,
+                                                                            int* __restrict__ cell_start, int* __restrict__ header) {
+    extern __shared__ __attribute__((aligned(16))) int hist[];          // [cell_stride]
+    __shared__ float red[6][16];
+    __shared__ int s_bad[16], s_wsum[16];
+    __shared__ float s_geo[5];
+    __shared__ int s_dim[5];
+    const int seg = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int start = seg == 0 ? 0 : offset[seg - 1], end = offset[seg], n = end - start;
+    int* hdr = header + (size_t)seg * KNNG_HDR;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    int bad = 0;
+    for (int i = start + tid; i < end; i += KNNG_BUILD_THREADS)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float v = xyz[(size_t)i * 3 + a];
+            bad |= !isfinite(v);
+            lo[a] = fminf(lo[a], v); hi[a] = fmaxf(hi[a], v);
+        }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        float l = lo[a], h = hi[a];
+        for (int o = 32; o > 0; o >>= 1) { l = fminf(l, __shfl_xor(l, o)); h = fmaxf(h, __shfl_xor(h, o)); }
+        if (lane == 0) { red[a][wave] = l; red[3 + a][wave] = h; }
+    }
+    const int wbad = __ballot(bad) != 0ull;
+    if (lane == 0) s_bad[wave] = wbad;
+    __syncthreads();
+    if (tid == 0) {
+        float mn[3], mx[3], ext[3];
+        int anybad = 0;
+        for (int w = 0; w < 16; ++w) anybad |= s_bad[w];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            float l = red[a][0], h = red[3 + a][0];
+            for (int w = 1; w < 16; ++w) { l = fminf(l, red[a][w]); h = fmaxf(h, red[3 + a][w]); }
+            mn[a] = l; mx[a] = h; ext[a] = h - l;
+        }
+        const float emax = fmaxf(ext[0], fmaxf(ext[1], ext[2]));
+        bool ok = !anybad && n >= min_points && n >= 17 && n <= KNNG_MAX_POINTS && emax > 0.f && isfinite(emax);
+        int cap = 4 * (n < KNNG_MAX_CELLS ? n : KNNG_MAX_CELLS);
+        if (cap > KNNG_MAX_CELLS) cap = KNNG_MAX_CELLS;
+        if (cap > cell_stride - 1) cap = cell_stride - 1;
+        float h = 0.f, inv_h = 0.f;
+        int dim[3] = {1, 1, 1}, cells = 0;
+        if (ok) {
+            // the finest cubic cell with at most `cap` cells on the box (about four per point: one to three points per occupied cell of
+            // a blob or a surface); an axis thinner than 1/1024 of the widest counts as that thick
+            const float thin = emax * (1.f / 1024.f);
+            h = cbrtf(fmaxf(ext[0], thin)) * cbrtf(fmaxf(ext[1], thin)) * cbrtf(fmaxf(ext[2], thin)) / cbrtf((float)cap);
+            h = fmaxf(h, emax * (1.f / 1023.f));
+            ok = false;
+            for (int it = 0; it < 64; ++it) {                       // the +1 per axis overshoots the cap: grow h by 1/16 until it fits
+                inv_h = 1.f / h;
+                bool fits = h >= 1e-15f && h <= 1e15f && isfinite(inv_h);
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    const float u = floorf((mx[a] - mn[a]) * inv_h);
+                    fits = fits && u < (float)KNNG_MAX_DIM;
+                    dim[a] = fits ? (int)u + 1 : 1;
+                }
+                cells = dim[0] * dim[1] * dim[2];                   // <= 2^30
+                if (fits && cells <= cap) { ok = true; break; }
+                h *= 1.0625f;
+            }
+        }
+        s_geo[0] = mn[0]; s_geo[1] = mn[1]; s_geo[2] = mn[2]; s_geo[3] = h; s_geo[4] = inv_h;
+        s_dim[0] = dim[0]; s_dim[1] = dim[1]; s_dim[2] = dim[2]; s_dim[3] = ok ? 1 : 0; s_dim[4] = ok ? cells : 0;
+        for (int a = 0; a < 5; ++a) { hdr[a] = __float_as_int(s_geo[a]); hdr[5 + a] = s_dim[a]; }
+    }
+    __syncthreads();
+    if (!s_dim[3]) return;                                          // not eligible: the queries of this segment take the full scan
+    const float ox = s_geo[0], oy = s_geo[1], oz = s_geo[2], inv_h = s_geo[4];
+    const int dx = s_dim[0], dy = s_dim[1], dz = s_dim[2], cells = s_dim[4];
+    for (int c = tid; c <= cells; c += KNNG_BUILD_THREADS) hist[c] = 0;
+    __syncthreads();
+    for (int i = start + tid; i < end; i += KNNG_BUILD_THREADS) {
+        const int c = (knng_cell(xyz[(size_t)i * 3], ox, inv_h, dx) * dy + knng_cell(xyz[(size_t)i * 3 + 1], oy, inv_h, dy)) * dz +
+                      knng_cell(xyz[(size_t)i * 3 + 2], oz, inv_h, dz);
+        atomicAdd(&hist[c], 1);
+    }
+    __syncthreads();
+    // exclusive prefix sum of the counts: a contiguous run of cells per thread, a wave scan of the run totals, the 16 wave totals
+    const int per = (cells + KNNG_BUILD_THREADS - 1) / KNNG_BUILD_THREADS;     // <= 16
+    const int c0 = tid * per, c1 = min(c0 + per, cells);
+    int sum = 0;
+    for (int c = c0; c < c1; ++c) sum += hist[c];
+    int incl = sum;
+    for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(incl, o); if (lane >= o) incl += v; }
+    if (lane == 63) s_wsum[wave] = incl;
+    __syncthreads();
+    int base = incl - sum;
+    for (int w = 0; w < wave; ++w) base += s_wsum[w];
+    int* cs = cell_start + (size_t)seg * cell_stride;
+    for (int c = c0; c < c1; ++c) { const int v = hist[c]; hist[c] = base; cs[c] = base; base += v; }
+    if (tid == 0) cs[cells] = n;
+    __syncthreads();
+    for (int i = start + tid; i < end; i += KNNG_BUILD_THREADS) {
+        const float x = xyz[(size_t)i * 3], y = xyz[(size_t)i * 3 + 1], z = xyz[(size_t)i * 3 + 2];
+        const int c = (knng_cell(x, ox, inv_h, dx) * dy + knng_cell(y, oy, inv_h, dy)) * dz + knng_cell(z, oz, inv_h, dz);
+        const int pos = atomicAdd(&hist[c], 1);                     // within-cell order is free: no result depends on it
+        pts[start + pos] = make_float4(x, y, z, __int_as_float(i));
+    }
+}
+
+// One wave per query.  Shell by shell (the first one is the whole 3 x 3 x 3 block: no query stops before rho = 1) each lane takes one
+// z-column range of the shell -- rim columns whole, inner columns' two caps -- and reads its two cell-start entries; a wave prefix sum
+// strings the ranges into one candidate stream, which is tested 64 at a time like knn_wave_query's chunks.
+// counters (may be null): [0] answered from the grid; sent to the full scan because [1] the segment is not eligible, [2] nsample > 16,
+// [3] not finished after KNNG_RMAX shells, [4] a tie made the any-order list ambiguous.
+__global__ void __attribute__((amdgpu_waves_per_eu(8, 8))) __launch_bounds__(KNNW_WAVES * 64) knn_grid_kernel(int nsample, int nseg, const float* __restrict__ xyz,
+                                                                    const float* __restrict__ new_xyz, const int* __restrict__ offset,
+                                                                    const int* __restrict__ new_offset, int m_total,
+                                                                    const float4* __restrict__ pts, const int* __restrict__ cell_start,
+                                                                    int cell_stride, const int* __restrict__ header, int* __restrict__ idx,
+                                                                    float* __restrict__ dist2, int write_sqrt, int* __restrict__ counters) {
+    extern __shared__ __attribute__((aligned(16))) float smem_f[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float* hd = smem_f + wave * 2 * nsample;
+    int* hi = (int*)(hd + nsample);
+    float* cand_d = smem_f + KNNW_WAVES * 2 * nsample + wave * 128;
+    int* cand_i = (int*)(cand_d + 64);
+    // "near": within the radius that holds about 1.5 nsample points at one point per cell, (4/3) pi r^3 = 1.5 nsample cells -- a heuristic for the order only
+    float near_k = cbrtf(0.358f * (float)nsample);
+    near_k *= near_k;
+    for (int q = blockIdx.x * KNNW_WAVES + wave; q < m_total; q += gridDim.x * KNNW_WAVES) {
+        int seg = 0;                                     // knn_wave_kernel's scan, as a binary search: the number of new_offset[0 .. nseg-2] <= q
+        for (int len = nseg - 1; len > 0;) {
+            const int half = len >> 1;
+            if (q >= new_offset[seg + half]) { seg += half + 1; len -= half + 1; }
+            else len = half;
+        }
+        const int start = seg == 0 ? 0 : offset[seg - 1], end = offset[seg];
+        const int* hdr = header + (size_t)seg * KNNG_HDR;
+        int cause = nsample > 16 ? 2 : (hdr[8] ? 0 : 1);
+        float bd = 1e10f;
+        int bi = start;
+        if (cause == 0) {
+            const float qx = new_xyz[(size_t)q * 3], qy = new_xyz[(size_t)q * 3 + 1], qz = new_xyz[(size_t)q * 3 + 2];
+            const float h = __int_as_float(hdr[3]), inv_h = __int_as_float(hdr[4]);
+            const int dimx = hdr[5], dimy = hdr[6], dimz = hdr[7];
+            const int ix = knng_cell(qx, __int_as_float(hdr[0]), inv_h, dimx), iy = knng_cell(qy, __int_as_float(hdr[1]), inv_h, dimy),
+                      iz = knng_cell(qz, __int_as_float(hdr[2]), inv_h, dimz);
+            const int* cs = cell_start + (size_t)seg * cell_stride;
+            const float near2 = near_k * h * h;
+            float top = 1e10f;
+            bool ambiguous = false, done = false;
+            for (int rho = 1; rho <= KNNG_RMAX && !done && !ambiguous; ++rho) {
+                const int side = 2 * rho + 1, inner = 2 * rho - 1;
+                const int nranges = rho == 1 ? 9 : 8 * rho + 2 * inner * inner;
+                const float inv_inner = 1.f / (float)inner;
+                for (int r0 = 0; r0 < nranges; r0 += 64) {
+                    const int r = r0 + lane;
+                    int s = 0, cnt = 0;
+                    if (r < nranges) {
+                        int ddx, ddy, za = iz - rho, zb = iz + rho;
+                        if (rho == 1) { ddx = r / 3 - 1; ddy = r % 3 - 1; }
+                        else if (r < side) { ddx = -rho; ddy = r - rho; }
+                        else if (r < 2 * side) { ddx = rho; ddy = r - side - rho; }
+                        else if (r < 8 * rho) { const int t = r - 2 * side; ddy = (t & 1) ? rho : -rho; ddx = (t >> 1) - (rho - 1); }
+                        else {
+                            const int t = r - 8 * rho, j = t >> 1;
+                            const int jq = (int)(((float)j + 0.5f) * inv_inner);           // j / inner, exact for these small integers
+                            ddx = jq - (rho - 1); ddy = j - jq * inner - (rho - 1);
+                            za = zb = (t & 1) ? iz + rho : iz - rho;
+                        }
+                        const int x = ix + ddx, y = iy + ddy;
+                        za = max(za, 0); zb = min(zb, dimz - 1);
+                        if (x >= 0 && x < dimx && y >= 0 && y < dimy && za <= zb) {
+                            const int col = (x * dimy + y) * dimz;
+                            s = cs[col + za];
+                            cnt = cs[col + zb + 1] - s;
+                        }
+                    }
+                    const int incl = knng_wave_scan(cnt);
+                    const int total = __builtin_amdgcn_readlane(incl, 63);
+                    for (int b = 0; b < total; b += 64) {
+                        const int t = b + lane;
+                        int j = 0;                                   // the range of candidate t: the number of lanes with incl <= t
+#pragma unroll
+                        for (int step = 32; step > 0; step >>= 1) { if (__shfl(incl, j + step - 1) <= t) j += step; }
+                        j = min(j, 63);
+                        const int excl = __shfl(incl - cnt, j), sj = __shfl(s, j);
+                        float d2 = 3e38f;
+                        int gi = 0;
+                        if (t < total) {
+                            const float4 P = pts[start + sj + (t - excl)];
+                            d2 = etch_sqdist(qx, qy, qz, P.x, P.y, P.z);
+                            gi = __float_as_int(P.w);
+                        }
+                        // the near candidates first (any order gives the same list): they fill the list, and most of the far ones then fail the
+                        // ballot instead of taking a turn each
+                        const bool near = d2 <= near2;
+                        for (int phase = 0; phase < 2; ++phase) {
+                            unsigned long long mask = __ballot(d2 <= top && near == (phase == 0));
+                            while (mask) {                               // wave-uniform
+                                const int e = __builtin_ctzll(mask);
+                                mask &= mask - 1ull;
+                                const float cd = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(d2), e));
+                                if (cd < top) {
+                                    if (nsample > 1) {
+                                        const float t2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bd), nsample - 2));
+                                        if (t2 == top && __builtin_amdgcn_readlane(bi, nsample - 1) != __builtin_amdgcn_readlane(bi, nsample - 2)) ambiguous = true;
+                                    }
+                                    const int ci = __builtin_amdgcn_readlane(gi, e);
+                                    const int pos = __popcll(__ballot(lane < nsample && bd <= cd));
+                                    const float pd = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(bd), 0x111, 0xf, 0xf, true));   // row_shr:1
+                                    const int pi = __builtin_amdgcn_update_dpp(0, bi, 0x111, 0xf, 0xf, true);
+                                    if (lane == pos) { bd = cd; bi = ci; }
+                                    else if (lane > pos) { bd = pd; bi = pi; }
+                                    top = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bd), nsample - 1));
+                                } else if (cd == top) {
+                                    ambiguous = true;                    // turned away on a tie: in index order it might have come first
+                                }
+                            }
+                        }
+                    }
+                }
+                const float rb = ((float)rho - KNNG_DELTA) * h;
+                if (top < rb * rb * KNNG_MARGIN) done = true;
+            }
+            if (ambiguous) cause = 4;
+            else if (!done) cause = 3;
+            else {
+                const float prev = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(bd), 0x111, 0xf, 0xf, true));
+                const int previ = __builtin_amdgcn_update_dpp(0, bi, 0x111, 0xf, 0xf, true);
+                const bool tie = lane > 0 && lane < nsample && bd == prev && bi != previ;
+                if (__ballot(tie) != 0ull) cause = 4;
+            }
+        }
+        if (cause != 0) knn_wave_query(q, start, end, nsample, lane, xyz, new_xyz, hd, hi, cand_d, cand_i, idx, dist2, write_sqrt);
+        else if (lane < nsample) {
+            idx[(size_t)q * nsample + lane] = bi;
+            dist2[(size_t)q * nsample + lane] = write_sqrt ? sqrtf(bd) : bd;
+        }
+        if (counters != nullptr && lane == 0) atomicAdd(&counters[cause], 1);
     }
 }
 
@@ -852,6 +1146,38 @@ int etch_knnquery_dev_bounded(int m, int nsample, int nseg, const float* xyz, co
 int etch_knnquery_dev(int m, int nsample, const float* xyz, const float* new_xyz, const int* offset, const int* new_offset, int* idx,
                       float* dist, int write_sqrt, void* stream) {
     return etch_knnquery_dev_bounded(m, nsample, 0x7fffffff, xyz, new_xyz, offset, new_offset, idx, dist, write_sqrt, stream);
+}
+
+// The cell grid of packed points for etch_knnquery_grid (one workgroup per segment, no host read).  pts (n, 4): x, y, z and the bits of the
+// global index per point in cell order; cell_start (nseg, cell_stride); header (nseg, 16) words.
+int etch_knn_grid_build(int nseg, int min_points, const float* xyz, const int* offset, float* pts, int* cell_start, int cell_stride, int* header,
+                        void* stream) {
+    if (nseg <= 0) return ETCH_OK;
+    if (!xyz || !offset || !pts || !cell_start || !header || cell_stride < 2 || cell_stride > KNNG_MAX_CELLS + 1) return ETCH_EINVAL;
+    const size_t lds = (size_t)cell_stride * sizeof(int);
+    if (lds + 1024 > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void*)knn_grid_build_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(knn_grid_build_kernel, dim3(nseg), dim3(KNNG_BUILD_THREADS), lds, (hipStream_t)stream, min_points, cell_stride, xyz, offset,
+                       (float4*)pts, cell_start, header);
+    ETCH_RETURN_IF_LAUNCH_FAILED();
+    return ETCH_OK;
+}
+
+int etch_knnquery_grid(int b, int m_total, int nsample, const float* xyz, const float* new_xyz, const int* offset, const int* new_offset,
+                       const float* pts, const int* cell_start, int cell_stride, const int* header, int* idx, float* dist, int write_sqrt,
+                       int* counters, void* stream) {
+    if (b <= 0 || m_total <= 0) return ETCH_OK;
+    if (nsample <= 0 || !pts || !cell_start || !header || cell_stride < 2 || cell_stride > KNNG_MAX_CELLS + 1) return ETCH_EINVAL;
+    if (nsample > 100) return ETCH_EUNSUPPORTED;
+    const size_t lds = (size_t)(KNNW_WAVES * 2 * nsample + KNNW_WAVES * 128) * 4;
+    long blocks = ((long)m_total + KNNW_WAVES - 1) / KNNW_WAVES;
+    if (blocks > 256 * 64) blocks = 256 * 64;
+    hipLaunchKernelGGL(knn_grid_kernel, dim3((unsigned)blocks), dim3(KNNW_WAVES * 64), lds, (hipStream_t)stream, nsample, b, xyz, new_xyz, offset,
+                       new_offset, m_total, (const float4*)pts, cell_start, cell_stride, header, idx, dist, write_sqrt, counters);
+    ETCH_RETURN_IF_LAUNCH_FAILED();
+    return ETCH_OK;
 }
 
 // ---- the reference's launchers under their own names and signatures (null stream, void, errors printed like grouping_cuda_kernel.cu:486-488)

@@ -87,13 +87,26 @@ def gather_rows(x, idx):
     return _memo(("rows", x.data_ptr(), idx.data_ptr()), (x, idx), lambda: ops.gather_rows(x, idx))
 
 
+def knn_grid(xyz, offset):
+    """The cell grid of (xyz, offset) for the kNN queries (ops.knn_grid_build), built once per scope on the stream of its first query: the
+    level's self query, the next level's down query and the interpolation onto the finer level all search the same support.  None when the
+    grid is switched off or no segment has a size it takes."""
+    oh = host_offsets(offset)
+    if not ops.KNN_GRID or not ops.knn_grid_eligible_sizes(oh):
+        return None
+    return _memo(("knngrid", xyz.data_ptr(), tuple(oh)), (xyz,), lambda: ops.knn_grid_build(xyz, offset))
+
+
 def knnquery(nsample, xyz, new_xyz, offset, new_offset):
     """pointops.py:32-45: -> idx (m,nsample) int32, dist (m,nsample) = sqrt(d2)."""
     if new_xyz is None:
         new_xyz = xyz
     oh, noh = host_offsets(offset), host_offsets(new_offset)
-    return _memo(("knn", nsample, xyz.data_ptr(), new_xyz.data_ptr(), tuple(oh), tuple(noh)), (xyz, new_xyz),
-                 lambda: ops.knnquery(nsample, xyz, new_xyz, offset, new_offset, noh))
+
+    def run():
+        grid = knn_grid(xyz, offset) if nsample <= 16 else None
+        return ops.knnquery(nsample, xyz, new_xyz, offset, new_offset, noh, grid=grid, offset_host=oh)
+    return _memo(("knn", nsample, xyz.data_ptr(), new_xyz.data_ptr(), tuple(oh), tuple(noh)), (xyz, new_xyz), run)
 
 
 def queryandgroup(nsample, xyz, new_xyz, feat, idx, offset, new_offset, use_xyz=True):

@@ -153,11 +153,54 @@ def _seg_max(offset_host):
     return mx
 
 
-def knnquery(nsample, xyz, new_xyz, offset, new_offset, new_offset_host=None, sqrt=True, wave_kernel=True):
+# kNN on a per-segment cell grid: the same idx / dist bit for bit.  KNN_GRID = False is the A/B partner and the tests' reference.
+KNN_GRID = os.environ.get("ETCH_KNN_GRID", "1") != "0"
+KNN_GRID_MIN_POINTS = 512        # smaller segments keep the full scan (a handful of 64-point chunks per query: nothing to save)
+KNN_GRID_MAX_POINTS = 16384      # as the library's KNNG_MAX_POINTS / KNNG_MAX_CELLS
+KNN_GRID_HEADER = 16
+
+
+class KnnGrid:
+    """The cell grid of one packed point tensor (ops.knn_grid_build): pts (n,4), cell_start (nseg, stride), header (nseg, 16)."""
+    __slots__ = ("pts", "cell_start", "header", "stride")
+
+    def __init__(self, pts, cell_start, header, stride):
+        self.pts, self.cell_start, self.header, self.stride = pts, cell_start, header, stride
+
+    def tensors(self):
+        return [self.pts, self.cell_start, self.header]
+
+
+def knn_grid_eligible_sizes(offset_host):
+    """True if any segment has a size the grid takes (eligibility is a function of a segment's own size, never of the batch)."""
+    prev = 0
+    for v in offset_host:
+        if KNN_GRID_MIN_POINTS <= int(v) - prev <= KNN_GRID_MAX_POINTS and int(v) - prev >= 17:
+            return True
+        prev = int(v)
+    return False
+
+
+def knn_grid_build(xyz, offset, min_points=None):
+    """Cell grid of packed xyz (n,3) + offset for knnquery(grid=...): one launch, no host read."""
+    _need(xyz, torch.float32, "xyz"), _need(offset, torch.int32, "offset")
+    n, nseg = xyz.shape[0], offset.numel()
+    stride = min(KNN_GRID_MAX_POINTS, 4 * max(int(n), 16)) + 1
+    pts = torch.empty((n, 4), dtype=torch.float32, device=xyz.device)
+    cell_start = torch.empty((nseg, stride), dtype=torch.int32, device=xyz.device)
+    header = torch.empty((nseg, KNN_GRID_HEADER), dtype=torch.int32, device=xyz.device)
+    _lib.call("etch_knn_grid_build", int(nseg), int(KNN_GRID_MIN_POINTS if min_points is None else min_points), xyz, offset, pts, cell_start, stride, header)
+    return KnnGrid(pts, cell_start, header, stride)
+
+
+def knnquery(nsample, xyz, new_xyz, offset, new_offset, new_offset_host=None, sqrt=True, wave_kernel=True, grid=None, offset_host=None, counters=None):
     """pointops.knnquery (pointops.py:32-45): -> idx (m,nsample) int32, dist (m,nsample) = sqrt(d2).
 
     `new_offset_host` (list of ints) avoids a device->host sync for the grid size; if omitted it is
-    read back from `new_offset` (one sync, like the reference's own .item() calls)."""
+    read back from `new_offset` (one sync, like the reference's own .item() calls).
+    With KNN_GRID on, the wave kernel and nsample <= 16 the query runs on the cell grid of (xyz, offset): `grid` (knn_grid_build) if the caller
+    has one, else built here; `offset_host`, when given, lets a call whose segments are all too small or too large skip the grid.  `counters`
+    (5) int32 receives the number of queries per outcome (etch_knnquery_grid) and sends the call to the grid kernel whatever nsample is."""
     if new_xyz is None:
         new_xyz = xyz
     _need(xyz, torch.float32, "xyz"), _need(new_xyz, torch.float32, "new_xyz")
@@ -167,6 +210,17 @@ def knnquery(nsample, xyz, new_xyz, offset, new_offset, new_offset_host=None, sq
     m = new_xyz.shape[0]
     idx = torch.empty((m, nsample), dtype=torch.int32, device=xyz.device)
     dist = torch.empty((m, nsample), dtype=torch.float32, device=xyz.device)
+    use_grid = KNN_GRID and wave_kernel and m > 0 and xyz.shape[0] > 0 and offset.numel() == len(new_offset_host) and (
+        counters is not None or grid is not None or (nsample <= 16 and (offset_host is None or knn_grid_eligible_sizes(offset_host))))
+    if use_grid:
+        if counters is not None:
+            _need(counters, torch.int32, "counters")
+            assert counters.numel() >= 5
+        if grid is None:
+            grid = knn_grid_build(xyz, offset)
+        _lib.call("etch_knnquery_grid", len(new_offset_host), int(m), int(nsample), xyz, new_xyz, offset, new_offset, grid.pts, grid.cell_start,
+                  int(grid.stride), grid.header, idx, dist, 1 if sqrt else 0, counters)
+        return idx, dist
     _lib.call("etch_knnquery", len(new_offset_host), _seg_max(new_offset_host), int(m) if wave_kernel else 0, int(nsample), xyz, new_xyz, offset, new_offset,
               idx, dist, 1 if sqrt else 0)
     return idx, dist

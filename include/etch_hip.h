@@ -87,6 +87,22 @@ int etch_knnquery_dev(int m, int nsample, const float* xyz, const float* new_xyz
 int etch_knnquery_dev_bounded(int m, int nsample, int nseg, const float* xyz, const float* new_xyz, const int* offset, const int* new_offset,
                               int* idx, float* dist, int write_sqrt, void* stream);
 
+/* kNN on a per-segment cell grid: etch_knnquery's results bit for bit, from the cells around each query.
+ * etch_knn_grid_build: packed xyz (n,3) + offset (nseg) -> pts (n,4) f32 = x, y, z, bits(global index) per point in cell order (z fastest),
+ * cell_start (nseg, cell_stride) i32 = first point of every cell relative to the segment, cells + 1 entries used, and header (nseg, 16) words =
+ * origin[3], h, 1/h (f32), dims[3], eligible, cells (i32).  One workgroup per segment, at most min(16 384, 4 n, cell_stride - 1) cells
+ * (2 <= cell_stride <= 16 385).  A segment is not eligible -- its queries take the full scan -- if it has fewer than max(min_points, 17) or
+ * more than 16 384 points, a non-finite coordinate, or no extent. */
+int etch_knn_grid_build(int nseg, int min_points, const float* xyz, const int* offset, float* pts, int* cell_start, int cell_stride, int* header,
+                        void* stream);
+/* etch_knnquery (wave-per-query form) over a grid built from the same xyz and offset.  A query goes to the full scan of etch_knnquery when its
+ * segment is not eligible, nsample > 16, it is not finished after 7 shells of cells, or a tied distance makes the any-order result ambiguous.
+ * counters (5) i32, may be NULL, are incremented by the number of queries answered from the grid [0] and sent to the full scan for each of
+ * these causes [1..4], in that order. */
+int etch_knnquery_grid(int b, int m_total, int nsample, const float* xyz, const float* new_xyz, const int* offset, const int* new_offset,
+                       const float* pts, const int* cell_start, int cell_stride, const int* header, int* idx, float* dist, int write_sqrt,
+                       int* counters, void* stream);
+
 /* ---- the reference's own launcher symbols --------------------------------------------------------------
  * Exactly the names and signatures the reference's host wrappers link against, so knnquery_cuda.cpp / sampling_cuda.cpp (and a
  * pointer-level wrapper of the vgtk kernels) build against libetch_hip.so unchanged.  Like the reference they launch on the NULL
