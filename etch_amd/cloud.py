@@ -6,11 +6,15 @@ handing it to the pipeline.
     remove_statistical_outliers(cloud, k=16, ratio=2.0)        keep m_i <= mean + ratio * std over the cloud
     remove_radius_outliers(cloud, radius, min_neighbours)      keep the points with enough neighbours within radius
     voxel_downsample(cloud, voxel)                             one centroid per occupied cell, in spatial (ix, iy, iz) order
-    prepare(cloud, N, keys, voxel=, stat=, radius=)            filters, voxel grid, bounding-box centre, stratified pick: the network's input
+    prepare(cloud, N, keys, voxel=, stat=, radius=, floor=, cluster=)   filters, floor, largest cluster, voxel grid, centre, pick: the network's input
+
+    fit_plane(cloud, threshold, keys, ...), remove_plane(...)  the dominant plane by RANSAC + one refit; drop it and what lies under it (section 22)
+    cluster(cloud, radius), keep_clusters(cloud, radius, ...)  Euclidean clusters = components of the radius graph; keep the largest
 
     python -m etch_amd.cloud --cloud_path scan.ply [--voxel V] [--outlier_k K --outlier_ratio R] [--outlier_radius r --outlier_min_neighbours m]
+                             [--floor_threshold T --floor_up X Y Z --floor_max_tilt DEG] [--cluster_radius R]
 
-Neighbours are rows of the same cloud only.  The kernels (csrc/cloud_filter.hip) are exact and defined in fp64; there is no CPU path."""
+Neighbours are rows of the same cloud only.  The kernels (csrc/cloud_filter.hip, csrc/cloud_isolate.hip) are exact and defined in fp64; there is no CPU path."""
 import argparse
 import math
 import os
@@ -197,12 +201,133 @@ def voxel_downsample(cloud, voxel):
     return _trim(out, total), count[:total]
 
 
-def prepare(cloud, N, keys, voxel=None, stat=None, radius=None, center=True):
-    """A raw cloud -> the network's input: the statistical filter (stat = (k, ratio)), the radius filter (radius = (r, min_neighbours)), the voxel
-    grid (voxel = the cell size), ops.bbox_center of what is left, and depth.pick's stratified pick of N points per cloud under `keys` -- with
-    a voxel grid the pick walks the cells in spatial order.  -> points (B,N,3) fp32, centres (B,3) fp64 (None without center), the cleaned
-    Cloud, which also carries .keep ((M) bool over the given rows: what the filters kept) and .stages (rows per cloud after each stage, a dict of
-    numpy arrays).  One readback for all stages; errors as in the single calls."""
+# ---------------------------------------------------------------------------------------------------------------- isolating the subject
+MAX_HYPOTHESES = 65536
+
+
+def _check_plane(B, threshold, keys, hypotheses=1024, up=None, max_tilt=None, min_inliers=3, refit=True):
+    """fit_plane's arguments, checked before any launch.  -> a dict: tau, keys (B) int64 numpy, H, up (a unit 3-tuple or None), cos_tilt,
+    min_inliers, refit."""
+    from . import mesh_io
+    tau = _check_positive(threshold, "threshold")
+    if int(hypotheses) != hypotheses or not 1 <= int(hypotheses) <= MAX_HYPOTHESES:
+        raise ValueError(f"hypotheses must be an integer in 1 .. {MAX_HYPOTHESES}, got {hypotheses}")
+    if int(min_inliers) != min_inliers or int(min_inliers) < 0:
+        raise ValueError(f"min_inliers must be a non-negative integer, got {min_inliers}")
+    cos_tilt = 0.0
+    if max_tilt is not None:
+        if not 0.0 <= float(max_tilt) <= 90.0:
+            raise ValueError(f"max_tilt must lie in [0, 90] degrees, got {max_tilt}")
+        if up is None:
+            raise ValueError("max_tilt needs up")
+        cos_tilt = 0.0 if float(max_tilt) == 90.0 else min(1.0, math.cos(math.radians(float(max_tilt))))
+    if up is not None:
+        u = np.asarray(up, np.float64).reshape(-1)
+        if u.shape != (3,) or not np.isfinite(u).all() or not float(np.sqrt((u * u).sum())) > 0.0:
+            raise ValueError(f"up must be three finite numbers, not all zero, got {up}")
+        u = u / np.sqrt((u * u).sum())
+        up = (float(u[0]), float(u[1]), float(u[2]))
+    return dict(tau=tau, keys=mesh_io._keys(keys, B), H=int(hypotheses), up=up, cos_tilt=cos_tilt, min_inliers=int(min_inliers), refit=bool(refit))
+
+
+def _plane(torch, ops, cloud, a):
+    """The launches of fit_plane on a checked argument dict.  -> plane (B,4), counts (B,3), found (B) int32, status (B) int32, on the device."""
+    pts, off = cloud.points, cloud.offsets
+    # the status words (NONFINITE) come from the bounding-box pass of the cell grid; it also writes M keys nobody reads here, which costs one pass
+    # over the rows, and with sort=False the cell size only scales those keys: any positive value does, 1.0 is one
+    _, status, _, _, _ = ops.cloud_cell_grid(pts, off, 1, 1, 1.0, sort=False)
+    key = torch.from_numpy(a["keys"]).to(pts.device)
+    planes, valid = ops.cloud_plane_hypotheses(pts, off, key, a["H"], up=a["up"], cos_tilt=a["cos_tilt"])
+    counts = ops.cloud_plane_score(pts, off, planes, a["tau"], valid=valid)
+    plane, best, found = ops.cloud_plane_select(planes, valid, counts, min_inliers=a["min_inliers"], has_up=a["up"] is not None)
+    if a["refit"]:
+        plane, best = ops.cloud_plane_refit(pts, off, plane, best, found, a["tau"])
+    return plane, best, found, status
+
+
+def fit_plane(cloud, threshold, keys, hypotheses=1024, up=None, max_tilt=None, min_inliers=3, refit=True):
+    """The dominant plane of every cloud by RANSAC: `hypotheses` planes through three rows drawn under the cloud's key (one integer per cloud, or
+    one for all), each scored by its rows within `threshold`; the one with the most inliers wins (a tie: the lowest hypothesis) and is refitted
+    once to its inliers by least squares.  up (with max_tilt in degrees) admits only planes whose normal lies within max_tilt of +-up and
+    orients them along up; without up the normal points to the side with more rows.  -> plane (B,4) fp64 = unit normal and d (s = n . x + d),
+    counts (B,3) int32 = inliers, above, below, found (B) bool -- False where the cloud has no plane with min_inliers inliers, which is a
+    result, not an error.  ValueError for bad arguments before any launch."""
+    o = _offsets(cloud)
+    a = _check_plane(len(o) - 1, threshold, keys, hypotheses, up, max_tilt, min_inliers, refit)
+    torch, ops, ctx = _ops(cloud)
+    with ctx:
+        plane, counts, found, status = _plane(torch, ops, cloud, a)
+    _raise_status("fit_plane", status.cpu().numpy())
+    return plane, counts, found.bool()
+
+
+def _raise_emptied(what, before, after):
+    gone = np.flatnonzero((np.asarray(after) == 0) & (np.asarray(before) > 0))
+    if len(gone):
+        raise _lib.EtchHipError(f"{what}: cloud {int(gone[0])}: no row is left")
+
+
+def remove_plane(cloud, threshold, keys, hypotheses=1024, up=None, max_tilt=None, min_inliers=3, refit=True):
+    """fit_plane, then keep_i = s_i > threshold where a plane was found: the floor and everything under it goes (and what stands closer than the
+    threshold to it).  -> (Cloud of the kept rows, keep (M) bool, plane (B,4), found (B) bool).  EtchHipError naming a cloud that loses every row."""
+    o = _offsets(cloud)
+    B = len(o) - 1
+    a = _check_plane(B, threshold, keys, hypotheses, up, max_tilt, min_inliers, refit)
+    torch, ops, ctx = _ops(cloud)
+    with ctx:
+        plane, _, found, status = _plane(torch, ops, cloud, a)
+        keep = ops.cloud_plane_keep(cloud.points, cloud.offsets, plane, found, a["tau"])
+        out = _compact(ops, cloud, keep)
+        host = torch.cat([status, out.offsets]).cpu().numpy()            # the one readback
+    _raise_status("remove_plane", host[:B])
+    _raise_emptied("remove_plane", np.diff(o), np.diff(host[B:].astype(np.int64)))
+    return _trim(out, int(host[-1])), keep[:int(o[-1])].bool(), plane, found.bool()
+
+
+def cluster(cloud, radius, brute=False):
+    """Euclidean clusters: the connected components of the graph that links two rows of a cloud at d2 <= radius * radius.  -> labels (M) int32 =
+    the lowest row of the row's component (local to its cloud), sizes (M) int32 = the rows of that component.  brute=True links by a scan of the
+    whole cloud: the same bits."""
+    radius = _check_positive(radius, "radius")
+    o = _offsets(cloud)
+    torch, ops, ctx = _ops(cloud)
+    with ctx:
+        label, size, status = ops.cloud_components(cloud.points, cloud.offsets, radius, brute=brute)
+    _raise_status("cluster", status.cpu().numpy())
+    return label[:int(o[-1])], size[:int(o[-1])]
+
+
+def _check_cluster(radius, min_points=1):
+    if int(min_points) != min_points or int(min_points) < 1:
+        raise ValueError(f"min_points must be a positive integer, got {min_points}")
+    return _check_positive(radius, "radius"), int(min_points)
+
+
+def keep_clusters(cloud, radius, largest=True, min_points=1):
+    """Keep the largest cluster of every cloud (a tie: the one with the lowest row), or with largest=False every cluster of at least min_points
+    rows.  -> (Cloud, keep (M) bool).  EtchHipError naming a cloud that loses every row."""
+    radius, min_points = _check_cluster(radius, min_points)
+    o = _offsets(cloud)
+    B = len(o) - 1
+    torch, ops, ctx = _ops(cloud)
+    with ctx:
+        label, size, status = ops.cloud_components(cloud.points, cloud.offsets, radius)
+        keep, _ = ops.cloud_component_keep(label, size, cloud.offsets, largest=largest, min_points=min_points)
+        out = _compact(ops, cloud, keep)
+        host = torch.cat([status, out.offsets]).cpu().numpy()
+    _raise_status("keep_clusters", host[:B])
+    _raise_emptied("keep_clusters", np.diff(o), np.diff(host[B:].astype(np.int64)))
+    return _trim(out, int(host[-1])), keep[:int(o[-1])].bool()
+
+
+def prepare(cloud, N, keys, voxel=None, stat=None, radius=None, center=True, floor=None, cluster=None):
+    """A raw cloud -> the network's input: the statistical filter (stat = (k, ratio)), the radius filter (radius = (r, min_neighbours)), the floor
+    (floor = a dict of fit_plane's arguments: threshold, keys, ...; keys defaults to `keys`), the largest cluster (cluster = (radius,
+    min_points)), the voxel grid (voxel = the cell size), ops.bbox_center of what is left, and depth.pick's stratified pick of N points per cloud
+    under `keys` -- with a voxel grid the pick walks the cells in spatial order.  -> points (B,N,3) fp32, centres (B,3) fp64 (None without
+    center), the cleaned Cloud, which also carries .keep ((M) bool over the given rows: what the stages kept), .stages (rows per cloud after each
+    stage, a dict of numpy arrays) and, with floor, .plane (B,4) fp64 and .plane_found (B) bool (both None without).  One readback for all
+    stages; errors as in the single calls."""
     from . import depth, mesh_io
     o = _offsets(cloud)
     B = len(o) - 1
@@ -210,6 +335,12 @@ def prepare(cloud, N, keys, voxel=None, stat=None, radius=None, center=True):
         stat = _check_stat(*stat)
     if radius is not None:
         radius = _check_radius(*radius)
+    if floor is not None:
+        floor = dict(floor)
+        floor.setdefault("keys", keys)
+        floor = _check_plane(B, **floor)
+    if cluster is not None:
+        cluster = _check_cluster(*cluster)
     if voxel is not None:
         voxel = _check_positive(voxel, "voxel")
     mesh_io._keys(keys, B)
@@ -219,6 +350,14 @@ def prepare(cloud, N, keys, voxel=None, stat=None, radius=None, center=True):
     dev = cloud.points.device
     words, names, cur = [], [], cloud
     keep = torch.ones((cloud.points.shape[0],), dtype=torch.bool, device=dev)
+    plane = found = None
+
+    def compose(keep, k):                                            # a kept row's rank among the kept rows is its row in the compacted cloud
+        if not names:
+            return k.bool()
+        rank = (torch.cumsum(keep.to(torch.int64), 0) - 1).clamp_(min=0)
+        return keep & k.bool()[rank]
+
     with ctx:
         if stat is not None:
             k1, _, status = _stat(ops, cur, *stat)
@@ -229,14 +368,24 @@ def prepare(cloud, N, keys, voxel=None, stat=None, radius=None, center=True):
         if radius is not None:
             count, status = ops.cloud_radius_count(cur.points, cur.offsets, radius[0])
             k2 = (count >= radius[1]).to(torch.int32)
-            if stat is not None:                                     # a kept row's rank among the kept rows is its row in the compacted cloud
-                rank = (torch.cumsum(keep.to(torch.int64), 0) - 1).clamp_(min=0)
-                keep = keep & k2.bool()[rank]
-            else:
-                keep = k2.bool()
+            keep = compose(keep, k2)
             cur = _compact(ops, cur, k2)
             words += [status, cur.offsets]
             names.append("radius")
+        if floor is not None:                                        # strays are gone: they vote for no plane
+            plane, _, found, status = _plane(torch, ops, cur, floor)
+            k3 = ops.cloud_plane_keep(cur.points, cur.offsets, plane, found, floor["tau"])
+            keep = compose(keep, k3)
+            cur = _compact(ops, cur, k3)
+            words += [status, cur.offsets]
+            names.append("floor")
+        if cluster is not None:                                      # the floor is gone: it no longer links the subject to what stands beside it
+            label, size, status = ops.cloud_components(cur.points, cur.offsets, cluster[0])
+            k4, _ = ops.cloud_component_keep(label, size, cur.offsets, largest=True, min_points=cluster[1])
+            keep = compose(keep, k4)
+            cur = _compact(ops, cur, k4)
+            words += [status, cur.offsets]
+            names.append("cluster")
         if voxel is not None:
             cur, _, status = _voxel(ops, cur, voxel)
             words += [status, cur.offsets]
@@ -249,6 +398,8 @@ def prepare(cloud, N, keys, voxel=None, stat=None, radius=None, center=True):
         part = host[i * (2 * B + 1):(i + 1) * (2 * B + 1)]
         _raise_status(f"prepare ({name})", part[:B])
         stages[name] = np.diff(part[B:].astype(np.int64))
+        if name in ("floor", "cluster"):
+            _raise_emptied(f"prepare ({name})", list(stages.values())[-2], stages[name])
     if host[-B:].any():
         raise _lib.EtchHipError(f"prepare: cloud {int(np.flatnonzero(host[-B:])[0])}: no point is left to pick from")
     total = int(host[-B - 1]) if names else int(o[-1])
@@ -259,6 +410,7 @@ def prepare(cloud, N, keys, voxel=None, stat=None, radius=None, center=True):
     else:
         cur = Cloud(cloud.points[:total], cloud.index[:total], cloud.offsets, cloud.count, None)
     cur.keep, cur.stages, cur.picked = keep[:int(o[-1])], stages, pixel             # picked (B,N) int32: the index of every picked row
+    cur.plane, cur.plane_found = plane, (found.bool() if found is not None else None)
     return p32, c, cur
 
 
@@ -285,12 +437,54 @@ def filter_args(a):
     return ((a.outlier_k, a.outlier_ratio) if a.outlier_k else None, (a.outlier_radius, a.outlier_min_neighbours) if a.outlier_radius > 0.0 else None)
 
 
+def add_isolate_flags(p):
+    """The flags that isolate the subject, shared like the cleaning flags; all default to off."""
+    p.add_argument("--floor_threshold", type=float, default=0.0, help="remove the floor: fit a plane by RANSAC and drop what lies closer than T metres "
+                   "to it or under it; 0 = off")
+    p.add_argument("--floor_hypotheses", type=int, default=1024, help=f"floor: RANSAC hypotheses (1 .. {MAX_HYPOTHESES})")
+    p.add_argument("--floor_up", type=float, nargs=3, metavar=("X", "Y", "Z"), default=None, help="floor: the up direction; the floor's normal points along it")
+    p.add_argument("--floor_max_tilt", type=float, default=None, help="floor: with --floor_up, admit only planes within DEG degrees of horizontal")
+    p.add_argument("--floor_min_inliers", type=int, default=3, help="floor: a plane with fewer inliers is no floor, and nothing is removed")
+    p.add_argument("--cluster_radius", type=float, default=0.0, help="keep the largest Euclidean cluster: points closer than R metres are linked; 0 = off")
+    p.add_argument("--cluster_min_points", type=int, default=1, help="cluster: the rows the largest cluster must have")
+
+
+def check_isolate_flags(p, a):
+    if a.floor_threshold < 0.0 or not math.isfinite(a.floor_threshold):
+        p.error("--floor_threshold must be positive and finite")
+    if not 1 <= a.floor_hypotheses <= MAX_HYPOTHESES:
+        p.error(f"--floor_hypotheses must lie in 1 .. {MAX_HYPOTHESES}")
+    if a.floor_up is not None and (not all(math.isfinite(x) for x in a.floor_up) or not any(a.floor_up)):
+        p.error("--floor_up must be three finite numbers, not all zero")
+    if a.floor_max_tilt is not None and (a.floor_up is None or not 0.0 <= a.floor_max_tilt <= 90.0):
+        p.error("--floor_max_tilt needs --floor_up and must lie in [0, 90]")
+    if a.floor_min_inliers < 0:
+        p.error("--floor_min_inliers must not be negative")
+    if a.cluster_radius < 0.0 or not math.isfinite(a.cluster_radius) or a.cluster_min_points < 1:
+        p.error("--cluster_radius must be positive and finite, --cluster_min_points at least 1")
+
+
+def isolate_args(a):
+    """The flags as prepare()'s floor= and cluster=."""
+    floor = dict(threshold=a.floor_threshold, hypotheses=a.floor_hypotheses, up=a.floor_up, max_tilt=a.floor_max_tilt,
+                 min_inliers=a.floor_min_inliers) if a.floor_threshold > 0.0 else None
+    return floor, (a.cluster_radius, a.cluster_min_points) if a.cluster_radius > 0.0 else None
+
+
+def isolate_report(clean):
+    """What the floor stage adds to a command's report: {} without it."""
+    if clean.plane is None:
+        return {}
+    return {"plane": clean.plane.cpu().numpy(), "plane_found": clean.plane_found.cpu().numpy()}
+
+
 def build_parser():
     from .inference_demo import add_flags
     p = argparse.ArgumentParser(prog="python -m etch_amd.cloud", description="Fit SMPL to a raw point cloud", conflict_handler="resolve")
     p.add_argument("--cloud_path", type=str, required=True, help="the cloud: .ply, .obj (vertices), .npy / .npz ((M,3)), .xyz / .txt (three columns)")
     p.add_argument("--voxel", type=float, default=0.0, help="voxel-grid down-sampling before the pick: the cell size in metres; 0 = off")
     add_filter_flags(p)
+    add_isolate_flags(p)
     add_flags(p)
     p.add_argument("--chamfer_refine", type=str, nargs="?", const="partial", default="none", choices=["none", "both", "partial", "clutter"],
                    help="refine the body against the whole cleaned cloud after the marker fit; without a value: partial")
@@ -301,6 +495,7 @@ def parse_args(argv=None):
     p = build_parser()
     a = p.parse_args(argv)
     check_filter_flags(p, a)
+    check_isolate_flags(p, a)
     if a.voxel < 0.0 or not math.isfinite(a.voxel):
         p.error("--voxel must be positive and finite")
     if a.num_point < 1:
@@ -319,12 +514,14 @@ def main(argv=None):
     if getattr(args, "ingest", "host") == "device":
         export = mesh_io.write_obj
     stat, radius = filter_args(args)
-    p32, c, clean = prepare(pack([raw], args.device), args.num_point, [args.seed], voxel=args.voxel if args.voxel > 0.0 else None, stat=stat, radius=radius)
+    floor, cluster = isolate_args(args)
+    p32, c, clean = prepare(pack([raw], args.device), args.num_point, [args.seed], voxel=args.voxel if args.voxel > 0.0 else None, stat=stat, radius=radius,
+                            floor=floor, cluster=cluster)
     points, center, cleaned = p32[0].cpu().numpy(), c[0].cpu().numpy(), clean.points.cpu().numpy()
     name = os.path.splitext(os.path.basename(args.cloud_path))[0]
     stages = {f"rows_{k}": v for k, v in clean.stages.items()}
     np.savez(os.path.join(args.output_folder, f"{name}_cloud.npz"), keep=clean.keep.cpu().numpy(), center=center, points=points,
-             removed=np.int64(len(raw) - int(clean.keep.sum())), rows_output=np.array([len(cleaned)]), **stages)
+             removed=np.int64(len(raw) - int(clean.keep.sum())), rows_output=np.array([len(cleaned)]), **stages, **isolate_report(clean))
     if args.chamfer_refine != "none":
         demo._refine_and_save(args, model, points, Mesh(cleaned - center, np.zeros((0, 3), np.int64)), center, name, export)
     else:

@@ -11,6 +11,7 @@
     python -m etch_amd.depth --depth_path D.npy --intrinsics FX FY CX CY [...]      fit a real depth frame
     python -m etch_amd.depth --scan_path S.obj --view_azimuth DEG [...]             fit a virtual view of a mesh
     ... --outlier_k K --outlier_ratio R / --outlier_radius r --outlier_min_neighbours m   drop flying pixels first (etch_amd.cloud, section 19)
+    ... --floor_threshold T [--floor_up X Y Z --floor_max_tilt DEG] / --cluster_radius R  drop the floor, keep the largest cluster (section 22)
 
 The kernels are bit-defined; there is no CPU path."""
 import argparse
@@ -331,6 +332,8 @@ def build_parser():
     add_flags(p)
     from .cloud import add_filter_flags
     add_filter_flags(p)                                          # flying pixels: clean the back-projected cloud before the pick (section 19)
+    from .cloud import add_isolate_flags
+    add_isolate_flags(p)                                         # the floor and what stands beside the subject (section 22)
     # the same flag with a default mode: a single view is a partial scan, so a bare --chamfer_refine is the one-sided scan -> body refinement
     p.add_argument("--chamfer_refine", type=str, nargs="?", const="partial", default="none", choices=["none", "both", "partial", "clutter"],
                    help="refine the body against the whole visible cloud after the marker fit; without a value: partial")
@@ -364,18 +367,23 @@ def parse_args(argv=None):
         p.error("--num_point must be at least 1")
     from .cloud import check_filter_flags
     check_filter_flags(p, a)
+    from .cloud import check_isolate_flags
+    check_isolate_flags(p, a)
     return a
 
 
-def view_points(args, device):
+def view_points(args, device, with_report=False):
     """The frame or the virtual view of `args` -> points (N,3) float32 numpy centred on the visible cloud, the centre, the visible cloud (M,3)
-    float64 numpy (uncentred), the depth map (H,W) float64 numpy, the Camera, picked pixels (N), name."""
+    float64 numpy (uncentred), the depth map (H,W) float64 numpy, the Camera, picked pixels (N), name; with_report=True
+    appends what the floor and cluster stages report ({} without them)."""
     import torch
 
     from . import cloud as C
     from . import mesh_io, ops
     stat, radius = C.filter_args(args) if hasattr(args, "outlier_k") else (None, None)
-    filtered = stat is not None or radius is not None
+    floor, cluster = C.isolate_args(args) if hasattr(args, "floor_threshold") else (None, None)
+    filtered = stat is not None or radius is not None or floor is not None or cluster is not None
+    report = {}
     if args.depth_path is not None:
         frame = load_depth(args.depth_path, args.depth_scale)
         R, t = load_extrinsics(args.extrinsics) if args.extrinsics else (None, None)
@@ -385,8 +393,8 @@ def view_points(args, device):
         cloud = _unproject(depth, cam.row()[None], near, far, device)
         if filtered:
             # the outlier filters run on the back-projected cloud; its index (the pixel) travels through the compaction
-            pts, c, clean = C.prepare(cloud, args.num_point, [args.seed], stat=stat, radius=radius)
-            vis, pixel = clean.points, clean.picked
+            pts, c, clean = C.prepare(cloud, args.num_point, [args.seed], stat=stat, radius=radius, floor=floor, cluster=cluster)
+            vis, pixel, report = clean.points, clean.picked, _isolate_report(C, clean)
         else:
             with torch.cuda.device(device):
                 c = ops.bbox_center(cloud.points, cloud.offsets)
@@ -403,13 +411,21 @@ def view_points(args, device):
         if filtered:
             (depth, _, _, _, rstatus, _), rows, dev = _render([mesh], [cam], None, False, 0.05, device)
             _raise_status("render", rstatus.cpu().numpy())
-            pts, c, clean = C.prepare(_unproject(depth, rows, 0.05, math.inf, dev), args.num_point, [args.seed], stat=stat, radius=radius)
-            vis, pixel = clean.points, clean.picked
+            pts, c, clean = C.prepare(_unproject(depth, rows, 0.05, math.inf, dev), args.num_point, [args.seed], stat=stat, radius=radius, floor=floor,
+                                      cluster=cluster)
+            vis, pixel, report = clean.points, clean.picked, _isolate_report(C, clean)
         else:
             pv = partial_view_points([mesh], [cam], args.num_point, [args.seed], center=True, device=device)
             pts, c, vis, depth, pixel = pv.points, pv.centers, pv.cloud.points, pv.cloud.depth, pv.pixel
         name = os.path.splitext(os.path.basename(args.scan_path))[0]
-    return (pts[0].cpu().numpy(), c[0].cpu().numpy(), vis.cpu().numpy(), depth[0].cpu().numpy(), cam, pixel[0].cpu().numpy(), name)
+    out = (pts[0].cpu().numpy(), c[0].cpu().numpy(), vis.cpu().numpy(), depth[0].cpu().numpy(), cam, pixel[0].cpu().numpy(), name)
+    return out + (report,) if with_report else out
+
+
+def _isolate_report(C, clean):
+    """What the floor and cluster stages add to <name>_view.npz: the plane and the rows after each of the two stages; {} without them."""
+    rows = {f"rows_{k}": v for k, v in clean.stages.items() if k in ("floor", "cluster")}
+    return {**C.isolate_report(clean), **rows}
 
 
 def main(argv=None):
@@ -422,9 +438,9 @@ def main(argv=None):
     export = Mesh.export
     if getattr(args, "ingest", "host") == "device":
         from .mesh_io import write_obj as export
-    points, center, visible, depth, cam, pixel, name = view_points(args, args.device)
+    points, center, visible, depth, cam, pixel, name, report = view_points(args, args.device, with_report=True)
     np.savez(os.path.join(args.output_folder, f"{name}_view.npz"), depth=depth, points=points, pixel=pixel, center=center, camera=cam.row(),
-             size=np.array([cam.height, cam.width]))
+             size=np.array([cam.height, cam.width]), **report)
     if args.chamfer_refine != "none":
         # the refinement's target is the whole visible cloud, centred like the points
         demo._refine_and_save(args, model, points, Mesh(visible - center, np.zeros((0, 3), np.int64)), center, name, export)

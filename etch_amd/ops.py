@@ -2230,3 +2230,116 @@ def cloud_voxel_grid(points, offsets, voxel):
               centroid, count, lowest, key)
     cell = torch.stack([key >> 42, (key >> 21) & (2 ** 21 - 1), key & (2 ** 21 - 1)], 1).to(torch.int32)
     return out_offsets, centroid, count, lowest, cell, status
+
+
+# ------------------------------------------------------------------ isolating the subject (csrc/cloud_isolate.hip)
+CLOUD_MAX_HYPOTHESES = 65536
+
+
+def _plane_args(planes, B, what):
+    _need(planes, torch.float64, "planes")
+    if planes.dim() != 3 or planes.shape[0] != B or planes.shape[2] != 4 or not 1 <= planes.shape[1] <= CLOUD_MAX_HYPOTHESES:
+        raise _lib.EtchHipError(f"{what}: planes must be ({B},H,4) with 1 <= H <= {CLOUD_MAX_HYPOTHESES}, got {tuple(planes.shape)}")
+    return planes.shape[1]
+
+
+def _check_tau(tau, what):
+    if not (float(tau) > 0.0 and math.isfinite(float(tau))):
+        raise _lib.EtchHipError(f"{what}: tau must be positive and finite, got {tau}")
+    return float(tau)
+
+
+def cloud_plane_hypotheses(points, offsets, keys, hypotheses, up=None, cos_tilt=0.0):
+    """etch_cloud_plane_hypotheses: keys (B) int64 holding the uint64 bits, up a UNIT vector of three floats or None.  -> planes (B,H,4) fp64,
+    valid (B,H) int32, both still on the device."""
+    B, _ = _cloud_args(points, offsets, "cloud_plane_hypotheses")
+    _need(keys, torch.int64, "keys")
+    H = int(hypotheses)
+    if keys.shape != (B,) or not 1 <= H <= CLOUD_MAX_HYPOTHESES:
+        raise _lib.EtchHipError(f"cloud_plane_hypotheses: keys must be ({B},) and 1 <= hypotheses <= {CLOUD_MAX_HYPOTHESES}")
+    u = (0.0, 0.0, 0.0) if up is None else tuple(float(x) for x in up)
+    if len(u) != 3 or not all(math.isfinite(x) for x in u) or not 0.0 <= float(cos_tilt) <= 1.0:
+        raise _lib.EtchHipError("cloud_plane_hypotheses: up must be three finite numbers and cos_tilt lie in [0, 1]")
+    planes = torch.empty((B, H, 4), dtype=torch.float64, device=points.device)
+    valid = torch.empty((B, H), dtype=torch.int32, device=points.device)
+    _lib.call("etch_cloud_plane_hypotheses", int(B), H, points, offsets, keys, int(up is not None), u[0], u[1], u[2], float(cos_tilt), planes, valid)
+    return planes, valid
+
+
+def cloud_plane_score(points, offsets, planes, tau, valid=None):
+    """etch_cloud_plane_score for ANY planes (B,H,4): -> counts (B,H,3) int32 = inliers, above, below; valid (B,H) int32 or None."""
+    B, M = _cloud_args(points, offsets, "cloud_plane_score")
+    H, tau = _plane_args(planes, B, "cloud_plane_score"), _check_tau(tau, "cloud_plane_score")
+    if valid is not None and _need(valid, torch.int32, "valid").shape != (B, H):
+        raise _lib.EtchHipError(f"cloud_plane_score: valid must be ({B},{H})")
+    counts = torch.empty((B, H, 3), dtype=torch.int32, device=points.device)
+    _lib.call("etch_cloud_plane_score", int(B), int(M), int(H), tau, points, offsets, planes, valid, counts)
+    return counts
+
+
+def cloud_plane_select(planes, valid, counts, min_inliers=3, has_up=False):
+    """etch_cloud_plane_select: -> plane (B,4) fp64, counts (B,3) int32, found (B) int32."""
+    _need(valid, torch.int32, "valid"), _need(counts, torch.int32, "counts")
+    B = planes.shape[0] if planes.dim() == 3 else 0
+    H = _plane_args(planes, B, "cloud_plane_select")
+    if B < 1 or valid.shape != (B, H) or counts.shape != (B, H, 3):
+        raise _lib.EtchHipError(f"cloud_plane_select: valid must be ({B},{H}) and counts ({B},{H},3) with B >= 1")
+    plane = torch.empty((B, 4), dtype=torch.float64, device=planes.device)
+    best = torch.empty((B, 3), dtype=torch.int32, device=planes.device)
+    found = torch.empty((B,), dtype=torch.int32, device=planes.device)
+    _lib.call("etch_cloud_plane_select", int(B), int(H), int(bool(has_up)), int(min_inliers), planes, valid, counts, plane, best, found)
+    return plane, best, found
+
+
+def _one_plane_args(points, offsets, plane, found, what):
+    B, M = _cloud_args(points, offsets, what)
+    _need(plane, torch.float64, "plane"), _need(found, torch.int32, "found")
+    if plane.shape != (B, 4) or found.shape != (B,):
+        raise _lib.EtchHipError(f"{what}: plane must be ({B},4) and found ({B},)")
+    return B, M
+
+
+def cloud_plane_refit(points, offsets, plane, counts, found, tau):
+    """etch_cloud_plane_refit: one least-squares step on the inliers of every found plane.  -> new plane (B,4), new counts (B,3); the arguments
+    are left unchanged."""
+    B, _ = _one_plane_args(points, offsets, plane, found, "cloud_plane_refit")
+    if _need(counts, torch.int32, "counts").shape != (B, 3):
+        raise _lib.EtchHipError(f"cloud_plane_refit: counts must be ({B},3)")
+    plane, counts = plane.clone(), counts.clone()
+    _lib.call("etch_cloud_plane_refit", int(B), _check_tau(tau, "cloud_plane_refit"), points, offsets, found, plane, counts)
+    return plane, counts
+
+
+def cloud_plane_keep(points, offsets, plane, found, tau):
+    """keep (M) int32 = the rows more than tau above a found plane (every row of a cloud without one)."""
+    B, M = _one_plane_args(points, offsets, plane, found, "cloud_plane_keep")
+    keep = torch.zeros((M,), dtype=torch.int32, device=points.device)
+    _lib.call("etch_cloud_plane_keep", int(B), int(M), _check_tau(tau, "cloud_plane_keep"), points, offsets, plane, found, keep)
+    return keep
+
+
+def cloud_components(points, offsets, radius, brute=False):
+    """Connected components of the radius graph (d2 <= radius * radius) per cloud.  -> label (M) int32 = the lowest row of the row's component,
+    local to its cloud, size (M) int32 = the component's rows, status (B) int32."""
+    B, M = _cloud_args(points, offsets, "cloud_components")
+    if not (float(radius) > 0.0 and math.isfinite(float(radius))):
+        raise _lib.EtchHipError(f"cloud_components: radius must be positive and finite, got {radius}")
+    _, status, sp, sk, order = cloud_cell_grid(points, offsets, 1, 1, float(radius), sort=not brute)
+    dev = points.device
+    parent = torch.empty((M,), dtype=torch.int32, device=dev)
+    label = torch.zeros((M,), dtype=torch.int32, device=dev)
+    size = torch.zeros((M,), dtype=torch.int32, device=dev)
+    _lib.call("etch_cloud_components", int(B), int(M), float(radius), int(bool(brute)), points if brute else sp, sk, order, offsets, status, parent, label, size)
+    return label, size, status
+
+
+def cloud_component_keep(label, size, offsets, largest=True, min_points=1):
+    """keep (M) int32 = size >= min_points and (not largest or label == the largest component's, a tie to the lowest label); winner (B) int32."""
+    _need(label, torch.int32, "label"), _need(size, torch.int32, "size"), _need(offsets, torch.int32, "offsets")
+    B = offsets.numel() - 1
+    if B < 1 or label.dim() != 1 or size.shape != label.shape or int(min_points) < 1:
+        raise _lib.EtchHipError("cloud_component_keep: label and size must be (M,), offsets (B+1) with B >= 1 and min_points >= 1")
+    keep = torch.zeros(label.shape, dtype=torch.int32, device=label.device)
+    winner = torch.empty((B,), dtype=torch.int32, device=label.device)
+    _lib.call("etch_cloud_component_keep", int(B), int(bool(largest)), int(min_points), label, size, offsets, winner, keep)
+    return keep, winner

@@ -1046,6 +1046,41 @@ int etch_cloud_compact(int B, const int* keep, const int* offsets, const double*
 int etch_cloud_voxel_grid(int B, const double* sorted_points, const long long* sorted_keys, const int* order, const int* offsets, const int* status,
                           void* workspace, int* cells, int* out_offsets, double* centroid, int* count, int* lowest, long long* cell_key, void* stream);
 
+/* ---- raw point clouds: isolating the subject -- RANSAC floor plane, Euclidean clusters (csrc/cloud_isolate.hip) ------- */
+
+/* H plane hypotheses per cloud, 1 <= H <= 65536: planes (B,H,4) fp64 = unit normal and d (a point x lies at s = ((nx x + ny y) + nz z) + d),
+ * valid (B,H) int32.  Hypothesis h of a cloud with n rows and key K: Philox4x32-10 with counter (h, 1, 0, 0) and key (low32 K, high32 K) -> r0..r3,
+ * rows i_a = (r_a n) >> 32 (a = 0, 1, 2); u = p[i1] - p[i0], v = p[i2] - p[i0], m = u x v (each component a difference of two rounded products),
+ * len2 = (mx mx + my my) + mz mz, normal = m / sqrt(len2), d = -((nx p0x + ny p0y) + nz p0z).  Invalid (four zeros, valid 0): two equal rows,
+ * !(len2 > 0), n < 3, or with has_up |normal . up| < cos_tilt; with has_up a plane is negated where normal . up < 0.  up must be a unit vector. */
+int etch_cloud_plane_hypotheses(int B, int H, const double* points, const int* offsets, const unsigned long long* keys, int has_up, double up_x,
+                                double up_y, double up_z, double cos_tilt, double* planes, int* valid, void* stream);
+/* counts (B,H,3) int32 = the rows of the cloud with |s| <= tau, with s > tau and with s < -tau, for ANY planes (B,H,4); a plane whose valid flag is 0
+ * scores 0, 0, 0 (valid may be NULL: every plane counts).  counts is zeroed by the call and filled with integer atomics. */
+int etch_cloud_plane_score(int B, int M, int H, double tau, const double* points, const int* offsets, const double* planes, const int* valid,
+                           int* counts, void* stream);
+/* The valid plane with the most inliers per cloud, a tie to the lowest h: plane (B,4), best_counts (B,3), found (B) int32.  Without has_up the
+ * winner is negated (and above / below swapped) where below > above.  found = 0, and zeros, where no plane is valid or inliers < min_inliers. */
+int etch_cloud_plane_select(int B, int H, int has_up, int min_inliers, const double* planes, const int* valid, const int* counts, double* plane,
+                            int* best_counts, int* found, void* stream);
+/* One least-squares step on the inliers of a found plane, in place: centroid c and the covariance of p - c over the rows with |s| <= tau (sums in
+ * an order n alone fixes, no float atomics), normal = the eigenvector of the smallest eigenvalue (cyclic Jacobi) on the side of the given normal,
+ * d = -(normal . c); counts are taken again against the new plane.  A plane with fewer than 3 inliers is left as it is. */
+int etch_cloud_plane_refit(int B, double tau, const double* points, const int* offsets, const int* found, double* plane, int* counts, void* stream);
+/* keep (M) int32 = s > tau for the rows of a cloud with a found plane, 1 for the rows of a cloud without, 0 behind the last cloud. */
+int etch_cloud_plane_keep(int B, int M, double tau, const double* points, const int* offsets, const double* plane, const int* found, int* keep,
+                          void* stream);
+/* Connected components of the graph that links rows i != j of one cloud with d2 <= radius radius: label (M) int32 = the lowest row of the row's
+ * component, local to its cloud, size (M) int32 = the component's rows, both by original row.  Needs the mode 1 keys of the same radius, sorted;
+ * brute != 0 scans the whole cloud instead: sorted_points is then the unsorted points and sorted_keys, order may be NULL.  parent (M) int32 is
+ * workspace.  Rows of a cloud with ETCH_CLOUD_STATUS_NONFINITE are not written. */
+int etch_cloud_components(int B, int M, double radius, int brute, const double* sorted_points, const long long* sorted_keys, const int* order,
+                          const int* offsets, const int* status, int* parent, int* label, int* size, void* stream);
+/* winner (B) int32 = the label of the largest component, a tie to the lowest label (-1 for an empty cloud); keep (M) int32 =
+ * size >= min_points and (largest == 0 or label == winner). */
+int etch_cloud_component_keep(int B, int largest, int min_points, const int* label, const int* size, const int* offsets, int* winner, int* keep,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif
