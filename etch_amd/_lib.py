@@ -2,7 +2,10 @@
 missing or a symbol is absent this raises, loudly.
 
 include/etch_hip.h is the one description of the C ABI: prototypes() parses it, _load() types every exported function from the parse, and
-call() is the one way the package calls the library."""
+call() is the one way the package calls the library.
+
+The library writes through raw pointers, which torch cannot see, and every cache of the package is keyed on (data_ptr, _version): a wrapper that
+lets the library write into a tensor it did not allocate itself calls wrote() on that tensor, after the launch or, where that is simpler, ahead of it."""
 import ctypes
 import os
 import re
@@ -140,6 +143,11 @@ def call(name, *args):
     if status and (streamed or status < 0):
         check(status, name)
     return status
+
+
+def wrote(*tensors):
+    """Announce a write through raw pointers: bumps `_version` of every tensor given (None is skipped), as an in-place torch op would have."""
+    torch.autograd.graph.increment_version([t for t in tensors if t is not None])
 
 
 def check(status, what):

@@ -11,6 +11,7 @@ import torch
 
 from . import _lib
 from . import ops
+from ._shared import Shared
 
 import os
 
@@ -37,6 +38,7 @@ def gemm_tn(A, B, out=None, accumulate=False):
     ws = torch.empty((_lib.call("etch_gemm_tn_workspace_floats", R, M, N),), dtype=torch.float32, device=A.device)
     counters = reduce_counters(A.device)
     _lib.call("etch_gemm_tn_fused", R, M, N, A, A.stride(0), B, B.stride(0), C, 1 if accumulate else 0, ws, counters)
+    _lib.wrote(out)
     return C
 
 
@@ -108,24 +110,19 @@ def inter_so3conv(feats_cl, W, bias, xyz, new_xyz, ball_idx, rk, sigma, chunk=10
     return InterSO3ConvFunction.apply(feats_cl, W, bias, xyz, new_xyz, ball_idx, rk, sigma, chunk)
 
 
-_INV_TABLES = {}
+_INV_TABLES = Shared(limit=16)
 
 
 def _inverse_tables(idx32):
     """Column-wise inverse of the intra conv's anchor tables (60, nt) -- every column is a permutation of the anchors.  A constant of the module's buffer:
     built once per (tensor, version) instead of with 2 nt launches in every backward (96 per training step)."""
-    key = (idx32.data_ptr(), idx32._version, tuple(idx32.shape), str(idx32.device))
-    hit = _INV_TABLES.get(key)
-    if hit is None:
-        if len(_INV_TABLES) > 16:
-            _INV_TABLES.clear()
-        with torch.no_grad():
-            inv = torch.empty_like(idx32)
-            ar = torch.arange(idx32.shape[0], dtype=torch.int32, device=idx32.device)
-            for t in range(idx32.shape[1]):
-                inv[idx32[:, t].long(), t] = ar
-        hit = _INV_TABLES[key] = (inv.contiguous(), idx32)          # (the key tensor is held: its address stays unique)
-    return hit[0]
+    def make():
+        inv = torch.empty_like(idx32)
+        ar = torch.arange(idx32.shape[0], dtype=torch.int32, device=idx32.device)
+        for t in range(idx32.shape[1]):
+            inv[idx32[:, t].long(), t] = ar
+        return inv.contiguous()
+    return _INV_TABLES.get((idx32.data_ptr(), idx32._version, tuple(idx32.shape), str(idx32.device)), make, keep=idx32)
 
 
 class IntraSO3ConvFunction(torch.autograd.Function):

@@ -49,6 +49,7 @@ class BatchNormFunction(torch.autograd.Function):
             mean, rstd, scale = stats[0], stats[1], stats[2]
             _lib.call("etch_bn_train_forward", R, C, x, x.stride(0), g, beta.detach().contiguous(), float(eps), float(-1.0 if momentum is None else momentum),
                       rm, rv, nbt, 1 if relu else 0, ws, counters, mean, rstd, scale, y)
+            _lib.wrote(rm, rv, nbt)         # the eval path's BatchNorm folds are keyed on the running statistics' versions
         else:
             rstd = torch.rsqrt(var + eps)
             scale = (g * rstd).contiguous()

@@ -9,6 +9,7 @@ import torch.nn.init as init
 from torch import nn
 
 from .. import ops
+from .._shared import Shared
 from ..config.EPN_options import get_default_cfg
 from .direction_backbones import BatchMLP, StackedMHSA
 from . import pointops
@@ -43,6 +44,7 @@ class GT_network_equiv(nn.Module):
         # magnitude / confidence
         self.magnitude_encoder = get_pointtransformer_magnitude(c=EPN_feat_dim + 3, k=1)
         self.confidence_encoder = get_pointtransformer_confidence(c=EPN_feat_dim + 3, k=len(option.markerset))
+        self._const_cache = Shared(limit=64)
         self._reset_parameters()
 
     def _reset_parameters(self):
@@ -296,15 +298,8 @@ class GT_network_equiv(nn.Module):
 
     def _const(self, key, make):
         """Per-shape constants of a forward (the identity `selected_indexs`, the broadcast standard vector): built once per (shape, device) instead of with
-        2 - 3 launches per forward.  Read-only by contract: the reference returns fresh tensors, callers that write into them must clone."""
-        c = self.__dict__.setdefault("_const_cache", {})
-        v = c.get(key)
-        if v is None:
-            if len(c) > 64:
-                c.clear()
-            with torch.no_grad():
-                v = c[key] = make()
-        return v
+        2 - 3 launches per forward.  The reference returns fresh tensors; here one tensor per key is shared, and rebuilt once a caller has written into it."""
+        return self._const_cache.get(key, make)
 
     def forward(self, hitpts, pred_items=["direction", "magnitude"], direction_mode="standard_vector"):
         """models_pointcloud.py:146-221.  See `differentiable` above for when the path with autograd history is taken."""
@@ -418,11 +413,11 @@ class GT_network_equiv(nn.Module):
     fps_pair = os.environ.get("ETCH_FPS_PAIR", "1") != "0"
 
     def _fps_pair_ahead(self, hitpts, xyz_b3n, B, N):
-        """The encoder's FPS and the nets' first FPS level in one launch (ops.fps_pair), handed to their callers through ops._FPS_READY: on the dense 8-scan
-        shard of configs[4] the two chains (27 + 11 ms, eight workgroups each) no longer queue behind each other on the index stream.  Only where both
-        will really be asked for with exactly these arguments (first conv strided and not lazily sampled, split FPS not selected)."""
+        """The encoder's FPS and the nets' first FPS level in one launch (ops.fps_pair), seeded into the forward's knn_scope under the keys their callers
+        memoise under (vgtk_so3conv.furthest_sample_index, pointops.furthestsampling): on the dense 8-scan shard of configs[4] the two chains (27 + 11 ms,
+        eight workgroups each) no longer queue behind each other on the index stream.  Only where both will really be asked for with exactly these
+        arguments (first conv strided and not lazily sampled, split FPS not selected)."""
         from .pointtransformer_seg import downsampled_offsets
-        ops._FPS_READY.clear()            # (a forward that raised half-way must not leave a result behind for a later tensor at the same address)
         ic = self.encoder.backbone[0].blocks[0].inter_conv.conv
         m = -(-N // ic.stride)
         if ic.stride <= 1 or ic.lazy_sample or m == N or ops.fps_split_default(B, N, hitpts.device) >= 2:
@@ -433,8 +428,8 @@ class GT_network_equiv(nn.Module):
         n_o_t = pointops.make_offsets(n_o, hitpts.device, like=(o, 4))
         packed = hitpts.view(-1, 3)
         idx_a, idx_b = ops.fps_pair(xyz_b3n, m, packed, o, n_o_t, n_o)
-        ops._FPS_READY[("vgtk", xyz_b3n.data_ptr(), int(m))] = idx_a
-        ops._FPS_READY[("pointops", packed.data_ptr(), n_o_t.data_ptr())] = idx_b
+        pointops._seed(("vgtk_fps", xyz_b3n.data_ptr(), int(m)), (xyz_b3n,), idx_a)
+        pointops._seed(("fps", packed.data_ptr(), tuple(oh), tuple(n_o)), (packed,), idx_b)
         return [idx_a, idx_b, n_o_t]
 
     def _input_order(self, hitpts):

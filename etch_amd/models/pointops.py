@@ -7,6 +7,7 @@ Same names and argument order.  Two host-side economies that do not change any r
 import torch
 
 from .. import ops
+from .._shared import Shared
 
 _knn_cache = None  # dict while a Point-Transformer forward is active
 
@@ -26,7 +27,7 @@ def set_host_offsets(o, values):
     return o
 
 
-_offset_tensors = {}   # (values, device) -> device int32 tensor; offsets are a pure function of (B, N, strides)
+_offset_tensors = Shared(limit=256)   # (values, device) -> device int32 tensor; offsets are a pure function of (B, N, strides)
 
 
 def offsets_tensor(values, device):
@@ -34,14 +35,12 @@ def offsets_tensor(values, device):
     synchronous pageable copy that would stall the host behind every kernel already queued (one stall per level per forward)."""
     device = torch.device(device)
     key = (tuple(int(v) for v in values), device.type, device.index if device.index is not None else torch.cuda.current_device())
-    t = _offset_tensors.get(key)
-    if t is None:
+
+    def make():
         t = set_host_offsets(torch.tensor(list(key[0]), dtype=torch.int32, device=device), key[0])
         torch.cuda.current_stream(device).synchronize()      # first use only: visible to every stream from here on
-        if len(_offset_tensors) > 256:
-            _offset_tensors.clear()
-        _offset_tensors[key] = t
-    return t
+        return t
+    return _offset_tensors.get(key, make)
 
 
 class knn_scope:
@@ -68,6 +67,13 @@ def _memo(key, keep, fn):
         hit = (fn(), keep)          # `keep` pins the key tensors so their addresses stay unique inside the scope
         _knn_cache[key] = hit
     return hit[0]
+
+
+def _seed(key, keep, value):
+    """Hand `value`, computed ahead, to the _memo call that will ask for `key`: it lives in the active scope and dies with it, return or raise."""
+    if _knn_cache is None:
+        raise RuntimeError("pointops._seed: no knn_scope is active")
+    _knn_cache[key] = (value, keep)
 
 
 def make_offsets(values, device, like=None):

@@ -5,6 +5,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from .._shared import Shared, constant_value
 from .. import vgtk_so3conv as sptk
 
 
@@ -15,22 +16,18 @@ def input_xyz(x):
     return pointops._memo(("epn_xyz", x.data_ptr(), tuple(x.shape)), (x,), lambda: x.permute(0, 2, 1).contiguous())
 
 
-_ones_cache = {}
+_ones_cache = Shared(limit=8)
 
 
 def _occupancy_ones(b, n, na, device):
-    """The all-ones occupancy features (functional.py:70-89) are a constant of the input shape: one read-only tensor per shape
-    instead of a 38 MB fill per forward (0.9 ms at 32 x 5 000 points)."""
-    key = (b, n, na, device.type, device.index)
-    t = _ones_cache.get(key)
-    if t is None:
-        if len(_ones_cache) > 8:
-            _ones_cache.clear()
+    """The all-ones occupancy features (functional.py:70-89) are a constant of the input shape: one shared tensor per shape instead of a 38 MB fill
+    per forward (0.9 ms at 32 x 5 000 points).  Registered as filled with 1.0: while constant_value() says so, consumers use the value instead of the
+    tensor (ops.inter_so3conv, SeparableSO3ConvBlock's one-channel skip branch); a caller's edit ends that and the next call here builds a fresh one."""
+    def make():
         t = torch.ones((b, n, na, 1), dtype=torch.float32, device=device)
-        torch.cuda.current_stream(device).synchronize() if device.type == "cuda" else None
-        t._etch_constant = 1.0          # read-only by contract: consumers may use the value instead of the tensor (SeparableSO3ConvBlock's one-channel skip branch)
-        _ones_cache[key] = t
-    return t
+        torch.cuda.current_stream(device).synchronize() if device.type == "cuda" else None     # first use only: visible to every stream from here on
+        return t
+    return _ones_cache.get((b, n, na, device.type, device.index), make, fill=1.0)
 
 
 def preprocess_input(x, na, add_center=True):
@@ -121,7 +118,7 @@ class SeparableSO3ConvBlock(nn.Module):
             # s = w_c f + bias_c is affine in the ONE input value of a row: its InstanceNorm statistics follow from mean / variance of f over the scan's
             # (sampled) rows -- mean_c = w_c mean(f) + bias_c, var_c = w_c^2 var(f) -- and the normalised branch is f slope_c + offset_c.  The (rows, C)
             # conv output, its statistics pass and its read by the final pass (0.31 + 0.18 ms, 0.6 GB at 32 x 5 000 points) are never made.
-            if getattr(fin, "_etch_constant", None) is not None:
+            if constant_value(fin) is not None:
                 # constant features (the occupancy ones of so3conv.py:7-16): s is constant per channel, its InstanceNorm is 0 -- the branch adds nothing
                 return ("zero",)
             f = fin.reshape(b, p1, na)

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._shared import Shared, constant_value
 
 
 # For direct callers of the typed functions (`_lib.lib().etch_x(...)` in tests and profiles/scripts); the package itself goes through _lib.call.
@@ -88,11 +89,6 @@ def _fps_split_checked(idx, split):
     return idx
 
 
-# One-shot hand-over of sampling results that fps_pair computed ahead of their callers (models_pointcloud._prefetch_indices): key -> idx.  A result is taken
-# (popped) by the first call whose arguments match; the keys hold data pointers of tensors the prefetcher keeps alive until then.
-_FPS_READY = {}
-
-
 def fps_pair(xyz_b3n, m, xyz_packed, offset, new_offset, new_offset_host):
     """The encoder's FPS (furthest_point_sampling(xyz_b3n, m)) and the Point-Transformer nets' first FPS level (furthestsampling(xyz_packed, offset,
     new_offset)) over the same b scans of n points each in ONE launch of 2 b workgroups (etch_fps_pair): both are one workgroup per scan and depend on the
@@ -111,9 +107,6 @@ def furthest_point_sampling(xyz, m, split=None):
     """epn_grouping.furthest_point_sampling (grouping_cuda.cpp:158-173): (b,3,n) -> (b,m) int32.  split = workgroups per scan (None: auto)."""
     _need(xyz, torch.float32, "xyz")
     b, _, n = xyz.shape
-    ready = _FPS_READY.pop(("vgtk", xyz.data_ptr(), int(m)), None) if _FPS_READY else None
-    if ready is not None:
-        return ready
     idx = torch.zeros((b, m), dtype=torch.int32, device=xyz.device)
     G = fps_split_default(b, n, xyz.device) if split is None else int(split)
     if G >= 2:
@@ -233,9 +226,6 @@ def furthestsampling(xyz, offset, new_offset, offset_host=None, new_offset_host=
         offset_host = offset.tolist()
     if new_offset_host is None:
         new_offset_host = new_offset.tolist()
-    ready = _FPS_READY.pop(("pointops", xyz.data_ptr(), new_offset.data_ptr()), None) if _FPS_READY else None
-    if ready is not None:
-        return ready
     idx = torch.zeros((int(new_offset_host[-1]),), dtype=torch.int32, device=xyz.device)
     nseg, n_max = len(offset_host), _seg_max(offset_host)
     G = fps_split_default(nseg, n_max, xyz.device) if split is None else int(split)
@@ -266,6 +256,8 @@ def linear(x, weight, bias=None, scale=None, shift=None, act=None, res=None, res
     O = weight.shape[0]
     if out is None:
         out = torch.empty((R, O), dtype=torch.float32, device=x.device)
+    else:
+        _lib.wrote(out)         # (the caller's tensor; announced ahead of the launch, which is asynchronous anyway)
     ldr = res.stride(0) if res is not None and res.dim() == 2 and res.shape[0] > 1 else O
     _lib.call("etch_linear", int(R), int(K), int(O), x2, ldx, row_idx, int(grp), int(p_in), int(p_out), weight, weight.stride(0), bias, scale, shift, ACT[act],
               res, ldr, int(res_mode), out, out.stride(0))
@@ -321,15 +313,12 @@ def inter_weight_frag(W, cin, ks=24):
     return permute_weight_frag(W[:, _inter_contraction_cols(cin, ks, W.device)].contiguous())
 
 
-_CONTRACTION_COLS = {}
+_CONTRACTION_COLS = Shared()
 
 
 def _inter_contraction_cols(cin, ks, device):
     """Column permutation of W [cout, cin*ks] into the contraction order of inter_so3conv_kernel (see inter_weight_frag); one upload per (shape, device)."""
-    key = (cin, ks, str(device))
-    if key not in _CONTRACTION_COLS:
-        _CONTRACTION_COLS[key] = _inter_contraction_cols_build(cin, ks, device)
-    return _CONTRACTION_COLS[key]
+    return _CONTRACTION_COLS.get((cin, ks, str(device)), lambda: _inter_contraction_cols_build(cin, ks, device))
 
 
 def _inter_contraction_cols_build(cin, ks, device):
@@ -530,8 +519,9 @@ def inter_so3conv(xyz, new_xyz, ball_idx, feats_cl, rk, W, Wp, bias, sigma, orde
         _need(Wq, torch.int16, "Wq")
         _lib.call("etch_inter_so3conv_split", b, cin, cout, p1, p2, nn, float(sigma), xyz, new_xyz, ball_idx, feats_cl, rk, Wq, bias, out, order, part)
     else:
-        # all-ones features (the encoder's occupancy tensor, tagged by models/so3conv.py): the one-channel kernel takes NULL and skips the feature gather
-        unit = cin == 1 and getattr(feats_cl, "_etch_constant", None) == 1.0 and cout <= 64 and nn * 60 >= 1026
+        # all-ones features (the encoder's occupancy tensor, registered by models/so3conv.py and not written to since): the one-channel kernel takes NULL
+        # and skips the feature gather
+        unit = cin == 1 and constant_value(feats_cl) == 1.0 and cout <= 64 and nn * 60 >= 1026
         _lib.call("etch_inter_so3conv_ordered", b, cin, cout, p1, p2, nn, float(sigma), xyz, new_xyz, ball_idx, None if unit else feats_cl, rk, W, Wp, bias, out,
                   order, part)
     if not want_stats:
@@ -886,6 +876,8 @@ def grouped_dot(h, w, bias, G, J, out=None):
     R = h.shape[0]
     if out is None:
         out = torch.empty((R, G), dtype=torch.float32, device=h.device)
+    else:
+        _lib.wrote(out)
     _lib.call("etch_grouped_dot", R, G, J, h, h.stride(0), w, bias, out, out.stride(0))
     return out
 
@@ -941,6 +933,8 @@ def linear_relu_dot(x, w, b1, w2, b2, G, wp=None, out=None):
     assert x.stride(1) == 1 and w.shape == (G * J, K) and b1.numel() == G * J and w2.numel() == G * J and b2.numel() == G
     if out is None:
         out = torch.empty((R, G), dtype=torch.float32, device=x.device)
+    else:
+        _lib.wrote(out)
     if wp is not None and wp.dtype == torch.float16 and (b1.data_ptr() | w2.data_ptr()) % 16 == 0:
         _lib.call("etch_linear_relu_dot_f16", R, int(K), int(G), int(J), x, x.stride(0) if R > 1 else K, wp, wp.wsc, b1, w2, b2, out,
                   out.stride(0) if R > 1 else G)
@@ -1385,6 +1379,7 @@ def smpl_chamfer_refine(consts, scan, params, V, scan_lengths=None, prior=None, 
     tr = torch.empty((B, iters), dtype=torch.float32, device=scan.device) if want_trace else None
     _lib.call("etch_smpl_chamfer_refine", B, N, int(V), int(nj), int(nb), int(n_extra), arr, scan, sl, parr, G, int(bidir), int(iters), float(lr), float(beta1),
               float(beta2), float(eps), params, verts, joints, tr, loss, ws)
+    _lib.wrote(params)
     return verts, joints, loss, tr
 
 
@@ -1498,6 +1493,7 @@ def smpl_surface_refine(consts, faces, points, params, lengths=None, weights=Non
     _lib.call("etch_smpl_surface_refine", B, N, V, F, int(nj), int(nb), int(n_extra), arr, faces, points, nl, weights, M, vids, pos, valid, parr, G, int(iters),
               float(lr), float(beta1), float(beta2), float(eps), float(w_dense), float(w_marker), float(w_beta), float(w_prior), float(trunc),
               int(bool(optimize_scale)), params, verts, joints, tr, loss, ws)
+    _lib.wrote(params)
     return verts, joints, loss, tr
 
 
@@ -1574,6 +1570,7 @@ def containment_energy_grad(body_verts, mesh, w, face, bary, d2, coef=None, w_co
     ws = _byte_workspace("etch_containment_energy_grad_workspace", body_verts.device, B, V)
     terms = torch.zeros((B, 2), dtype=torch.float64, device=body_verts.device)
     _lib.call("etch_containment_energy_grad", B, V, body_verts, verts, faces, voff, foff, w, face, bary, d2, coef, float(w_contain), ws, terms, g)
+    _lib.wrote(g)
     return terms, g
 
 
@@ -1617,6 +1614,7 @@ def smpl_surface_refine_contain(consts, faces, points, params, scan, lengths=Non
     _lib.call("etch_smpl_surface_refine_contain", B, N, V, F, int(nj), int(nb), int(n_extra), arr, faces, points, nl, weights, M, vids, pos, valid, parr, G,
               int(iters), float(lr), float(beta1), float(beta2), float(eps), float(w_dense), float(w_marker), float(w_beta), float(w_prior), float(trunc),
               int(bool(optimize_scale)), mf, sv, sf, svo, sfo, float(w_contain), int(contain_every), params, verts, joints, tr, loss, ws)
+    _lib.wrote(params)
     return verts, joints, loss, tr
 
 
@@ -1711,6 +1709,7 @@ def smpld_register(base, R, D, scan, nbr_ptr, nbr_idx, n_edges, lambda_s, scan_l
     trace = torch.empty((B, iters, 4), dtype=torch.float32, device=dev) if want_trace else None
     _lib.call("etch_smpld_register", B, N, V, base, R, scan, sl, nbr_ptr, nbr_idx, int(n_edges), iters, (ctypes.c_float * iters)(*lam), float(lambda_m),
               float(w_s2m), float(w_m2s), tr, float(lr), D, verts, energy, trace, ws)
+    _lib.wrote(D)
     return verts, energy, trace
 
 
@@ -1941,6 +1940,7 @@ def train_losses(direction, magnitude, confidences, part_labels, t_vectors, t_co
               t_labels if part_labels is not None else None]
     _lib.call("etch_train_losses", int(B), int(K), int(N), int(M), *heads, *used_t, index, w[0], w[1], w[2], w[3],
               float(scale_magnitude), ws, counter, losses, status, *grads)
+    _lib.wrote(status)
     return losses, status, grads
 
 
@@ -1986,6 +1986,7 @@ def grad_pack(T, C, chunk_tensor, first_chunk, numel, grads, offsets, flat, scal
             _need(status, torch.int32, "status")
     _lib.call("etch_grad_pack", int(T), int(C), chunk_tensor, first_chunk, numel, grads, offsets, flat, float(scale), int(mode), losses, status,
               int(tail_offset))
+    _lib.wrote(flat)
 
 
 def grad_unpack_tail(tail, losses=None, status=None):
@@ -2000,6 +2001,7 @@ def grad_unpack_tail(tail, losses=None, status=None):
         status = torch.zeros((1,), dtype=torch.int32, device=tail.device)
     _need(losses, torch.float32, "losses"), _need(status, torch.int32, "status")
     _lib.call("etch_grad_unpack_tail", tail, losses, status)
+    _lib.wrote(losses, status)
     return losses, status
 
 

@@ -3,6 +3,7 @@
 import numpy as np
 import torch
 
+from . import _lib
 from . import ops
 
 
@@ -160,6 +161,9 @@ class GuardedAdam(torch.optim.Optimizer):
         if g["dirty"]:
             g["pmv"].copy_(torch.from_numpy(g["pmv_host"].view(np.int64)))
             g["dirty"] = False
+            # what a step writes through this table (which tensors it really steps is known on the device only); state["step"] are views of g["steps"]
+            states = [st for st in map(self.state.get, g["params"]) if st]
+            g["written"] = g["params"] + [st[k] for st in states for k in ("exp_avg", "exp_avg_sq")] + [g["steps"], self._counters]
         g["gdev"].copy_(g["ring"][slot], non_blocking=True)
         ev = g["events"][slot] or torch.cuda.Event()
         ev.record()
@@ -188,6 +192,7 @@ class GuardedAdam(torch.optim.Optimizer):
                 raise ValueError("GuardedAdam supports weight_decay=0, amsgrad=False, maximize=False only")
             ops.guarded_adam_step(g["T"], g["C"], g["chunk_tensor"], g["first_chunk"], g["numel"], g["pmv"], g["gdev"], self._status, g["steps"],
                                   g["chunkflags"], float(lr), (float(betas[0]), float(betas[1])), float(eps), self._counters)
+            _lib.wrote(*g["written"])
         self._flat_pending = False
 
     # ---- gradients through a flat buffer (accumulated and data-parallel steps)

@@ -11,6 +11,7 @@ import torch.nn as nn
 
 from . import constants as K
 from . import ops
+from ._shared import Shared
 from . import vgtk_functional as functional  # noqa: F401  (the reference's `vgtk.so3conv.functional`)
 
 
@@ -58,21 +59,18 @@ def ball_query_index(query_points, support_points, radius, n_sample):
     return ops.ball_query(query_points, support_points, radius, n_sample)
 
 
-_IDENTITY_SAMPLES = {}
+_IDENTITY_SAMPLES = Shared(limit=64)
 
 
 def furthest_sample_index(pc, n_sample, lazy_sample):
-    """pc/sample.py:75-85."""
+    """pc/sample.py:75-85.  The sampled case is looked up in the forward's pointops.knn_scope first: the model may have computed it ahead (ops.fps_pair)."""
     if pc.shape[2] == n_sample or lazy_sample:
         nb = pc.shape[0]
-        key = (nb, int(n_sample), str(pc.device))
-        v = _IDENTITY_SAMPLES.get(key)
-        if v is None:            # (a per-shape constant: two launches per conv and forward otherwise; read-only by contract)
-            if len(_IDENTITY_SAMPLES) > 64:
-                _IDENTITY_SAMPLES.clear()
-            v = _IDENTITY_SAMPLES[key] = torch.arange(n_sample, device=pc.device, dtype=torch.int32).view(1, -1).expand(nb, -1).contiguous()
-        return v
-    return ops.furthest_point_sampling(pc, n_sample)
+        # (a per-shape constant: two launches per conv and forward otherwise; one shared tensor, rebuilt if a caller wrote into it)
+        return _IDENTITY_SAMPLES.get((nb, int(n_sample), str(pc.device)),
+                                     lambda: torch.arange(n_sample, device=pc.device, dtype=torch.int32).view(1, -1).expand(nb, -1).contiguous())
+    from .models import pointops
+    return pointops._memo(("vgtk_fps", pc.data_ptr(), int(n_sample)), (pc,), lambda: ops.furthest_point_sampling(pc, n_sample))
 
 
 def furthest_sample(pc, n_sample, lazy_sample=True):
