@@ -13,8 +13,12 @@ handing it to the pipeline.
 
     python -m etch_amd.cloud --cloud_path scan.ply [--voxel V] [--outlier_k K --outlier_ratio R] [--outlier_radius r --outlier_min_neighbours m]
                              [--floor_threshold T --floor_up X Y Z --floor_max_tilt DEG] [--cluster_radius R]
+                             [--more_views B.ply C.ply .. --align_gate G --align_gate_min g --align_decay D --align_iters K --view_init F.npz --fuse_voxel V]
 
-Neighbours are rows of the same cloud only.  The kernels (csrc/cloud_filter.hip, csrc/cloud_isolate.hip) are exact and defined in fp64; there is no CPU path."""
+    nearest(source, target, gate), align(source, target, ...)  gated nearest rows across two clouds; rigid registration by ICP on the cell grid (section 23)
+    transform(cloud, R, t), register_views(views), fuse(views, transforms, voxel=)   several views into one frame, one cloud per subject
+
+Neighbours are rows of the same cloud only.  The kernels (csrc/cloud_filter.hip, csrc/cloud_isolate.hip, csrc/cloud_align.hip) are exact and defined in fp64; there is no CPU path."""
 import argparse
 import math
 import os
@@ -414,7 +418,240 @@ def prepare(cloud, N, keys, voxel=None, stat=None, radius=None, center=True, flo
     return p32, c, cur
 
 
+# ---------------------------------------------------------------------------------------------------------------- registering several views
+STATUS_DEGENERATE = 8
+ALIGN_TOL_ANGLE, ALIGN_TOL_SHIFT = 1e-9, 1e-9                       # radians, metres: far below a scanner's noise, far above fp64 rounding
+
+
+class Alignment:
+    """What align() returns, per pair of clouds: R (B,3,3), t (B,3) fp64 and pair (Ms) int32 (the last matching, -1 = unmatched) on the device;
+    matched (B), rms (B), steps (B), status (B) numpy -- status holds STATUS_DEGENERATE where a step had fewer than 3 pairs or pairs of rank < 2
+    (the transform then stayed as it was from that step on)."""
+
+    def __init__(self, R, t, matched, rms, steps, status, pair):
+        self.R, self.t, self.matched, self.rms, self.steps, self.status, self.pair = R, t, matched, rms, steps, status, pair
+
+
+def _check_pairs(source, target):
+    so, to = _offsets(source), _offsets(target)
+    if len(so) != len(to):
+        raise ValueError(f"source and target must hold the same number of clouds, got {len(so) - 1} and {len(to) - 1}")
+    return so, to
+
+
+def _check_align(gate=0.2, gate_min=0.02, decay=0.9, iters=40, tol_angle=ALIGN_TOL_ANGLE, tol_shift=ALIGN_TOL_SHIFT, cell=None):
+    """align's loop arguments, checked before any launch.  -> a dict: gates (the gate of every step, fp64 on the host), tol_angle, tol_shift, cell."""
+    gate = _check_positive(gate, "gate")
+    gate_min = _check_positive(gate_min, "gate_min")
+    if gate_min > gate:
+        raise ValueError(f"gate_min must not exceed gate, got {gate_min} > {gate}")
+    if not 0.0 < float(decay) <= 1.0:
+        raise ValueError(f"decay must lie in (0, 1], got {decay}")
+    if int(iters) != iters or int(iters) < 1:
+        raise ValueError(f"iters must be a positive integer, got {iters}")
+    if not (float(tol_angle) >= 0.0 and float(tol_shift) >= 0.0):
+        raise ValueError(f"tol_angle and tol_shift must not be negative, got {tol_angle} and {tol_shift}")
+    if cell is not None:
+        _check_positive(cell, "cell")
+    return dict(gates=[max(gate_min, gate * float(decay) ** k) for k in range(int(iters))], tol_angle=float(tol_angle), tol_shift=float(tol_shift), cell=cell)
+
+
+def _init_pose(init, B, dev):
+    """init: None, (R (B,3,3), t (B,3)) or (B,4,4) poses, arrays or tensors -> R, t fp64 on the device (None, None for None)."""
+    import torch
+    if init is None:
+        return None, None
+    if isinstance(init, (tuple, list)) and len(init) == 2 and (init[0] is None) != (init[1] is None):
+        raise ValueError("a transform is R and t together: one of them is missing")
+    if isinstance(init, (tuple, list)) and len(init) == 2 and all(isinstance(x, torch.Tensor) and x.is_cuda for x in init):
+        R, t = (x.to(device=dev, dtype=torch.float64) for x in init)         # device tensors (an Alignment's) stay there: no copy to the host, and
+        if R.numel() != 9 * B or t.numel() != 3 * B:                         # so no look at their values
+            raise ValueError(f"init must give a rotation and a shift for each of the {B} clouds")
+        return R.reshape(B, 3, 3).contiguous(), t.reshape(B, 3).contiguous()
+    if isinstance(init, (tuple, list)) and len(init) == 2:
+        R, t = (np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x, np.float64) for x in init)
+    else:
+        T = np.asarray(init.cpu() if isinstance(init, torch.Tensor) else init, np.float64).reshape(-1, 4, 4)
+        R, t = T[:, :3, :3], T[:, :3, 3]
+    R, t = R.reshape(-1, 3, 3), t.reshape(-1, 3)
+    if R.shape != (B, 3, 3) or t.shape != (B, 3) or not (np.isfinite(R).all() and np.isfinite(t).all()):
+        raise ValueError(f"init must give a finite rotation and shift for each of the {B} clouds")
+    return torch.from_numpy(np.ascontiguousarray(R)).to(dev), torch.from_numpy(np.ascontiguousarray(t)).to(dev)
+
+
+def nearest(source, target, gate, R=None, t=None, cell=None, brute=False):
+    """For every row of source cloud b, moved by x = R_b p + t_b: the nearest row of target cloud b with d2 <= gate * gate, a tie to the lowest
+    row.  -> pair (Ms) int32 = that row, local to its cloud (-1 without one), d2 (Ms) fp64 (+inf without one), on the device.  The same bits for
+    any cell size and from brute=True.  EtchHipError naming the cloud where a coordinate of either side is not finite."""
+    gate = _check_positive(gate, "gate")
+    if cell is not None:
+        _check_positive(cell, "cell")
+    so, _ = _check_pairs(source, target)
+    R, t = _init_pose(None if R is None and t is None else (R, t), len(so) - 1, source.points.device)
+    torch, ops, ctx = _ops(source)
+    with ctx:
+        pair, d2, status = ops.cloud_nearest(source.points, source.offsets, target.points, target.offsets, gate, R=R, t=t, cell=cell, brute=brute)
+    _raise_status("nearest", status.cpu().numpy() & STATUS_NONFINITE)
+    return pair[:int(so[-1])], d2[:int(so[-1])]
+
+
+def _align(torch, ops, source, target, a, R, t, brute):
+    return ops.cloud_align(source.points, source.offsets, target.points, target.offsets, a["gates"], a["tol_angle"], a["tol_shift"], R=R, t=t,
+                           cell=a["cell"], brute=brute)
+
+
+def _alignment(torch, out, B, what):
+    """The one readback of an align call."""
+    host = torch.cat([out["matched"].double(), out["steps"].double(), out["status"].double(), out["rms"]]).cpu().numpy().reshape(4, B)
+    status = host[2].astype(np.int32)
+    _raise_status(what, status & STATUS_NONFINITE)
+    return Alignment(out["R"], out["t"], host[0].astype(np.int32), host[3], host[1].astype(np.int32), status, out["pair"])
+
+
+def align(source, target, gate=0.2, gate_min=0.02, decay=0.9, iters=40, tol_angle=ALIGN_TOL_ANGLE, tol_shift=ALIGN_TOL_SHIFT, init=None, cell=None,
+          brute=False):
+    """Point-to-point ICP with a shrinking gate, every pair of clouds on its own: step k matches every moved source row to its nearest target row
+    within max(gate_min, gate * decay^k), then takes the rigid step that fits the matched rows best (least squares, closed form).  A pair
+    stops early once a step turns by less than tol_angle radians and moves its matched rows' centroid by less than tol_shift; the defaults end
+    a pair whose matching has frozen (copies of the same rows) and are inert between two samplings of a surface, where the steps shrink by
+    only ~0.86 a step and `iters` ends the loop: set tol_shift to a fraction of the expected rms there.  init: start poses
+    (R, t) or (B,4,4); the method converges from about 20 degrees and 10 cm on a body, not from anywhere.  -> Alignment.  The loop runs on the
+    device without a host synchronisation; brute=True gives the same bits without the grid.  ValueError for bad arguments before any launch."""
+    a = _check_align(gate, gate_min, decay, iters, tol_angle, tol_shift, cell)
+    so, _ = _check_pairs(source, target)
+    B = len(so) - 1
+    torch, ops, ctx = _ops(source)
+    R, t = _init_pose(init, B, source.points.device)
+    with ctx:
+        out = _align(torch, ops, source, target, a, R, t, brute)
+        res = _alignment(torch, out, B, "align")
+    res.pair = res.pair[:int(so[-1])]
+    return res
+
+
+def transform(cloud, R, t):
+    """The cloud moved: x = R_b p + t_b for every row of cloud b (R, t: arrays, or device tensors such as an Alignment's, which are used where
+    they are).  -> a Cloud with the same index, offsets and count."""
+    o = _offsets(cloud)
+    R, t = _init_pose((R, t), len(o) - 1, cloud.points.device)
+    torch, ops, ctx = _ops(cloud)
+    with ctx:
+        pts = ops.cloud_transform(cloud.points, cloud.offsets, R, t)
+    return Cloud(pts, cloud.index, cloud.offsets, cloud.count, None)
+
+
+def _union(torch, clouds, offsets):
+    """Clouds of B subjects each (host offsets given) -> one Cloud whose cloud b holds the rows of every part's cloud b, part after part; index is
+    the row inside the part.  Packed on the device."""
+    B = len(offsets[0]) - 1
+    dev = clouds[0].points.device
+    parts, index = [], []
+    for b in range(B):
+        for c, o in zip(clouds, offsets):
+            parts.append(c.points[int(o[b]):int(o[b + 1])])
+            index.append(c.index[int(o[b]):int(o[b + 1])])
+    n = np.array([sum(int(o[b + 1] - o[b]) for o in offsets) for b in range(B)], np.int64)
+    if n.sum() >= 2 ** 31 // 3:
+        raise ValueError("the views together are too large for 32-bit offsets")
+    off = torch.from_numpy(np.concatenate([[0], np.cumsum(n)]).astype(np.int32)).to(dev)
+    return Cloud(torch.cat(parts).contiguous(), torch.cat(index).contiguous(), off, torch.from_numpy(n.astype(np.int32)).to(dev), None)
+
+
+def _check_views(views):
+    views = list(views)
+    if not views:
+        raise ValueError("no view to register")
+    offsets = [_offsets(v) for v in views]
+    if len({len(o) for o in offsets}) != 1:
+        raise ValueError(f"every view must hold the same number of clouds, got {[len(o) - 1 for o in offsets]}")
+    return views, offsets
+
+
+def register_views(views, init=None, **align_kw):
+    """Views (Clouds of B subjects each) into the frame of view 0: view k is aligned to the union of the views 0 .. k - 1 as already placed.
+    init: one start pose per view (None, (R, t) or (B,4,4)), or None.  -> a list of Alignment, one per view (view 0: the identity)."""
+    a = _check_align(**align_kw)
+    views, offsets = _check_views(views)
+    if init is not None and len(init) != len(views):
+        raise ValueError(f"init must hold one entry per view, got {len(init)} for {len(views)} views")
+    B = len(offsets[0]) - 1
+    torch, ops, ctx = _ops(views[0])
+    dev = views[0].points.device
+    with ctx:
+        eye = torch.eye(3, dtype=torch.float64, device=dev).repeat(B, 1, 1)
+        out = [Alignment(eye, torch.zeros((B, 3), dtype=torch.float64, device=dev), np.diff(offsets[0]).astype(np.int32), np.zeros(B),
+                         np.zeros(B, np.int32), np.zeros(B, np.int32), None)]
+        placed = [views[0]]
+        for k in range(1, len(views)):
+            R, t = _init_pose(None if init is None else init[k], B, dev)
+            res = _alignment(torch, _align(torch, ops, views[k], _union(torch, placed, offsets[:k]), a, R, t, False), B, f"register_views (view {k})")
+            res.pair = res.pair[:int(offsets[k][-1])]
+            out.append(res)
+            placed.append(Cloud(ops.cloud_transform(views[k].points, views[k].offsets, res.R, res.t), views[k].index, views[k].offsets, views[k].count, None))
+    return out
+
+
+def fuse(views, transforms, voxel=None):
+    """The views, each moved by its transform (an Alignment or (R, t)), concatenated into one cloud per subject; with voxel, voxel_downsample of
+    that, so that a surface several views saw is present once.  -> Cloud."""
+    views, offsets = _check_views(views)
+    transforms = list(transforms)
+    if len(transforms) != len(views):
+        raise ValueError(f"fuse needs one transform per view, got {len(transforms)} for {len(views)} views")
+    if voxel is not None:
+        voxel = _check_positive(voxel, "voxel")
+    torch, ops, ctx = _ops(views[0])
+    moved = [transform(v, *((T.R, T.t) if isinstance(T, Alignment) else T)) for v, T in zip(views, transforms)]
+    with ctx:
+        union = _union(torch, moved, offsets)
+    return voxel_downsample(union, voxel)[0] if voxel is not None else union
+
+
 # ---------------------------------------------------------------------------------------------------------------- the command
+def add_align_flags(p):
+    """The flags that register further views onto --cloud_path's frame; without --more_views nothing changes."""
+    p.add_argument("--more_views", type=str, nargs="+", default=None, help="further views of the same subject, registered onto the first cloud's frame "
+                   "and fused with it before the cleaning stages")
+    p.add_argument("--align_gate", type=float, default=0.2, help="registration: the first gate in metres")
+    p.add_argument("--align_gate_min", type=float, default=0.02, help="registration: the smallest gate")
+    p.add_argument("--align_decay", type=float, default=0.9, help="registration: the gate shrinks by this factor a step")
+    p.add_argument("--align_iters", type=int, default=40, help="registration: steps at most")
+    p.add_argument("--view_init", type=str, default=None, help="an .npz whose array `poses` (V,4,4) holds a start pose for every view of --more_views")
+    p.add_argument("--fuse_voxel", type=float, default=0.0, help="fuse the registered views on a voxel grid of V metres; 0 = concatenate")
+
+
+def check_align_flags(p, a):
+    try:
+        _check_align(a.align_gate, a.align_gate_min, a.align_decay, a.align_iters)
+    except ValueError as e:
+        p.error(f"registration: {e}")
+    if a.fuse_voxel < 0.0 or not math.isfinite(a.fuse_voxel):
+        p.error("--fuse_voxel must be positive and finite")
+    if a.more_views is None and a.view_init is not None:
+        p.error("--view_init needs --more_views")
+
+
+def register_files(first, args):
+    """The command's registration stage: --more_views read, registered onto `first` ((n,3) numpy) and fused.  -> the fused (n,3) numpy, the report."""
+    from . import mesh_io
+    more = [mesh_io.read_cloud(f) for f in args.more_views]
+    init = None
+    if args.view_init is not None:
+        poses = np.asarray(np.load(args.view_init)["poses"], np.float64)
+        if poses.shape != (len(more), 4, 4):
+            raise ValueError(f"--view_init: poses must be ({len(more)},4,4), got {poses.shape}")
+        init = [None] + [poses[k:k + 1] for k in range(len(more))]
+    views = [pack([v], args.device) for v in [first] + more]
+    res = register_views(views, init=init, gate=args.align_gate, gate_min=args.align_gate_min, decay=args.align_decay, iters=args.align_iters)
+    fused = fuse(views, res, voxel=args.fuse_voxel if args.fuse_voxel > 0.0 else None)
+    pose = np.tile(np.eye(4), (len(views), 1, 1))
+    for k, r in enumerate(res):
+        pose[k, :3, :3], pose[k, :3, 3] = r.R[0].cpu().numpy(), r.t[0].cpu().numpy()
+    report = {"view_pose": pose, "view_matched": np.array([int(r.matched[0]) for r in res]), "view_rms": np.array([float(r.rms[0]) for r in res]),
+              "view_steps": np.array([int(r.steps[0]) for r in res]), "view_status": np.array([int(r.status[0]) for r in res])}
+    return fused.points.cpu().numpy(), report
+
+
 def add_filter_flags(p):
     """The cleaning flags python -m etch_amd.cloud and python -m etch_amd.depth share; all default to off."""
     p.add_argument("--outlier_k", type=int, default=0, help="statistical outlier removal: neighbours per point (1 .. 32); 0 = off")
@@ -485,6 +722,7 @@ def build_parser():
     p.add_argument("--voxel", type=float, default=0.0, help="voxel-grid down-sampling before the pick: the cell size in metres; 0 = off")
     add_filter_flags(p)
     add_isolate_flags(p)
+    add_align_flags(p)
     add_flags(p)
     p.add_argument("--chamfer_refine", type=str, nargs="?", const="partial", default="none", choices=["none", "both", "partial", "clutter"],
                    help="refine the body against the whole cleaned cloud after the marker fit; without a value: partial")
@@ -496,6 +734,7 @@ def parse_args(argv=None):
     a = p.parse_args(argv)
     check_filter_flags(p, a)
     check_isolate_flags(p, a)
+    check_align_flags(p, a)
     if a.voxel < 0.0 or not math.isfinite(a.voxel):
         p.error("--voxel must be positive and finite")
     if a.num_point < 1:
@@ -515,13 +754,16 @@ def main(argv=None):
         export = mesh_io.write_obj
     stat, radius = filter_args(args)
     floor, cluster = isolate_args(args)
+    views = {}
+    if args.more_views:                                               # the views enter as one cloud, ahead of every cleaning stage
+        raw, views = register_files(raw, args)
     p32, c, clean = prepare(pack([raw], args.device), args.num_point, [args.seed], voxel=args.voxel if args.voxel > 0.0 else None, stat=stat, radius=radius,
                             floor=floor, cluster=cluster)
     points, center, cleaned = p32[0].cpu().numpy(), c[0].cpu().numpy(), clean.points.cpu().numpy()
     name = os.path.splitext(os.path.basename(args.cloud_path))[0]
     stages = {f"rows_{k}": v for k, v in clean.stages.items()}
     np.savez(os.path.join(args.output_folder, f"{name}_cloud.npz"), keep=clean.keep.cpu().numpy(), center=center, points=points,
-             removed=np.int64(len(raw) - int(clean.keep.sum())), rows_output=np.array([len(cleaned)]), **stages, **isolate_report(clean))
+             removed=np.int64(len(raw) - int(clean.keep.sum())), rows_output=np.array([len(cleaned)]), **stages, **isolate_report(clean), **views)
     if args.chamfer_refine != "none":
         demo._refine_and_save(args, model, points, Mesh(cleaned - center, np.zeros((0, 3), np.int64)), center, name, export)
     else:

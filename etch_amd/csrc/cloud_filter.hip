@@ -25,21 +25,6 @@
 
 namespace {
 
-// the shell of Chebyshev ring rho around the cell (ix, iy, iz): the rim columns whole, the inner columns' two caps
-template <class F>
-__device__ __forceinline__ void cloud_scan_ring(const long long* __restrict__ keys, int lo, int hi, int ix, int iy, int iz, int rho, F&& f) {
-    for (int dx = -rho; dx <= rho; ++dx)
-        for (int dy = -rho; dy <= rho; ++dy) {
-            const int ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy;
-            if ((ax > ay ? ax : ay) == rho) {
-                cloud_scan_column(keys, lo, hi, ix + dx, iy + dy, iz - rho, iz + rho, f);
-            } else {
-                cloud_scan_column(keys, lo, hi, ix + dx, iy + dy, iz - rho, iz - rho, f);
-                cloud_scan_column(keys, lo, hi, ix + dx, iy + dy, iz + rho, iz + rho, f);
-            }
-        }
-}
-
 // ---- bounding box, status, cell size: one workgroup per cloud ------------------------------------------------------------------------------
 __global__ __launch_bounds__(CLOUD_SCAN_THREADS) void cloud_bounds_kernel(int mode, int k, double cell, const double* __restrict__ points,
                                                                           const int* __restrict__ offsets, double* __restrict__ grid,

@@ -1,5 +1,6 @@
-// The cell grid of the raw-cloud kernels (DESIGN sections 19 and 22), shared by cloud_filter.hip and cloud_isolate.hip: the squared distance,
-// the cloud of a packed row, and the walk over one column of cells of a cloud's sorted keys.  Both files are built with -ffp-contract=off.
+// The cell grid of the raw-cloud kernels (DESIGN sections 19, 22 and 23), shared by cloud_filter.hip, cloud_isolate.hip and cloud_align.hip: the
+// squared distance, the cloud of a packed row, and the walk over one column or one ring of cells of a cloud's sorted keys.  All three files are
+// built with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -43,6 +44,21 @@ __device__ __forceinline__ void cloud_scan_column(const long long* __restrict__ 
     const int a = cloud_lower_bound(keys, lo, hi, base | (long long)z0);
     const int e = cloud_lower_bound(keys, a, hi, (base | (long long)z1) + 1);
     for (int j = a; j < e; ++j) f(j);
+}
+
+// the shell of Chebyshev ring rho around the cell (ix, iy, iz): the rim columns whole, the inner columns' two caps
+template <class F>
+__device__ __forceinline__ void cloud_scan_ring(const long long* __restrict__ keys, int lo, int hi, int ix, int iy, int iz, int rho, F&& f) {
+    for (int dx = -rho; dx <= rho; ++dx)
+        for (int dy = -rho; dy <= rho; ++dy) {
+            const int ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy;
+            if ((ax > ay ? ax : ay) == rho) {
+                cloud_scan_column(keys, lo, hi, ix + dx, iy + dy, iz - rho, iz + rho, f);
+            } else {
+                cloud_scan_column(keys, lo, hi, ix + dx, iy + dy, iz - rho, iz - rho, f);
+                cloud_scan_column(keys, lo, hi, ix + dx, iy + dy, iz + rho, iz + rho, f);
+            }
+        }
 }
 
 }  // namespace

@@ -2345,3 +2345,137 @@ def cloud_component_keep(label, size, offsets, largest=True, min_points=1):
     winner = torch.empty((B,), dtype=torch.int32, device=label.device)
     _lib.call("etch_cloud_component_keep", int(B), int(bool(largest)), int(min_points), label, size, offsets, winner, keep)
     return keep, winner
+
+
+# ------------------------------------------------------------------ registering views (csrc/cloud_align.hip)
+ALIGN_STATUS_DEGENERATE = 8
+
+
+def _align_pairs(src_points, src_offsets, tgt_points, tgt_offsets, what):
+    B, Ms = _cloud_args(src_points, src_offsets, what)
+    Bt, Mt = _cloud_args(tgt_points, tgt_offsets, what)
+    if Bt != B:
+        raise _lib.EtchHipError(f"{what}: {B} source clouds but {Bt} target clouds")
+    return B, Ms, Mt
+
+
+def _align_transform(R, t, B, dev, what):
+    """R (B,3,3), t (B,3) fp64 on the device, the identity where None; always fresh tensors the library may write."""
+    R = torch.eye(3, dtype=torch.float64, device=dev).repeat(B, 1, 1) if R is None else _need(R, torch.float64, "R").reshape(-1, 3, 3).clone().contiguous()
+    t = torch.zeros((B, 3), dtype=torch.float64, device=dev) if t is None else _need(t, torch.float64, "t").reshape(-1, 3).clone().contiguous()
+    if R.shape != (B, 3, 3) or t.shape != (B, 3):
+        raise _lib.EtchHipError(f"{what}: R must be ({B},3,3) and t ({B},3), got {tuple(R.shape)} and {tuple(t.shape)}")
+    return R, t
+
+
+def _some(t):
+    """A tensor the library can take the address of: an empty one has none, and no row of it is ever read."""
+    return t if t is None or t.numel() else t.new_zeros((1,) + tuple(t.shape[1:]))
+
+
+def _check_gate(gate, cell, what):
+    if not (float(gate) > 0.0 and math.isfinite(float(gate))):
+        raise _lib.EtchHipError(f"{what}: gate must be positive and finite, got {gate}")
+    if cell is not None and not (float(cell) > 0.0 and math.isfinite(float(cell))):
+        raise _lib.EtchHipError(f"{what}: cell must be positive and finite, got {cell}")
+    return float(gate), 0.0 if cell is None else float(cell)
+
+
+def cloud_align_grid(points, offsets, gate, cell=None, sort=True):
+    """The TARGET's cell grid for etch_cloud_nearest (the header states the cell rule; cell= overrides it) and the stable sort of its rows by
+    (cloud, key).  -> grid (B,4), center (B,3) fp64, status (B) int32, and with sort: sorted_points (M,3), sorted_keys (M) int64, order (M) int32."""
+    B, M = _cloud_args(points, offsets, "cloud_align_grid")
+    gate, cell = _check_gate(gate, cell, "cloud_align_grid")
+    dev = points.device
+    grid = torch.empty((B, 4), dtype=torch.float64, device=dev)
+    center = torch.empty((B, 3), dtype=torch.float64, device=dev)
+    keys = torch.empty((M,), dtype=torch.int64, device=dev)
+    cloud = torch.empty((M,), dtype=torch.int32, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    _lib.call("etch_cloud_align_grid", int(B), int(M), gate, cell, _some(points), offsets, grid, center, _some(keys), _some(cloud), status)
+    if not sort:
+        return grid, center, status, None, None, None
+    skeys, order = torch.sort(keys, stable=True)
+    if B > 1:
+        _, second = torch.sort(cloud[order], stable=True)
+        order, skeys = order[second], skeys[second]
+    return grid, center, status, points[order].contiguous(), skeys.contiguous(), order.to(torch.int32).contiguous()
+
+
+def _query_order(src_points, src_offsets, gate, cell):
+    """The source rows in the order of their own cells: neighbours share a wave, and a rigid motion keeps them neighbours."""
+    return cloud_align_grid(src_points, src_offsets, gate, cell if cell else None)[5]
+
+
+def cloud_nearest(src_points, src_offsets, tgt_points, tgt_offsets, gate, R=None, t=None, cell=None, brute=False):
+    """etch_cloud_nearest: the nearest row of target cloud b within `gate` of every moved row R_b p + t_b of source cloud b.  -> pair (Ms) int32
+    (the row local to its cloud, -1 without one), d2 (Ms) fp64 (+inf without one), status (B) int32, all still on the device."""
+    B, Ms, Mt = _align_pairs(src_points, src_offsets, tgt_points, tgt_offsets, "cloud_nearest")
+    gate, cell = _check_gate(gate, cell, "cloud_nearest")
+    dev = src_points.device
+    R, t = _align_transform(R, t, B, dev, "cloud_nearest")
+    grid, _, status, sp, sk, order = cloud_align_grid(tgt_points, tgt_offsets, gate, cell if cell else None, sort=not brute)
+    qorder = None if brute else _query_order(src_points, src_offsets, gate, cell)
+    pair = torch.full((Ms,), -1, dtype=torch.int32, device=dev)
+    d2 = torch.full((Ms,), math.inf, dtype=torch.float64, device=dev)
+    g = torch.tensor([gate], dtype=torch.float64, device=dev)
+    _lib.call("etch_cloud_nearest", int(B), int(Ms), int(bool(brute)), _some(src_points), src_offsets, qorder, _some(tgt_points if brute else sp), _some(sk), _some(order),
+              tgt_offsets, grid, R, t, g, None, status, _some(pair), _some(d2))
+    return pair, d2, status
+
+
+def _align_state(B, Ms, dev):
+    z = lambda *s, dtype=torch.float64: torch.zeros(s, dtype=dtype, device=dev)                                    # noqa: E731
+    return dict(sums=z(B, 16), matched=z(B, dtype=torch.int32), rms=z(B), dR=z(B, 3, 3), dt=z(B, 3), done=z(B, dtype=torch.int32),
+                steps=z(B, dtype=torch.int32))
+
+
+def cloud_align_step(src_points, src_offsets, tgt_points, tgt_offsets, pair, d2=None, R=None, t=None):
+    """etch_cloud_align_step: one rigid step from the given pairs (pair (Ms) int32: the matched row of the target cloud, local to it, or -1).
+    -> dR (B,3,3), dt (B,3), m (B) int32, sums (B,16), then status (B) int32 and the composed R (B,3,3), t (B,3) -- unchanged where the status
+    holds ALIGN_STATUS_DEGENERATE."""
+    B, Ms, Mt = _align_pairs(src_points, src_offsets, tgt_points, tgt_offsets, "cloud_align_step")
+    _need(pair, torch.int32, "pair")
+    if pair.shape != (Ms,) or (d2 is not None and _need(d2, torch.float64, "d2").shape != (Ms,)):
+        raise _lib.EtchHipError(f"cloud_align_step: pair and d2 must be ({Ms},)")
+    dev = src_points.device
+    R, t = _align_transform(R, t, B, dev, "cloud_align_step")
+    _, center, status, _, _, _ = cloud_align_grid(tgt_points, tgt_offsets, 1.0, sort=False)
+    s = _align_state(B, Ms, dev)
+    _lib.call("etch_cloud_align_step", int(B), _some(src_points), src_offsets, _some(tgt_points), tgt_offsets, _some(pair), d2, center, 0.0, 0.0, R, t, s["sums"], s["matched"],
+              s["rms"], s["dR"], s["dt"], status, s["done"], s["steps"])
+    return s["dR"], s["dt"], s["matched"], s["sums"], status, R, t
+
+
+def cloud_align(src_points, src_offsets, tgt_points, tgt_offsets, gates, tol_angle, tol_shift, R=None, t=None, cell=None, brute=False):
+    """etch_cloud_align: len(gates) steps of nearest + rigid step, the target's grid built once, no host synchronisation.  gates: the gate of every
+    step, host floats.  -> a dict of device tensors: R (B,3,3), t (B,3), matched (B) int32, rms (B), steps (B) int32, status (B) int32, pair (Ms)
+    int32 and d2 (Ms) of the last matching, done (B) int32."""
+    B, Ms, Mt = _align_pairs(src_points, src_offsets, tgt_points, tgt_offsets, "cloud_align")
+    gates = [float(g) for g in gates]
+    if not gates or not all(g > 0.0 and math.isfinite(g) for g in gates):
+        raise _lib.EtchHipError("cloud_align: gates must be a non-empty list of positive finite numbers")
+    if not (float(tol_angle) >= 0.0 and float(tol_shift) >= 0.0):
+        raise _lib.EtchHipError("cloud_align: the tolerances must not be negative")
+    _, cell = _check_gate(gates[0], cell, "cloud_align")
+    dev = src_points.device
+    R, t = _align_transform(R, t, B, dev, "cloud_align")
+    grid, center, status, sp, sk, order = cloud_align_grid(tgt_points, tgt_offsets, max(gates), cell if cell else None, sort=not brute)
+    qorder = None if brute else _query_order(src_points, src_offsets, max(gates), cell)
+    s = _align_state(B, Ms, dev)
+    pair = torch.full((Ms,), -1, dtype=torch.int32, device=dev)
+    d2 = torch.full((Ms,), math.inf, dtype=torch.float64, device=dev)
+    g = torch.tensor(gates, dtype=torch.float64, device=dev)
+    _lib.call("etch_cloud_align", int(B), int(Ms), len(gates), int(bool(brute)), _some(src_points), src_offsets, qorder, _some(sp), _some(sk), _some(order), _some(tgt_points),
+              tgt_offsets, grid, center, g, float(tol_angle), float(tol_shift), R, t, s["sums"], s["matched"], s["rms"], s["dR"], s["dt"], status, s["done"],
+              s["steps"], _some(pair), _some(d2))
+    return dict(R=R, t=t, matched=s["matched"], rms=s["rms"], steps=s["steps"], status=status, pair=pair, d2=d2, done=s["done"])
+
+
+def cloud_transform(points, offsets, R, t):
+    """out (M,3) = R_b p + t_b for every row of cloud b (zeros behind the last cloud)."""
+    B, M = _cloud_args(points, offsets, "cloud_transform")
+    R, t = _align_transform(R, t, B, points.device, "cloud_transform")
+    out = torch.zeros((M, 3), dtype=torch.float64, device=points.device)
+    _lib.call("etch_cloud_transform", int(B), int(M), _some(points), offsets, R, t, _some(out))
+    return out

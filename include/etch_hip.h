@@ -1081,6 +1081,56 @@ int etch_cloud_components(int B, int M, double radius, int brute, const double* 
 int etch_cloud_component_keep(int B, int largest, int min_points, const int* label, const int* size, const int* offsets, int* winner, int* keep,
                               void* stream);
 
+/* ---- raw point clouds: rigid registration of several views -- gated nearest rows, moments, Horn's step (csrc/cloud_align.hip) */
+
+#define ETCH_ALIGN_STATUS_DEGENERATE 8   /* a step had fewer than 3 matched pairs or a cross-covariance of rank < 2: the transform was kept */
+#define ETCH_ALIGN_MAX_RINGS 8           /* rings of cells a nearest query examines before it scans its whole cloud instead */
+/* The rank threshold.  With s1 >= s2 >= s3 the singular values of the centred cross-covariance C = sum (x - mean x)(q - mean q)^T and
+ * e = sign det C, Horn's 4 x 4 matrix has the two largest eigenvalues l1 = s1 + s2 + e s3 (the trace of C's singular values, signed) and
+ * l2 = s1 - s2 - e s3.  A step is degenerate when l1 - l2 = 2 (s2 + e s3) <= ETCH_ALIGN_RANK_EPS l1: the second singular value lies below
+ * 5e-10 of that trace, which is where the rotation about the first singular direction stops being determined. */
+#define ETCH_ALIGN_RANK_EPS 1e-9
+/* A transform is R (B,9) fp64 row-major and t (B,3) per pair of clouds: x = R p + t, per component ((R_r0 px + R_r1 py) + R_r2 pz) + t_r.
+ *
+ * The TARGET's cell grid: grid (B,4) fp64 = the bounding-box minimum and the cell size h of every target cloud, center (B,3) its bounding-box
+ * centre, keys (M) int64 and cloud (M) int32 as etch_cloud_cell_keys writes them, status (B) int32 (written).  h = cell where cell > 0, else
+ * max(sqrt(32 (ex ey + ey ez + ez ex) / n), 32 L / n, gate / (ETCH_ALIGN_MAX_RINGS - 1)): 32 rows per occupied cell, and ring
+ * ETCH_ALIGN_MAX_RINGS lies strictly beyond the first gate (8 h (1 - 2^-20) >= 8/7 gate (1 - 2^-20) > gate), so a row without a partner ends its
+ * ring walk there and never scans its cloud; always h >= 2^-20 L.  The caller sorts the rows by (cloud, key) with a STABLE sort. */
+int etch_cloud_align_grid(int B, int M, double gate, double cell, const double* points, const int* offsets, double* grid, double* center,
+                          long long* keys, int* cloud, int* status, void* stream);
+/* For source row i of pair b: among the rows j of target cloud b with d2 = ((dx dx + dy dy) + dz dz) <= g g (g = gate[0] on the device, the
+ * product rounded once; d = R p_i + t - q_j) the one with the least d2, a tie to the lowest row: pair (Ms) int32 = that row local to its cloud,
+ * d2 (Ms) fp64; -1 and +inf where there is none.  Exact for any cell size and for queries outside the target's grid.  tgt_points are the target's
+ * rows sorted with tgt_keys and tgt_order; brute != 0 scans the whole target cloud for every row: tgt_points is then the unsorted target and
+ * tgt_keys, tgt_order, grid may be NULL.  query_order (Ms) int32 or NULL: thread i serves source row query_order[i] (a permutation of the rows
+ * that groups neighbours into a wave; it changes no result).  done (B) int32 or NULL: the rows of a pair with done != 0 are not touched.
+ * status (B) int32 is read and ORed: a pair with ETCH_CLOUD_STATUS_NONFINITE gets -1 / +inf, and a non-finite source row sets that bit. */
+int etch_cloud_nearest(int B, int Ms, int brute, const double* src_points, const int* src_offsets, const int* query_order, const double* tgt_points,
+                       const long long* tgt_keys, const int* tgt_order, const int* tgt_offsets, const double* grid, const double* R, const double* t,
+                       const double* gate, const int* done, int* status, int* pair, double* d2, void* stream);
+/* One rigid step per pair from the matched rows (pair[i] >= 0; tgt_points UNSORTED): with x = R p + t, x' = x - center and q' = q - center,
+ * sums (B,16) fp64 = sum x' (3), sum q' (3), sum x' q'^T (9, row = the component of x'), sum d2 (d2 (Ms) as etch_cloud_nearest wrote it; NULL:
+ * recomputed), each summed as one strided partial per thread (rows lo + tid, lo + tid + 1024, ..) and a fixed tree over the 1024 partials: an
+ * order n alone fixes.  matched (B) int32 = m, rms (B) = sqrt(sum d2 / m) (+inf for m = 0).  dR (B,9), dt (B,3) minimise sum |dR x + dt - q|^2
+ * (Horn's quaternion, cyclic Jacobi, det dR = +1); R <- dR R, t <- dR t + dt in place.  A degenerate step (above) ORs
+ * ETCH_ALIGN_STATUS_DEGENERATE into status, leaves R, t, writes dR = I, dt = 0 and sets done.  done (B) int32: a pair with done != 0 is
+ * skipped whole; it is set when the step turned by less than tol_angle (radians) and moved the matched rows' centroid by less than tol_shift,
+ * and for a pair with ETCH_CLOUD_STATUS_NONFINITE.  steps (B) int32 is incremented for every pair that took the step. */
+int etch_cloud_align_step(int B, const double* src_points, const int* src_offsets, const double* tgt_points, const int* tgt_offsets, const int* pair,
+                          const double* d2, const double* center, double tol_angle, double tol_shift, double* R, double* t, double* sums, int* matched,
+                          double* rms, double* dR, double* dt, int* status, int* done, int* steps, void* stream);
+/* The loop: iters times etch_cloud_nearest with the gate gates[k] (iters fp64 on the device) and etch_cloud_align_step, 2 iters launches and no
+ * host synchronisation; everything a step leaves stays on the device.  tgt_sorted, tgt_keys, tgt_order: the target's grid, built once;
+ * tgt_points: the unsorted target.  brute != 0 reads tgt_points alone.  pair and d2 hold the last matching of every pair of clouds. */
+int etch_cloud_align(int B, int Ms, int iters, int brute, const double* src_points, const int* src_offsets, const int* query_order,
+                     const double* tgt_sorted, const long long* tgt_keys, const int* tgt_order, const double* tgt_points, const int* tgt_offsets,
+                     const double* grid, const double* center, const double* gates, double tol_angle, double tol_shift, double* R, double* t,
+                     double* sums, int* matched, double* rms, double* dR, double* dt, int* status, int* done, int* steps, int* pair, double* d2,
+                     void* stream);
+/* out (M,3) = R_b p + t_b for every row of cloud b; the rows behind the last cloud are not written. */
+int etch_cloud_transform(int B, int M, const double* points, const int* offsets, const double* R, const double* t, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
