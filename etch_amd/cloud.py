@@ -13,12 +13,15 @@ handing it to the pipeline.
 
     python -m etch_amd.cloud --cloud_path scan.ply [--voxel V] [--outlier_k K --outlier_ratio R] [--outlier_radius r --outlier_min_neighbours m]
                              [--floor_threshold T --floor_up X Y Z --floor_max_tilt DEG] [--cluster_radius R]
-                             [--more_views B.ply C.ply .. --align_gate G --align_gate_min g --align_decay D --align_iters K --view_init F.npz --fuse_voxel V]
+                             [--more_views B.ply C.ply .. --align_gate G --align_gate_min g --align_decay D --align_iters K --align_metric {point,plane} --align_normal_k K
+                              --view_init F.npz --fuse_voxel V]
 
     nearest(source, target, gate), align(source, target, ...)  gated nearest rows across two clouds; rigid registration by ICP on the cell grid (section 23)
     transform(cloud, R, t), register_views(views), fuse(views, transforms, voxel=)   several views into one frame, one cloud per subject
 
-Neighbours are rows of the same cloud only.  The kernels (csrc/cloud_filter.hip, csrc/cloud_isolate.hip, csrc/cloud_align.hip) are exact and defined in fp64; there is no CPU path."""
+    normals(cloud, k=16, viewpoint=None)                       unit normal, surface variation and flag per row from the k nearest rows (section 24)
+
+Neighbours are rows of the same cloud only.  The kernels (csrc/cloud_filter.hip, csrc/cloud_isolate.hip, csrc/cloud_align.hip, csrc/cloud_normals.hip) are exact and defined in fp64; there is no CPU path."""
 import argparse
 import math
 import os
@@ -108,6 +111,52 @@ def knn_mean_distance(cloud, k, cell=None, brute=False):
         mean, status = ops.cloud_knn_mean(cloud.points, cloud.offsets, k, cell=cell, brute=brute)
     _raise_status("knn_mean_distance", status.cpu().numpy())
     return mean[:int(o[-1])]
+
+
+NORMAL_FLAG_FEW, NORMAL_FLAG_AMBIGUOUS = 1, 2
+NORMAL_MIN_K = 3
+
+
+def _check_normal_k(k):
+    if int(k) != k or not NORMAL_MIN_K <= int(k) <= MAX_K:
+        raise ValueError(f"k must be an integer in {NORMAL_MIN_K} .. {MAX_K}, got {k}")
+    return int(k)
+
+
+def _viewpoint(viewpoint, B, dev):
+    """None, one position (3,) for every cloud or (B,3) -> None or a (B,3) fp64 tensor on the device; ValueError for any other shape."""
+    import torch
+    if viewpoint is None:
+        return None
+    v = viewpoint.detach().cpu().numpy() if isinstance(viewpoint, torch.Tensor) else np.asarray(viewpoint)
+    if v.dtype.kind not in "fiu" or v.shape not in ((3,), (B, 3)):
+        raise ValueError(f"viewpoint must be (3,) or ({B},3) numbers, got {v.dtype} {v.shape}")
+    v = np.array(np.broadcast_to(v.astype(np.float64), (B, 3)), order="C")
+    if not np.isfinite(v).all():
+        raise ValueError("viewpoint must be finite")
+    return torch.from_numpy(v).to(dev)
+
+
+def normals(cloud, k=16, viewpoint=None, cell=None, brute=False, return_cov=False):
+    """Surface normals from the k nearest rows: -> normal (M,3) fp64, variation (M) fp64, flag (M) int32 on the device (and the
+    covariance (M,6) with return_cov).  The normal is the unit eigenvector of the smallest eigenvalue of the neighbourhood's covariance, variation
+    that eigenvalue over the trace; a row with flag != 0 (NORMAL_FLAG_FEW: a cloud of 1 or 2 rows, NORMAL_FLAG_AMBIGUOUS: collinear, coincident or
+    isotropic neighbours) gets (0, 0, 0).  Sign: the largest component positive, or towards `viewpoint` ((3,) or one position per cloud) --
+    nothing is propagated from row to row, so the field is not globally consistent on a closed surface without a viewpoint.  cell= and brute=True
+    change no bit.  ValueError for k outside 3 .. 32, a bad viewpoint or bad offsets, before any launch; EtchHipError naming the cloud that holds a
+    non-finite coordinate."""
+    k = _check_normal_k(k)
+    if cell is not None:
+        _check_positive(cell, "cell")
+    o = _offsets(cloud)
+    view = _viewpoint(viewpoint, len(o) - 1, cloud.points.device)
+    torch, ops, ctx = _ops(cloud)
+    with ctx:
+        out = ops.cloud_normals(cloud.points, cloud.offsets, k, viewpoint=view, cell=cell, brute=brute, return_cov=return_cov)
+    _raise_status("normals", out[3].cpu().numpy())
+    total = int(o[-1])
+    res = (out[0][:total], out[1][:total], out[2][:total])
+    return res + (out[4][:total],) if return_cov else res
 
 
 def radius_neighbour_count(cloud, radius, brute=False):
@@ -495,9 +544,34 @@ def nearest(source, target, gate, R=None, t=None, cell=None, brute=False):
     return pair[:int(so[-1])], d2[:int(so[-1])]
 
 
-def _align(torch, ops, source, target, a, R, t, brute):
+def _align(torch, ops, source, target, a, R, t, brute, normals=None):
     return ops.cloud_align(source.points, source.offsets, target.points, target.offsets, a["gates"], a["tol_angle"], a["tol_shift"], R=R, t=t,
-                           cell=a["cell"], brute=brute)
+                           cell=a["cell"], brute=brute, tgt_normals=normals)
+
+
+METRICS = ("point", "plane")
+
+
+def _check_metric(metric, normals=None, normal_k=16):
+    """The metric arguments of align and register_views, checked before any launch."""
+    if metric not in METRICS:
+        raise ValueError(f"metric must be one of {METRICS}, got {metric!r}")
+    if metric == "point" and normals is not None:
+        raise ValueError("normals= are the target's normals for metric='plane'; metric='point' takes none")
+    return _check_normal_k(normal_k) if metric == "plane" else None
+
+
+def _given_normals(normals, Mt, dev):
+    """normals= of align: (Mt,3) numbers, an array or a tensor -> fp64 on the device; ValueError for any other shape."""
+    import torch
+    if isinstance(normals, torch.Tensor):
+        if tuple(normals.shape) != (Mt, 3) or not (normals.dtype.is_floating_point or normals.dtype in (torch.int32, torch.int64)):
+            raise ValueError(f"normals must be ({Mt},3) numbers, got {normals.dtype} {tuple(normals.shape)}")
+        return normals.to(device=dev, dtype=torch.float64).contiguous()
+    n = np.asarray(normals)
+    if n.shape != (Mt, 3) or n.dtype.kind not in "fiu":
+        raise ValueError(f"normals must be ({Mt},3) numbers, got {n.dtype} {n.shape}")
+    return torch.from_numpy(np.array(n, np.float64, order="C")).to(dev)
 
 
 def _alignment(torch, out, B, what):
@@ -509,21 +583,31 @@ def _alignment(torch, out, B, what):
 
 
 def align(source, target, gate=0.2, gate_min=0.02, decay=0.9, iters=40, tol_angle=ALIGN_TOL_ANGLE, tol_shift=ALIGN_TOL_SHIFT, init=None, cell=None,
-          brute=False):
+          brute=False, metric="point", normals=None, normal_k=16):
     """Point-to-point ICP with a shrinking gate, every pair of clouds on its own: step k matches every moved source row to its nearest target row
     within max(gate_min, gate * decay^k), then takes the rigid step that fits the matched rows best (least squares, closed form).  A pair
     stops early once a step turns by less than tol_angle radians and moves its matched rows' centroid by less than tol_shift; the defaults end
     a pair whose matching has frozen (copies of the same rows) and are inert between two samplings of a surface, where the steps shrink by
     only ~0.86 a step and `iters` ends the loop: set tol_shift to a fraction of the expected rms there.  init: start poses
     (R, t) or (B,4,4); the method converges from about 20 degrees and 10 cm on a body, not from anywhere.  -> Alignment.  The loop runs on the
-    device without a host synchronisation; brute=True gives the same bits without the grid.  ValueError for bad arguments before any launch."""
+    device without a host synchronisation; brute=True gives the same bits without the grid.  ValueError for bad arguments before any launch.
+    metric="plane"  takes point-to-plane steps instead: the matching is the same, the step minimises the squared distances to the
+    tangent planes of the matched target rows, which lets a surface slide along itself and converges in a few steps where the point metric needs
+    tens.  The target's normals are computed once per call from normal_k neighbours (normals()), or handed in as normals= (Mt,3), a file's own for
+    example; their sign does not matter, a target row with the normal (0, 0, 0) matches nothing.  A step with fewer than 6 matched rows or an exactly
+    singular system (an exact plane, collinear rows) is STATUS_DEGENERATE; a merely near-symmetric target is not detected and slides."""
     a = _check_align(gate, gate_min, decay, iters, tol_angle, tol_shift, cell)
-    so, _ = _check_pairs(source, target)
+    normal_k = _check_metric(metric, normals, normal_k)
+    so, to = _check_pairs(source, target)
     B = len(so) - 1
+    if normals is not None:
+        normals = _given_normals(normals, target.points.shape[0], target.points.device)
     torch, ops, ctx = _ops(source)
     R, t = _init_pose(init, B, source.points.device)
     with ctx:
-        out = _align(torch, ops, source, target, a, R, t, brute)
+        if metric == "plane" and normals is None:
+            normals = ops.cloud_normals(target.points, target.offsets, normal_k)[0]     # a non-finite row: the loop's own status raises below
+        out = _align(torch, ops, source, target, a, R, t, brute, normals)
         res = _alignment(torch, out, B, "align")
     res.pair = res.pair[:int(so[-1])]
     return res
@@ -567,10 +651,12 @@ def _check_views(views):
     return views, offsets
 
 
-def register_views(views, init=None, **align_kw):
+def register_views(views, init=None, metric="point", normal_k=16, **align_kw):
     """Views (Clouds of B subjects each) into the frame of view 0: view k is aligned to the union of the views 0 .. k - 1 as already placed.
-    init: one start pose per view (None, (R, t) or (B,4,4)), or None.  -> a list of Alignment, one per view (view 0: the identity)."""
+    init: one start pose per view (None, (R, t) or (B,4,4)), or None.  metric="plane": align's point-to-plane steps, the normals computed on the
+    union anew for every view.  -> a list of Alignment, one per view (view 0: the identity)."""
     a = _check_align(**align_kw)
+    normal_k = _check_metric(metric, None, normal_k)
     views, offsets = _check_views(views)
     if init is not None and len(init) != len(views):
         raise ValueError(f"init must hold one entry per view, got {len(init)} for {len(views)} views")
@@ -584,7 +670,9 @@ def register_views(views, init=None, **align_kw):
         placed = [views[0]]
         for k in range(1, len(views)):
             R, t = _init_pose(None if init is None else init[k], B, dev)
-            res = _alignment(torch, _align(torch, ops, views[k], _union(torch, placed, offsets[:k]), a, R, t, False), B, f"register_views (view {k})")
+            union = _union(torch, placed, offsets[:k])
+            normals = ops.cloud_normals(union.points, union.offsets, normal_k)[0] if metric == "plane" else None
+            res = _alignment(torch, _align(torch, ops, views[k], union, a, R, t, False, normals), B, f"register_views (view {k})")
             res.pair = res.pair[:int(offsets[k][-1])]
             out.append(res)
             placed.append(Cloud(ops.cloud_transform(views[k].points, views[k].offsets, res.R, res.t), views[k].index, views[k].offsets, views[k].count, None))
@@ -616,6 +704,9 @@ def add_align_flags(p):
     p.add_argument("--align_gate_min", type=float, default=0.02, help="registration: the smallest gate")
     p.add_argument("--align_decay", type=float, default=0.9, help="registration: the gate shrinks by this factor a step")
     p.add_argument("--align_iters", type=int, default=40, help="registration: steps at most")
+    p.add_argument("--align_metric", type=str, default="point", choices=METRICS, help="registration: point-to-point steps, or point-to-plane steps "
+                   "on normals computed from the views (a few steps instead of tens)")
+    p.add_argument("--align_normal_k", type=int, default=16, help="registration with --align_metric plane: neighbours per normal (3 .. 32)")
     p.add_argument("--view_init", type=str, default=None, help="an .npz whose array `poses` (V,4,4) holds a start pose for every view of --more_views")
     p.add_argument("--fuse_voxel", type=float, default=0.0, help="fuse the registered views on a voxel grid of V metres; 0 = concatenate")
 
@@ -623,6 +714,7 @@ def add_align_flags(p):
 def check_align_flags(p, a):
     try:
         _check_align(a.align_gate, a.align_gate_min, a.align_decay, a.align_iters)
+        _check_metric(a.align_metric, None, a.align_normal_k)
     except ValueError as e:
         p.error(f"registration: {e}")
     if a.fuse_voxel < 0.0 or not math.isfinite(a.fuse_voxel):
@@ -642,13 +734,14 @@ def register_files(first, args):
             raise ValueError(f"--view_init: poses must be ({len(more)},4,4), got {poses.shape}")
         init = [None] + [poses[k:k + 1] for k in range(len(more))]
     views = [pack([v], args.device) for v in [first] + more]
-    res = register_views(views, init=init, gate=args.align_gate, gate_min=args.align_gate_min, decay=args.align_decay, iters=args.align_iters)
+    res = register_views(views, init=init, gate=args.align_gate, gate_min=args.align_gate_min, decay=args.align_decay, iters=args.align_iters,
+                         metric=args.align_metric, normal_k=args.align_normal_k)
     fused = fuse(views, res, voxel=args.fuse_voxel if args.fuse_voxel > 0.0 else None)
     pose = np.tile(np.eye(4), (len(views), 1, 1))
     for k, r in enumerate(res):
         pose[k, :3, :3], pose[k, :3, 3] = r.R[0].cpu().numpy(), r.t[0].cpu().numpy()
     report = {"view_pose": pose, "view_matched": np.array([int(r.matched[0]) for r in res]), "view_rms": np.array([float(r.rms[0]) for r in res]),
-              "view_steps": np.array([int(r.steps[0]) for r in res]), "view_status": np.array([int(r.status[0]) for r in res])}
+              "view_steps": np.array([int(r.steps[0]) for r in res]), "view_status": np.array([int(r.status[0]) for r in res]), "view_metric": np.array(args.align_metric)}
     return fused.points.cpu().numpy(), report
 
 

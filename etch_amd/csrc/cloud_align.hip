@@ -262,6 +262,127 @@ __global__ __launch_bounds__(ALIGN_GROUP) void align_step_kernel(const double* _
     steps[b] = steps[b] + 1;
 }
 
+// ---- the point-to-plane step: 32 sums, the 6 x 6 solve, compose ------------------------------------------------------------------
+#define ALIGN_PLANE_SUMS 32
+#define ALIGN_PLANE_LANES 4                  // values that share one pass of the tree through LDS (4 x 8 KiB)
+
+static_assert(ALIGN_PLANE_EPS == ETCH_ALIGN_PLANE_EPS, "the pivot threshold of the header");
+
+// ALIGN_PLANE_LANES block sums in one pass: every value walks the tree of align_block_sum (s[tid] + s[tid + w], w = 512 .. 1) in a row of its own,
+// so each sum has the bits a pass of its own would give, for a quarter of the barriers
+__device__ __forceinline__ void align_block_sum_lanes(double* v, double (*s)[ALIGN_GROUP]) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+#pragma unroll
+    for (int a = 0; a < ALIGN_PLANE_LANES; ++a) s[a][tid] = v[a];
+    __syncthreads();
+    for (int w = ALIGN_GROUP / 2; w >= 1; w >>= 1) {
+        if (tid < w) {
+#pragma unroll
+            for (int a = 0; a < ALIGN_PLANE_LANES; ++a) s[a][tid] = s[a][tid] + s[a][tid + w];
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int a = 0; a < ALIGN_PLANE_LANES; ++a) v[a] = s[a][0];
+}
+
+__global__ __launch_bounds__(ALIGN_GROUP) void align_step_plane_kernel(const double* __restrict__ S, const int* __restrict__ soff, const double* __restrict__ T,
+                                                                       const double* __restrict__ N, const int* __restrict__ toff,
+                                                                       const int* __restrict__ pair, const double* __restrict__ d2,
+                                                                       const double* __restrict__ grid, const double* __restrict__ center,
+                                                                       double tol_angle, double tol_shift, double* __restrict__ Rm, double* __restrict__ tv,
+                                                                       double* __restrict__ sums, int* __restrict__ matched, double* __restrict__ rms,
+                                                                       double* __restrict__ dR_out, double* __restrict__ dt_out, double* __restrict__ y_out,
+                                                                       int* __restrict__ status, int* __restrict__ done, int* __restrict__ steps) {
+    __shared__ double s[ALIGN_PLANE_LANES][ALIGN_GROUP];
+    __shared__ int si[ALIGN_GROUP];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (done[b]) return;                                                    // uniform over the workgroup
+    if (status[b] & ETCH_CLOUD_STATUS_NONFINITE) {
+        if (tid == 0) done[b] = 1;
+        return;
+    }
+    const int lo = soff[b], hi = soff[b + 1], tlo = toff[b], tn = toff[b + 1] - tlo;
+    double R[9], t[3];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = Rm[9 * b + k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t[k] = tv[3 * b + k];
+    const double c0 = center[3 * b], c1 = center[3 * b + 1], c2 = center[3 * b + 2];
+    double acc[ALIGN_PLANE_SUMS];
+#pragma unroll
+    for (int k = 0; k < ALIGN_PLANE_SUMS; ++k) acc[k] = 0.0;
+    int m = 0;
+    for (int i = lo + tid; i < hi; i += ALIGN_GROUP) {
+        const int j = pair[i];
+        if (j < 0 || j >= tn) continue;
+        const double* nr = N + 3 * (size_t)(tlo + j);
+        const double n0 = nr[0], n1 = nr[1], n2 = nr[2];
+        if (n0 == 0.0 && n1 == 0.0 && n2 == 0.0) continue;                  // a target row without a normal matches nothing
+        double x, y, z;
+        align_apply(R, t, S[3 * (size_t)i], S[3 * (size_t)i + 1], S[3 * (size_t)i + 2], x, y, z);
+        const double* q = T + 3 * (size_t)(tlo + j);
+        const double xc0 = x - c0, xc1 = y - c1, xc2 = z - c2;
+        const double r = ((x - q[0]) * n0 + (y - q[1]) * n1) + (z - q[2]) * n2;
+        const double J[6] = {xc1 * n2 - xc2 * n1, xc2 * n0 - xc0 * n2, xc0 * n1 - xc1 * n0, n0, n1, n2};
+        ++m;
+        int e = 0;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int c = a; c < 6; ++c) acc[e++] += J[a] * J[c];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) acc[21 + a] += J[a] * r;
+        acc[27] += r * r;
+        acc[28] += d2 ? d2[i] : cloud_d2(x, y, z, q);
+        acc[29] += xc0, acc[30] += xc1, acc[31] += xc2;
+    }
+    __syncthreads();
+    si[tid] = m;
+    __syncthreads();
+    for (int w = ALIGN_GROUP / 2; w >= 1; w >>= 1) {
+        if (tid < w) si[tid] += si[tid + w];
+        __syncthreads();
+    }
+    m = si[0];
+#pragma unroll
+    for (int k = 0; k < ALIGN_PLANE_SUMS; k += ALIGN_PLANE_LANES) align_block_sum_lanes(acc + k, s);
+    if (tid != 0) return;
+    double* const total = s[0];                                             // the 32 sums parked in LDS: the solve's 6 x 6 factor needs the registers
+#pragma unroll
+    for (int k = 0; k < ALIGN_PLANE_SUMS; ++k) total[k] = acc[k];
+    double dR[9], dt[3], yv[6], angle, shift;
+    const double c[3] = {c0, c1, c2};
+    const double e0 = c0 - grid[4 * b], e1 = c1 - grid[4 * b + 1], e2 = c2 - grid[4 * b + 2];
+    const double rho = sqrt((e0 * e0 + e1 * e1) + e2 * e2);
+    const bool good = align_plane_solve(m, total, c, rho, dR, dt, angle, shift, yv);
+    if (good) {
+        align_compose(dR, dt, R, t);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) Rm[9 * b + k] = R[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) tv[3 * b + k] = t[k];
+        if (angle < tol_angle && shift < tol_shift) done[b] = 1;
+    } else {
+        status[b] |= ETCH_ALIGN_STATUS_DEGENERATE;                          // the transform stays for the rest of the call
+        done[b] = 1;
+    }
+#pragma unroll
+    for (int k = 0; k < ALIGN_PLANE_SUMS; ++k) sums[ALIGN_PLANE_SUMS * b + k] = total[k];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) dR_out[9 * b + k] = dR[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) dt_out[3 * b + k] = dt[k];
+    if (y_out) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) y_out[6 * b + k] = yv[k];
+    }
+    matched[b] = m;
+    rms[b] = m > 0 ? sqrt(total[28] / (double)m) : INFINITY;
+    steps[b] = steps[b] + 1;
+}
+
 __global__ __launch_bounds__(256) void align_transform_kernel(int B, int M, const double* __restrict__ P, const int* __restrict__ offsets,
                                                               const double* __restrict__ Rm, const double* __restrict__ tv, double* __restrict__ out) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -286,6 +407,15 @@ int launch_step(int B, const double* src, const int* soff, const double* tgt, co
                 int* done, int* steps, hipStream_t st) {
     hipLaunchKernelGGL(align_step_kernel, dim3(B), dim3(ALIGN_GROUP), 0, st, src, soff, tgt, toff, pair, d2, center, tol_angle, tol_shift, R, t, sums, matched,
                        rms, dR, dt, status, done, steps);
+    ETCH_RETURN_IF_LAUNCH_FAILED();
+    return ETCH_OK;
+}
+
+int launch_step_plane(int B, const double* src, const int* soff, const double* tgt, const double* normals, const int* toff, const int* pair, const double* d2,
+                      const double* grid, const double* center, double tol_angle, double tol_shift, double* R, double* t, double* sums, int* matched,
+                      double* rms, double* dR, double* dt, double* y, int* status, int* done, int* steps, hipStream_t st) {
+    hipLaunchKernelGGL(align_step_plane_kernel, dim3(B), dim3(ALIGN_GROUP), 0, st, src, soff, tgt, normals, toff, pair, d2, grid, center, tol_angle, tol_shift,
+                       R, t, sums, matched, rms, dR, dt, y, status, done, steps);
     ETCH_RETURN_IF_LAUNCH_FAILED();
     return ETCH_OK;
 }
@@ -348,6 +478,42 @@ int etch_cloud_align(int B, int Ms, int iters, int brute, const double* src_poin
         }
         const int e = launch_step(B, src_points, src_offsets, tgt_points, tgt_offsets, pair, d2, center, tol_angle, tol_shift, R, t, sums, matched, rms, dR, dt,
                                   status, done, steps, st);
+        if (e != ETCH_OK) return e;
+    }
+    return ETCH_OK;
+}
+
+int etch_cloud_align_step_plane(int B, const double* src_points, const int* src_offsets, const double* tgt_points, const double* tgt_normals,
+                                const int* tgt_offsets, const int* pair, const double* d2, const double* grid, const double* center, double tol_angle,
+                                double tol_shift, double* R, double* t, double* sums, int* matched, double* rms, double* dR, double* dt, double* y,
+                                int* status, int* done, int* steps, void* stream) {
+    if (B < 1 || !src_points || !src_offsets || !tgt_points || !tgt_normals || !tgt_offsets || !pair || !grid || !center || !R || !t || !sums || !matched ||
+        !rms || !dR || !dt || !status || !done || !steps)
+        return ETCH_EINVAL;
+    if (!(tol_angle >= 0.0) || !(tol_shift >= 0.0)) return ETCH_EINVAL;
+    return launch_step_plane(B, src_points, src_offsets, tgt_points, tgt_normals, tgt_offsets, pair, d2, grid, center, tol_angle, tol_shift, R, t, sums, matched,
+                             rms, dR, dt, y, status, done, steps, (hipStream_t)stream);
+}
+
+int etch_cloud_align_plane(int B, int Ms, int iters, int brute, const double* src_points, const int* src_offsets, const int* query_order,
+                           const double* tgt_sorted, const long long* tgt_keys, const int* tgt_order, const double* tgt_points, const double* tgt_normals,
+                           const int* tgt_offsets, const double* grid, const double* center, const double* gates, double tol_angle, double tol_shift,
+                           double* R, double* t, double* sums, int* matched, double* rms, double* dR, double* dt, int* status, int* done, int* steps,
+                           int* pair, double* d2, void* stream) {
+    if (B < 1 || Ms < 0 || iters < 1 || !src_points || !src_offsets || !tgt_points || !tgt_normals || !tgt_offsets || !grid || !center || !gates || !R || !t ||
+        !sums || !matched || !rms || !dR || !dt || !status || !done || !steps || !pair || !d2)
+        return ETCH_EINVAL;
+    if (!brute && (!tgt_sorted || !tgt_keys || !tgt_order)) return ETCH_EINVAL;
+    if (!(tol_angle >= 0.0) || !(tol_shift >= 0.0)) return ETCH_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    for (int k = 0; k < iters; ++k) {                                       // two launches a step; the done flags live on the device
+        if (Ms > 0) {
+            const int e = launch_nearest(B, Ms, brute, src_points, src_offsets, query_order, brute ? tgt_points : tgt_sorted, tgt_keys, tgt_order, tgt_offsets,
+                                         grid, R, t, gates + k, done, status, pair, d2, st);
+            if (e != ETCH_OK) return e;
+        }
+        const int e = launch_step_plane(B, src_points, src_offsets, tgt_points, tgt_normals, tgt_offsets, pair, d2, grid, center, tol_angle, tol_shift, R, t, sums,
+                                        matched, rms, dR, dt, nullptr, status, done, steps, st);
         if (e != ETCH_OK) return e;
     }
     return ETCH_OK;

@@ -124,3 +124,96 @@ ALIGN_HD void align_compose(const double* dR, const double* dt, double* R, doubl
 #pragma unroll
     for (int k = 0; k < 3; ++k) t[k] = tn[k];
 }
+
+// ---- the point-to-plane step -------------------------------------------------------------------------------------------------
+#define ALIGN_PLANE_EPS 1e-9                 // = ETCH_ALIGN_PLANE_EPS of the header
+#define ALIGN_PLANE_SERIES 1e-4              // below this angle the half-angle sine and cosine come from their series
+
+// the index of entry (i, j), i <= j, of a symmetric 6 x 6 matrix stored as its upper triangle, row-major
+ALIGN_HD constexpr int align_tri(int i, int j) { return i * 6 - i * (i - 1) / 2 + (j - i); }
+
+// sums[32] = the 21 upper-triangle entries of A = sum J J^T (row-major), g = sum J r (6), sum r^2, sum d2, sum x' (3) over the m matched rows,
+// J = (x' x n, n), r = (x - q).n, x' = x - c.  Minimises sum (r + J.y)^2 over y = (omega, tau): A y = -g, solved as Abar z = -gbar with
+// Abar = D A D / m, gbar = D g / m, y = D z, D = diag(1/rho, 1/rho, 1/rho, 1, 1, 1) and rho the half-diagonal of the target's box: the rotation
+// columns then carry lengths relative to the cloud, like the translation columns, and nothing is scaled by diag(A) -- that scaling divides by zero
+// on an exactly planar target and hides a plane's, a cylinder's or a sphere's free motions behind pivots of 0.99.  LDL^T in the fixed order
+// 0 .. 5, no pivoting.  -> dR (9) from the quaternion (cos th/2, sin(th/2) omega / th), th = |omega|, normalised and written in the 1 - 2 (..)
+// form, so dR is a rotation to rounding whatever the data; dt = c - dR c + tau; angle = th; shift = |(dR - I) mean x' + tau|, the movement of the
+// matched rows' centroid; y (6) = omega, tau.  Returns false, and dR = I, dt = 0, y = 0, where the step is degenerate: m < 6, rho not positive
+// and finite, or a pivot d_i that fails d_i > ALIGN_PLANE_EPS max_j Abar_jj (a zero or NaN pivot fails and is never divided by).  The criterion
+// guards exact singularity only -- an exact plane with exact normals, collinear data, no normal at all; a merely near-symmetric target (a noisy
+// plane, a cylinder) is not flagged and slides, as a planar patch does under Horn's rule above.
+ALIGN_HD bool align_plane_solve(int m, const double* sums, const double* c, double rho, double* dR, double* dt, double& angle, double& shift, double* y) {
+    dR[0] = dR[4] = dR[8] = 1.0;
+    dR[1] = dR[2] = dR[3] = dR[5] = dR[6] = dR[7] = 0.0;
+    dt[0] = dt[1] = dt[2] = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) y[i] = 0.0;
+    angle = 0.0, shift = 0.0;
+    if (m < 6 || !(rho > 0.0) || !std::isfinite(rho)) return false;
+    const double dm = (double)m, inv = 1.0 / rho;
+    double L[6][6], d[6], z[6];                                      // L: the scaled matrix on and above the diagonal, the factor below it
+    double top = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+#pragma unroll
+        for (int j = i; j < 6; ++j) {
+            double v = sums[align_tri(i, j)] / dm;
+            if (i < 3) v = v * inv;
+            if (j < 3) v = v * inv;
+            L[i][j] = v;
+        }
+        z[i] = -(i < 3 ? (sums[21 + i] / dm) * inv : sums[21 + i] / dm);
+        if (L[i][i] > top) top = L[i][i];
+    }
+    const double floor_ = ALIGN_PLANE_EPS * top;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        double dj = L[j][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) dj = dj - (L[j][k] * L[j][k]) * d[k];
+        if (!(dj > floor_) || !(dj > 0.0)) return false;
+        d[j] = dj;
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            double v = L[j][i];
+#pragma unroll
+            for (int k = 0; k < j; ++k) v = v - (L[i][k] * L[j][k]) * d[k];
+            L[i][j] = v / dj;
+        }
+    }
+#pragma unroll
+    for (int i = 1; i < 6; ++i)                                      // L w = -gbar
+#pragma unroll
+        for (int k = 0; k < i; ++k) z[i] = z[i] - L[i][k] * z[k];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) z[i] = z[i] / d[i];
+#pragma unroll
+    for (int i = 4; i >= 0; --i)                                     // L^T z = w
+#pragma unroll
+        for (int k = i + 1; k < 6; ++k) z[i] = z[i] - L[k][i] * z[k];
+    const double wx = z[0] * inv, wy = z[1] * inv, wz = z[2] * inv, tx = z[3], ty = z[4], tz = z[5];
+    const double th = sqrt((wx * wx + wy * wy) + wz * wz);
+    if (!std::isfinite(th) || !std::isfinite(tx) || !std::isfinite(ty) || !std::isfinite(tz)) return false;
+    double qw, kf;                                                   // q = (qw, kf omega)
+    if (th < ALIGN_PLANE_SERIES) qw = 1.0 - (th * th) / 8.0, kf = 0.5 - (th * th) / 48.0;
+    else qw = cos(0.5 * th), kf = sin(0.5 * th) / th;
+    double qx = kf * wx, qy = kf * wy, qz = kf * wz;
+    const double len = sqrt(((qw * qw + qx * qx) + qy * qy) + qz * qz);
+    qw = qw / len, qx = qx / len, qy = qy / len, qz = qz / len;
+    dR[0] = 1.0 - 2.0 * (qy * qy + qz * qz), dR[1] = 2.0 * (qx * qy - qw * qz), dR[2] = 2.0 * (qx * qz + qw * qy);
+    dR[3] = 2.0 * (qx * qy + qw * qz), dR[4] = 1.0 - 2.0 * (qx * qx + qz * qz), dR[5] = 2.0 * (qy * qz - qw * qx);
+    dR[6] = 2.0 * (qx * qz - qw * qy), dR[7] = 2.0 * (qy * qz + qw * qx), dR[8] = 1.0 - 2.0 * (qx * qx + qy * qy);
+    const double tau[3] = {tx, ty, tz};
+    const double mx[3] = {sums[29] / dm, sums[30] / dm, sums[31] / dm};
+    double sh[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        dt[r] = (c[r] - ((dR[3 * r] * c[0] + dR[3 * r + 1] * c[1]) + dR[3 * r + 2] * c[2])) + tau[r];
+        sh[r] = (((dR[3 * r] * mx[0] + dR[3 * r + 1] * mx[1]) + dR[3 * r + 2] * mx[2]) - mx[r]) + tau[r];
+    }
+    shift = sqrt((sh[0] * sh[0] + sh[1] * sh[1]) + sh[2] * sh[2]);
+    angle = th;
+    y[0] = wx, y[1] = wy, y[2] = wz, y[3] = tx, y[4] = ty, y[5] = tz;
+    return true;
+}

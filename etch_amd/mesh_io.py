@@ -292,7 +292,7 @@ def read_ply(path):
         return parse_ply(fh.read(), str(path))
 
 
-def format_ply(points_or_mesh, binary=True):
+def format_ply(points_or_mesh, binary=True, normals=None):
     v = getattr(points_or_mesh, "vertices", points_or_mesh)
     f = getattr(points_or_mesh, "faces", None)
     v = np.asarray(v)
@@ -303,8 +303,13 @@ def format_ply(points_or_mesh, binary=True):
     f = np.zeros((0, 3), np.int64) if f is None else np.asarray(f)
     if f.ndim != 2 or f.shape[1] != 3 or (len(f) and (f.min() < 0 or f.max() >= len(v))):
         raise ValueError("write_ply: faces must be (F,3) indices into the vertices")
+    if normals is not None:                              # one row per vertex, in the type of the points: x y z nx ny nz
+        nrm = np.asarray(normals)
+        if nrm.shape != v.shape or nrm.dtype.kind not in "fiu":
+            raise ValueError(f"write_ply: normals must be {v.shape} numbers, got {nrm.dtype} {nrm.shape}")
+        v = np.ascontiguousarray(np.concatenate([v, nrm.astype(v.dtype)], 1))
     head = [b"ply", b"format binary_little_endian 1.0" if binary else b"format ascii 1.0", b"element vertex %d" % len(v)]
-    head += [b"property %s %s" % (t.encode(), a) for a in (b"x", b"y", b"z")]
+    head += [b"property %s %s" % (t.encode(), a) for a in (b"x", b"y", b"z", b"nx", b"ny", b"nz")[:v.shape[1]]]
     if len(f):
         head += [b"element face %d" % len(f), b"property list uchar int vertex_indices"]
     head = b"\n".join(head + [b"end_header"]) + b"\n"
@@ -315,25 +320,34 @@ def format_ply(points_or_mesh, binary=True):
             rows["n"], rows["i"] = 3, f
             body += rows.tobytes()
     else:
-        body = "".join(f"{repr(float(a))} {repr(float(b))} {repr(float(c))}\n" for a, b, c in v.astype(np.float64)).encode()
+        body = "".join(" ".join(repr(float(a)) for a in row) + "\n" for row in v.astype(np.float64)).encode()
         body += "".join(f"3 {int(a)} {int(b)} {int(c)}\n" for a, b, c in f).encode()
     return head + body
 
 
-def write_ply(points_or_mesh, path, binary=True):
+def write_ply(points_or_mesh, path, binary=True, normals=None):
     """Points (M,3) or a mesh (vertices, faces) as PLY: float32 points stay `float`, everything else is written as `double`, so a float64
-    round trip is exact in both forms (the ascii form writes the shortest text that reads back to the same double)."""
-    data = format_ply(points_or_mesh, binary)
+    round trip is exact in both forms (the ascii form writes the shortest text that reads back to the same double).  normals (M,3), one per
+    point or per vertex of the mesh, are written as nx ny nz in the type of the points; without them the file is what it always was."""
+    data = format_ply(points_or_mesh, binary, normals)
     with open(path, "wb") as fh:
         fh.write(data)
 
 
-def read_cloud(path):
+def read_cloud(path, return_normals=False):
     """The points of a file as (M,3) float64: .ply, .obj (its vertices), .npy / .npz (an (M,3) array; a .npz holds one array, or one named
-    `points`) and .xyz / .txt (three columns, further columns ignored)."""
+    `points`) and .xyz / .txt (three columns, further columns ignored).  return_normals: -> points, normals, the nx ny nz of a .ply as (M,3)
+    float64, None for a file that has none (every other kind)."""
+    points, normals = _read_cloud(path)
+    return (points, normals) if return_normals else points
+
+
+def _read_cloud(path):
     ext = os.path.splitext(str(path))[1].lower()
+    normals = None
     if ext == ".ply":
-        p = read_ply(path).vertices
+        ply = read_ply(path)
+        p, normals = ply.vertices, ply.normals
     elif ext == ".obj":
         p = read_obj(path).vertices
     elif ext == ".npy":
@@ -356,7 +370,7 @@ def read_cloud(path):
     p = np.asarray(p)
     if p.ndim != 2 or p.shape[1] != 3 or p.dtype.kind not in "fiu":
         raise ValueError(f"{path}: a cloud is an (M,3) array of numbers, got {p.dtype} {p.shape}")
-    return np.ascontiguousarray(p, np.float64)
+    return np.ascontiguousarray(p, np.float64), None if normals is None else np.ascontiguousarray(normals, np.float64)
 
 
 def pack_meshes(meshes):

@@ -2173,6 +2173,31 @@ def cloud_knn_mean(points, offsets, k, cell=None, brute=False):
     return mean, status
 
 
+def cloud_normals(points, offsets, k, viewpoint=None, cell=None, brute=False, return_cov=False):
+    """etch_cloud_normals: the normal of every row from its min(k, n - 1) nearest other rows of its cloud, 3 <= k <= 32, on the
+    cell grid of cloud_knn_mean (the same rule for the cell size; `cell` overrides it and changes no bit).  viewpoint (B,3) fp64 or None.
+    -> normal (M,3) fp64, variation (M) fp64, flag (M) int32 (zeros for a cloud with a status bit), status (B) int32, and with return_cov the
+    covariance (M,6) fp64, all still on the device."""
+    B, M = _cloud_args(points, offsets, "cloud_normals")
+    if not 3 <= int(k) <= CLOUD_MAX_K:
+        raise _lib.EtchHipError(f"cloud_normals: k must lie in 3 .. {CLOUD_MAX_K}, got {k}")
+    if cell is not None and not (float(cell) > 0.0 and math.isfinite(float(cell))):
+        raise _lib.EtchHipError(f"cloud_normals: cell must be positive and finite, got {cell}")
+    if viewpoint is not None:
+        _need(viewpoint, torch.float64, "viewpoint")
+        if tuple(viewpoint.shape) != (B, 3):
+            raise _lib.EtchHipError(f"cloud_normals: viewpoint must be ({B},3), got {tuple(viewpoint.shape)}")
+    dev = points.device
+    grid, status, sp, sk, order = cloud_cell_grid(points, offsets, 0, k, 0.0 if cell is None else float(cell), sort=not brute)
+    normal = torch.zeros((M, 3), dtype=torch.float64, device=dev)
+    variation = torch.zeros((M,), dtype=torch.float64, device=dev)
+    flag = torch.zeros((M,), dtype=torch.int32, device=dev)
+    cov = torch.zeros((M, 6), dtype=torch.float64, device=dev) if return_cov else None
+    _lib.call("etch_cloud_normals", int(B), int(M), int(k), int(bool(brute)), points if brute else sp, sk, order, offsets, grid, status, viewpoint,
+              normal, variation, flag, cov)
+    return (normal, variation, flag, status, cov) if return_cov else (normal, variation, flag, status)
+
+
 def cloud_radius_count(points, offsets, radius, brute=False):
     """The number of other rows of its cloud within `radius` of every row (d2 <= radius * radius).  -> count (M) int32, status (B) int32."""
     B, M = _cloud_args(points, offsets, "cloud_radius_count")
@@ -2447,11 +2472,41 @@ def cloud_align_step(src_points, src_offsets, tgt_points, tgt_offsets, pair, d2=
     return s["dR"], s["dt"], s["matched"], s["sums"], status, R, t
 
 
-def cloud_align(src_points, src_offsets, tgt_points, tgt_offsets, gates, tol_angle, tol_shift, R=None, t=None, cell=None, brute=False):
+def _align_normals(tgt_normals, Mt, what):
+    _need(tgt_normals, torch.float64, "tgt_normals")
+    if tuple(tgt_normals.shape) != (Mt, 3):
+        raise _lib.EtchHipError(f"{what}: tgt_normals must be ({Mt},3), got {tuple(tgt_normals.shape)}")
+    return tgt_normals
+
+
+def cloud_align_step_plane(src_points, src_offsets, tgt_points, tgt_offsets, tgt_normals, pair, d2=None, R=None, t=None):
+    """etch_cloud_align_step_plane: one point-to-plane step from the given pairs and the target's normals (Mt,3).
+    -> dR (B,3,3), dt (B,3), m (B) int32, sums (B,32), y (B,6) = omega, tau, then status (B) int32 and the composed R (B,3,3), t (B,3) -- unchanged
+    where the status holds ALIGN_STATUS_DEGENERATE."""
+    B, Ms, Mt = _align_pairs(src_points, src_offsets, tgt_points, tgt_offsets, "cloud_align_step_plane")
+    _need(pair, torch.int32, "pair")
+    if pair.shape != (Ms,) or (d2 is not None and _need(d2, torch.float64, "d2").shape != (Ms,)):
+        raise _lib.EtchHipError(f"cloud_align_step_plane: pair and d2 must be ({Ms},)")
+    _align_normals(tgt_normals, Mt, "cloud_align_step_plane")
+    dev = src_points.device
+    R, t = _align_transform(R, t, B, dev, "cloud_align_step_plane")
+    grid, center, status, _, _, _ = cloud_align_grid(tgt_points, tgt_offsets, 1.0, sort=False)
+    s = _align_state(B, Ms, dev)
+    sums = torch.zeros((B, 32), dtype=torch.float64, device=dev)
+    y = torch.zeros((B, 6), dtype=torch.float64, device=dev)
+    _lib.call("etch_cloud_align_step_plane", int(B), _some(src_points), src_offsets, _some(tgt_points), _some(tgt_normals), tgt_offsets, _some(pair), d2, grid,
+              center, 0.0, 0.0, R, t, sums, s["matched"], s["rms"], s["dR"], s["dt"], y, status, s["done"], s["steps"])
+    return s["dR"], s["dt"], s["matched"], sums, y, status, R, t
+
+
+def cloud_align(src_points, src_offsets, tgt_points, tgt_offsets, gates, tol_angle, tol_shift, R=None, t=None, cell=None, brute=False, tgt_normals=None):
     """etch_cloud_align: len(gates) steps of nearest + rigid step, the target's grid built once, no host synchronisation.  gates: the gate of every
-    step, host floats.  -> a dict of device tensors: R (B,3,3), t (B,3), matched (B) int32, rms (B), steps (B) int32, status (B) int32, pair (Ms)
+    step, host floats.  tgt_normals (Mt,3) fp64: the point-to-plane step of etch_cloud_align_plane instead of Horn's (None: the point metric).
+    -> a dict of device tensors: R (B,3,3), t (B,3), matched (B) int32, rms (B), steps (B) int32, status (B) int32, pair (Ms)
     int32 and d2 (Ms) of the last matching, done (B) int32."""
     B, Ms, Mt = _align_pairs(src_points, src_offsets, tgt_points, tgt_offsets, "cloud_align")
+    if tgt_normals is not None:
+        _align_normals(tgt_normals, Mt, "cloud_align")
     gates = [float(g) for g in gates]
     if not gates or not all(g > 0.0 and math.isfinite(g) for g in gates):
         raise _lib.EtchHipError("cloud_align: gates must be a non-empty list of positive finite numbers")
@@ -2466,6 +2521,12 @@ def cloud_align(src_points, src_offsets, tgt_points, tgt_offsets, gates, tol_ang
     pair = torch.full((Ms,), -1, dtype=torch.int32, device=dev)
     d2 = torch.full((Ms,), math.inf, dtype=torch.float64, device=dev)
     g = torch.tensor(gates, dtype=torch.float64, device=dev)
+    if tgt_normals is not None:
+        sums = torch.zeros((B, 32), dtype=torch.float64, device=dev)
+        _lib.call("etch_cloud_align_plane", int(B), int(Ms), len(gates), int(bool(brute)), _some(src_points), src_offsets, qorder, _some(sp), _some(sk), _some(order),
+                  _some(tgt_points), _some(tgt_normals), tgt_offsets, grid, center, g, float(tol_angle), float(tol_shift), R, t, sums, s["matched"], s["rms"], s["dR"],
+                  s["dt"], status, s["done"], s["steps"], _some(pair), _some(d2))
+        return dict(R=R, t=t, matched=s["matched"], rms=s["rms"], steps=s["steps"], status=status, pair=pair, d2=d2, done=s["done"])
     _lib.call("etch_cloud_align", int(B), int(Ms), len(gates), int(bool(brute)), _some(src_points), src_offsets, qorder, _some(sp), _some(sk), _some(order), _some(tgt_points),
               tgt_offsets, grid, center, g, float(tol_angle), float(tol_shift), R, t, s["sums"], s["matched"], s["rms"], s["dR"], s["dt"], status, s["done"],
               s["steps"], _some(pair), _some(d2))

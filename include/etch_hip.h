@@ -1131,6 +1131,60 @@ int etch_cloud_align(int B, int Ms, int iters, int brute, const double* src_poin
 /* out (M,3) = R_b p + t_b for every row of cloud b; the rows behind the last cloud are not written. */
 int etch_cloud_transform(int B, int M, const double* points, const int* offsets, const double* R, const double* t, double* out, void* stream);
 
+/* ---- raw point clouds: surface normals on the cell grid (csrc/cloud_normals.hip, csrc/cloud_normal_solve.h) ------------------ */
+
+#define ETCH_NORMAL_FLAG_FEW 1           /* the row has fewer than 2 neighbours (a cloud of 1 or 2 rows) */
+#define ETCH_NORMAL_FLAG_AMBIGUOUS 2     /* lambda1 - lambda0 > ETCH_NORMAL_GAP_EPS lambda2 does not hold: collinear, coincident or isotropic neighbours */
+#define ETCH_NORMAL_GAP_EPS 1e-9
+/* For row i of a cloud with n rows, ke = min(k, n - 1), 3 <= k <= ETCH_CLOUD_MAX_K.  The neighbourhood is the ke least (d2, row) pairs among the
+ * OTHER rows of the cloud, d2 = ((dx dx + dy dy) + dz dz), row = the original row: a tie in d2 goes to the lower row.  With e_j = q_j - p_i per
+ * component, taken in ascending (d2, row) order, s = sum e_j and S_ab = sum e_a e_b (the product rounded once), each a sequential sum from 0 in
+ * that order; w = ke + 1 (the row itself counts with e = 0), mu = s / w, C_ab = S_ab / w - mu_a mu_b.  cov (M,6) fp64 = C_xx, C_xy, C_xz, C_yy,
+ * C_yz, C_zz or NULL (not written): the order is fixed, so it is defined to the bit.  Cyclic Jacobi (pairs (0,1), (0,2), (1,2), at most 10 sweeps)
+ * gives lambda0 <= lambda1 <= lambda2; normal (M,3) fp64 = the normalised eigenvector of lambda0, variation (M) fp64 = lambda0 / ((lambda0 +
+ * lambda1) + lambda2), 0 where that trace is not positive.  flag (M) int32 = ETCH_NORMAL_FLAG_*; a flagged row gets the normal (0, 0, 0).
+ * Sign: the component of the largest magnitude is positive, a tie to the lowest axis; with viewpoint (B,3) fp64, one sensor position per cloud
+ * (NULL: none), the normal is then flipped where ((n_x w_x + n_y w_y) + n_z w_z) < 0, w = viewpoint - p, so n.(v - p) >= 0 and an exact 0
+ * keeps the first rule.  No orientation is propagated between rows.
+ * Inputs as etch_cloud_knn_mean takes them: the mode 0 keys, sorted; exact for any cell size; brute != 0: every query scans its whole cloud,
+ * sorted_points is then the unsorted points and sorted_keys, order, grid may be NULL.  All outputs are by original row.  Rows of a cloud with
+ * ETCH_CLOUD_STATUS_NONFINITE are not written. */
+int etch_cloud_normals(int B, int M, int k, int brute, const double* sorted_points, const long long* sorted_keys, const int* order, const int* offsets,
+                       const double* grid, const int* status, const double* viewpoint, double* normal, double* variation, int* flag, double* cov,
+                       void* stream);
+
+/* ---- raw point clouds: the point-to-plane step of the registration (csrc/cloud_align.hip, csrc/cloud_align_solve.h) ---------- */
+
+/* A pivot d_i of the LDL^T factorisation below must exceed this fraction of the largest diagonal entry of the scaled matrix. */
+#define ETCH_ALIGN_PLANE_EPS 1e-9
+/* One point-to-plane step per pair from given pairs.  tgt_normals (Mt,3) fp64: one normal per UNSORTED target row, as etch_cloud_normals or a
+ * file gives them; the residual ((x - q).n)^2 is blind to the sign of n, so no consistent orientation is needed.  A matched row is a source
+ * row i with pair[i] >= 0 whose target row has a non-zero normal.  x = R p + t, c = center, x' = x - c and d2 as etch_cloud_align_step states them;
+ * r = ((dx n_x + dy n_y) + dz n_z), d = x - q; a = x' x n, every product rounded once; J = (a, n).  sums (B,32) fp64 = the 21 upper-triangle
+ * entries of sum J J^T, row-major (a product rounded once per term), the 6 of sum J r, sum r^2, sum d2, sum x' (3), each summed as
+ * etch_cloud_align_step sums: one strided partial per thread (rows lo + tid, lo + tid + 1024, ..) and the fixed tree over the 1024 partials (four sums
+ * share a pass through LDS, each in the tree a pass of its own would walk).  matched (B) = m, rms (B) = sqrt(sum d2 / m) (+inf for m = 0).
+ * Solve A y = -g, y = (omega, tau): the three rotation rows and columns are scaled by 1 / rho, rho = |center - box minimum| from grid (B,4) (as
+ * etch_cloud_align_grid wrote it: always needed, brute or not), everything is divided by m, LDL^T runs in the fixed order 0 .. 5.  The step is
+ * degenerate -- ETCH_ALIGN_STATUS_DEGENERATE is ORed into status, R and t stay, dR = I, dt = 0, y = 0, done is set -- where m < 6, rho is not
+ * positive, or a pivot fails d_i > ETCH_ALIGN_PLANE_EPS max_j Abar_jj (a zero or NaN pivot fails).  That guards exact singularity only: an exact
+ * plane with exact normals, collinear data, no normals; a near-symmetric target is not flagged, it slides.  Update: th = |omega|, dR from the
+ * quaternion (cos th/2, sin(th/2) omega / th) (a series below th = 1e-4), normalised, in the 1 - 2 (yy + zz) form; dt = c - dR c + tau;
+ * R <- dR R, t <- dR t + dt in place; y (B,6) fp64 = omega, tau (NULL: not written).  done is also set when th < tol_angle and the matched rows'
+ * centroid moved by |(dR - I) mean x' + tau| < tol_shift.  status, done and steps as etch_cloud_align_step. */
+int etch_cloud_align_step_plane(int B, const double* src_points, const int* src_offsets, const double* tgt_points, const double* tgt_normals,
+                                const int* tgt_offsets, const int* pair, const double* d2, const double* grid, const double* center, double tol_angle,
+                                double tol_shift, double* R, double* t, double* sums, int* matched, double* rms, double* dR, double* dt, double* y,
+                                int* status, int* done, int* steps, void* stream);
+/* etch_cloud_align with the point-to-plane step: iters times etch_cloud_nearest (unchanged: the nearest row within the gate, whatever its normal)
+ * and etch_cloud_align_step_plane, 2 iters launches and no host synchronisation; sums is (B,32).  brute != 0 reads tgt_points, tgt_normals and
+ * grid alone and gives the same bits: the pairs are the same, and the sums depend on the pairs alone. */
+int etch_cloud_align_plane(int B, int Ms, int iters, int brute, const double* src_points, const int* src_offsets, const int* query_order,
+                           const double* tgt_sorted, const long long* tgt_keys, const int* tgt_order, const double* tgt_points, const double* tgt_normals,
+                           const int* tgt_offsets, const double* grid, const double* center, const double* gates, double tol_angle, double tol_shift,
+                           double* R, double* t, double* sums, int* matched, double* rms, double* dR, double* dt, int* status, int* done, int* steps,
+                           int* pair, double* d2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
