@@ -22,7 +22,8 @@ EXTRA = {"index_ops.hip": ["-ffp-contract=off"], "chamfer_fit.hip": ["-ffp-contr
          "geodesic.hip": ["-ffp-contract=off"], "mesh_sample.hip": ["-ffp-contract=off"], "register.hip": ["-ffp-contract=off"],
          "depth_render.hip": ["-ffp-contract=off"], "surface_fit.hip": ["-ffp-contract=off"], "containment.hip": ["-ffp-contract=off"],
          "cloud_filter.hip": ["-ffp-contract=off"], "cloud_isolate.hip": ["-ffp-contract=off"],
-         "cloud_align.hip": ["-ffp-contract=off"], "cloud_normals.hip": ["-ffp-contract=off"]}
+         "cloud_align.hip": ["-ffp-contract=off"], "cloud_normals.hip": ["-ffp-contract=off"],
+         "cloud_global.hip": ["-ffp-contract=off"]}
 
 
 def hipcc():

@@ -14,14 +14,18 @@ handing it to the pipeline.
     python -m etch_amd.cloud --cloud_path scan.ply [--voxel V] [--outlier_k K --outlier_ratio R] [--outlier_radius r --outlier_min_neighbours m]
                              [--floor_threshold T --floor_up X Y Z --floor_max_tilt DEG] [--cluster_radius R]
                              [--more_views B.ply C.ply .. --align_gate G --align_gate_min g --align_decay D --align_iters K --align_metric {point,plane} --align_normal_k K
-                              --view_init F.npz --fuse_voxel V]
+                              --view_init F.npz --fuse_voxel V
+                              --align_global --align_global_voxel V --align_feature_k K --align_hypotheses H --view_origin X Y Z]
 
     nearest(source, target, gate), align(source, target, ...)  gated nearest rows across two clouds; rigid registration by ICP on the cell grid (section 23)
     transform(cloud, R, t), register_views(views), fuse(views, transforms, voxel=)   several views into one frame, one cloud per subject
 
     normals(cloud, k=16, viewpoint=None)                       unit normal, surface variation and flag per row from the k nearest rows (section 24)
 
-Neighbours are rows of the same cloud only.  The kernels (csrc/cloud_filter.hip, csrc/cloud_isolate.hip, csrc/cloud_align.hip, csrc/cloud_normals.hip) are exact and defined in fp64; there is no CPU path."""
+    features(cloud, k=32, viewpoint=), global_align(source, target, keys, viewpoint=(vs, vt), ...)   FPFH descriptors; a rough pose from nothing by
+                                                               feature matches and RANSAC, the start of align(init="global") (section 25)
+
+Neighbours are rows of the same cloud only.  The kernels (csrc/cloud_filter.hip, csrc/cloud_isolate.hip, csrc/cloud_align.hip, csrc/cloud_normals.hip, csrc/cloud_global.hip) are exact and defined in fp64; there is no CPU path."""
 import argparse
 import math
 import os
@@ -583,7 +587,7 @@ def _alignment(torch, out, B, what):
 
 
 def align(source, target, gate=0.2, gate_min=0.02, decay=0.9, iters=40, tol_angle=ALIGN_TOL_ANGLE, tol_shift=ALIGN_TOL_SHIFT, init=None, cell=None,
-          brute=False, metric="point", normals=None, normal_k=16):
+          brute=False, metric="point", normals=None, normal_k=16, keys=None, viewpoint=None, global_kw=None):
     """Point-to-point ICP with a shrinking gate, every pair of clouds on its own: step k matches every moved source row to its nearest target row
     within max(gate_min, gate * decay^k), then takes the rigid step that fits the matched rows best (least squares, closed form).  A pair
     stops early once a step turns by less than tol_angle radians and moves its matched rows' centroid by less than tol_shift; the defaults end
@@ -595,13 +599,26 @@ def align(source, target, gate=0.2, gate_min=0.02, decay=0.9, iters=40, tol_angl
     tangent planes of the matched target rows, which lets a surface slide along itself and converges in a few steps where the point metric needs
     tens.  The target's normals are computed once per call from normal_k neighbours (normals()), or handed in as normals= (Mt,3), a file's own for
     example; their sign does not matter, a target row with the normal (0, 0, 0) matches nothing.  A step with fewer than 6 matched rows or an exactly
-    singular system (an exact plane, collinear rows) is STATUS_DEGENERATE; a merely near-symmetric target is not detected and slides."""
+    singular system (an exact plane, collinear rows) is STATUS_DEGENERATE; a merely near-symmetric target is not detected and slides.
+    init="global"  starts from global_align(source, target, keys, viewpoint=viewpoint, **global_kw) instead of a given pose: keys
+    and viewpoint = (the source's, the target's) sensor position are then needed.  Where it finds no pose the loop starts from the identity and the
+    status holds STATUS_GLOBAL_NOT_FOUND; the GlobalAlignment is the result's .start."""
     a = _check_align(gate, gate_min, decay, iters, tol_angle, tol_shift, cell)
     normal_k = _check_metric(metric, normals, normal_k)
     so, to = _check_pairs(source, target)
     B = len(so) - 1
     if normals is not None:
         normals = _given_normals(normals, target.points.shape[0], target.points.device)
+    start = None
+    if isinstance(init, str):
+        if init != "global":
+            raise ValueError(f"init must be None, poses or 'global', got {init!r}")
+        if keys is None:
+            raise ValueError("init='global' needs keys")
+        start = global_align(source, target, keys, viewpoint=viewpoint, **(global_kw or {}))
+        init = (start.R, start.t)
+    elif keys is not None or viewpoint is not None or global_kw is not None:
+        raise ValueError("keys, viewpoint and global_kw belong to init='global'")
     torch, ops, ctx = _ops(source)
     R, t = _init_pose(init, B, source.points.device)
     with ctx:
@@ -610,6 +627,9 @@ def align(source, target, gate=0.2, gate_min=0.02, decay=0.9, iters=40, tol_angl
         out = _align(torch, ops, source, target, a, R, t, brute, normals)
         res = _alignment(torch, out, B, "align")
     res.pair = res.pair[:int(so[-1])]
+    if start is not None:
+        res.status = res.status | np.where(start.found, 0, STATUS_GLOBAL_NOT_FOUND).astype(np.int32)
+        res.start = start
     return res
 
 
@@ -651,29 +671,91 @@ def _check_views(views):
     return views, offsets
 
 
-def register_views(views, init=None, metric="point", normal_k=16, **align_kw):
+def _union_rows(torch, rows, offsets):
+    """Per-row tensors of several parts (host offsets given) in the row order of _union."""
+    B = len(offsets[0]) - 1
+    return torch.cat([r[int(o[b]):int(o[b + 1])] for b in range(B) for r, o in zip(rows, offsets)]).contiguous()
+
+
+def _global_views_prepare(torch, ops, views, a, viewpoints):
+    """The descriptors of every view in its own frame, once: -> a list of (Cloud trimmed to its rows, feature, has_feature, host offsets)."""
+    B = views[0].offsets.numel() - 1
+    dev = views[0].points.device
+    if viewpoints is None or len(viewpoints) != len(views):
+        raise ValueError(f"viewpoints must hold one sensor position per view, got {0 if viewpoints is None else len(viewpoints)} for {len(views)} views")
+    vp = [_viewpoint(v, B, dev) for v in viewpoints]
+    if any(v is None for v in vp):
+        raise ValueError("viewpoints must give a sensor position for every view")
+    words, sides = [], []
+    for v, w in zip(views, vp):
+        n = len(words)
+        sides.append(_global_side(ops, v, a, w, words) + (len(words) - n,))
+    host = torch.cat(words + [s[0].offsets for s in sides]).cpu().numpy()      # one readback for all views
+    at, out = 0, []
+    for k, (c, f, h, n) in enumerate(sides):
+        for _ in range(n):
+            _raise_status(f"register_views (view {k})", host[at:at + B])
+            at += B
+    for c, f, h, n in sides:
+        o = host[at:at + B + 1].astype(np.int64)
+        at += B + 1
+        total = int(o[-1])
+        out.append((Cloud(c.points[:total], c.index[:total], c.offsets, c.count, None), f[:total], h[:total], o))
+    return out
+
+
+def register_views(views, init=None, metric="point", normal_k=16, keys=None, viewpoints=None, global_kw=None, **align_kw):
     """Views (Clouds of B subjects each) into the frame of view 0: view k is aligned to the union of the views 0 .. k - 1 as already placed.
     init: one start pose per view (None, (R, t) or (B,4,4)), or None.  metric="plane": align's point-to-plane steps, the normals computed on the
-    union anew for every view.  -> a list of Alignment, one per view (view 0: the identity)."""
+    union anew for every view.  -> a list of Alignment, one per view (view 0: the identity).
+    init="global"  needs no start pose: the descriptors of every view are computed once in its own frame (global_align's
+    arguments in global_kw, its keys in keys, one sensor position per view in viewpoints, each in its view's frame), view k is matched against the
+    voxelised rows of the views 0 .. k - 1 as placed, with their own descriptors, and then refined against the union exactly as with a given pose.
+    A view without a found pose starts from the identity, its status holds STATUS_GLOBAL_NOT_FOUND; every Alignment but the first carries .start."""
     a = _check_align(**align_kw)
     normal_k = _check_metric(metric, None, normal_k)
     views, offsets = _check_views(views)
+    B = len(offsets[0]) - 1
+    g = None
+    if isinstance(init, str):
+        if init != "global":
+            raise ValueError(f"init must be None, poses or 'global', got {init!r}")
+        if keys is None:
+            raise ValueError("init='global' needs keys")
+        g, init = _check_global(B, keys, **(global_kw or {})), None
+    elif keys is not None or viewpoints is not None or global_kw is not None:
+        raise ValueError("keys, viewpoints and global_kw belong to init='global'")
     if init is not None and len(init) != len(views):
         raise ValueError(f"init must hold one entry per view, got {len(init)} for {len(views)} views")
-    B = len(offsets[0]) - 1
     torch, ops, ctx = _ops(views[0])
     dev = views[0].points.device
     with ctx:
+        sides = _global_views_prepare(torch, ops, views, g, viewpoints) if g is not None else None
+        coarse = [sides[0][0]] if g is not None else None
         eye = torch.eye(3, dtype=torch.float64, device=dev).repeat(B, 1, 1)
         out = [Alignment(eye, torch.zeros((B, 3), dtype=torch.float64, device=dev), np.diff(offsets[0]).astype(np.int32), np.zeros(B),
                          np.zeros(B, np.int32), np.zeros(B, np.int32), None)]
         placed = [views[0]]
         for k in range(1, len(views)):
             R, t = _init_pose(None if init is None else init[k], B, dev)
+            start = None
+            if g is not None:
+                so = [s[3] for s in sides[:k]]
+                seen = _union(torch, coarse, so)
+                src, fs, hs, _ = sides[k]
+                match = _global_match(torch, ops, src, fs, hs, seen, _union_rows(torch, [s[1] for s in sides[:k]], so),
+                                      _union_rows(torch, [s[2] for s in sides[:k]], so), g["mutual"])
+                start = _global_result(torch, [], B, *_global_pose(torch, ops, src, seen, match, g), f"register_views (view {k})")
+                R, t = start.R, start.t
             union = _union(torch, placed, offsets[:k])
             normals = ops.cloud_normals(union.points, union.offsets, normal_k)[0] if metric == "plane" else None
             res = _alignment(torch, _align(torch, ops, views[k], union, a, R, t, False, normals), B, f"register_views (view {k})")
             res.pair = res.pair[:int(offsets[k][-1])]
+            if start is not None:
+                res.status = res.status | np.where(start.found, 0, STATUS_GLOBAL_NOT_FOUND).astype(np.int32)
+                res.start = start
+                c = sides[k][0]
+                coarse.append(Cloud(ops.cloud_transform(c.points, c.offsets, res.R, res.t), c.index, c.offsets, c.count, None))
             out.append(res)
             placed.append(Cloud(ops.cloud_transform(views[k].points, views[k].offsets, res.R, res.t), views[k].index, views[k].offsets, views[k].count, None))
     return out
@@ -695,6 +777,171 @@ def fuse(views, transforms, voxel=None):
     return voxel_downsample(union, voxel)[0] if voxel is not None else union
 
 
+# ---------------------------------------------------------------------------------------------------------------- global registration
+MAX_GLOBAL_HYPOTHESES = 262144
+STATUS_GLOBAL_NOT_FOUND = 16                                       # align(init="global"): no pose was found, the loop started from the identity
+
+
+class GlobalAlignment:
+    """What global_align() returns, per pair of clouds: R (B,3,3), t (B,3) fp64 on the device; found (B) bool, inliers (B) int32 and
+    correspondences (B) int32 numpy.  found False (R = I, t = 0) is a result, not an error."""
+
+    def __init__(self, R, t, found, inliers, correspondences):
+        self.R, self.t, self.found, self.inliers, self.correspondences = R, t, found, inliers, correspondences
+
+
+def _feature_normals(ops, cloud, k, view, normals, grid, brute):
+    """The oriented normals and their flags for the descriptors, on a cell grid built before.  -> normal (M,3) fp64, flag (M) int32 on the device."""
+    import torch
+    if normals is not None:
+        n = _given_normals(normals, cloud.points.shape[0], cloud.points.device)
+        return n, ((n == 0.0).all(1) | ~torch.isfinite(n).all(1)).to(torch.int32) * NORMAL_FLAG_AMBIGUOUS      # a row without a normal has no descriptor
+    out = ops.cloud_normals(cloud.points, cloud.offsets, k, viewpoint=view, brute=brute, grid=grid)
+    return out[0], out[2]
+
+
+def _features(ops, cloud, k, view, normals, cell=None, brute=False):
+    """Normals and descriptors on ONE cell grid: the keys and the two sorts are the same for both."""
+    grid = ops.cloud_cell_grid(cloud.points, cloud.offsets, 0, k, 0.0 if cell is None else float(cell), sort=not brute)
+    normal, flag = _feature_normals(ops, cloud, k, view, normals, grid, brute)
+    return ops.cloud_fpfh(cloud.points, cloud.offsets, normal, flag, k, brute=brute, grid=grid)
+
+
+def _check_feature_source(viewpoint, normals):
+    if viewpoint is None and normals is None:
+        raise ValueError("features need oriented normals: give viewpoint= (the sensor position) or normals=; sign-free normals make no descriptor")
+    if viewpoint is not None and normals is not None:
+        raise ValueError("give viewpoint= or normals=, not both")
+
+
+def features(cloud, k=32, viewpoint=None, normals=None, cell=None, brute=False, return_spfh=False):
+    """FPFH descriptors: 33-bin histograms of the angles between a row's normal and those of its k nearest rows, weighted over
+    the neighbourhood.  The normals come from `viewpoint` ((3,) or one sensor position per cloud) through normals(), or are given as oriented
+    `normals` (M,3); neither raises ValueError.  -> feature (M,33) fp64, has_feature (M) bool on the device (and with return_spfh the pass-1
+    counts spfh (M,33) int32, their number c (M) int32 and the neighbour lists (M,k) int32).  A row has no feature where its normal is flagged, it
+    counted no pair or a block of its histogram is empty.  cell= and brute=True change no bit."""
+    k = _check_normal_k(k)
+    _check_feature_source(viewpoint, normals)
+    if cell is not None:
+        _check_positive(cell, "cell")
+    o = _offsets(cloud)
+    view = _viewpoint(viewpoint, len(o) - 1, cloud.points.device)
+    torch, ops, ctx = _ops(cloud)
+    with ctx:
+        feature, has, spfh, count, nbr, status = _features(ops, cloud, k, view, normals, cell, brute)
+    _raise_status("features", status.cpu().numpy())
+    total = int(o[-1])
+    res = (feature[:total], has[:total].bool())
+    return res + (spfh[:total], count[:total], nbr[:total]) if return_spfh else res
+
+
+def _check_global(B, keys, voxel=0.02, feature_k=32, hypotheses=65536, tau=None, edge_similarity=0.9, min_edge=0.05, min_inliers=6, mutual=False,
+                  refit_steps=2):
+    """global_align's arguments, checked before any launch.  -> a dict."""
+    from . import mesh_io
+    if voxel is not None:
+        voxel = _check_positive(voxel, "voxel")
+    if tau is None:
+        if voxel is None:
+            raise ValueError("tau=None means 1.5 * voxel: with voxel=None give tau")
+        tau = 1.5 * voxel
+    tau = _check_positive(tau, "tau")
+    if int(hypotheses) != hypotheses or not 1 <= int(hypotheses) <= MAX_GLOBAL_HYPOTHESES:
+        raise ValueError(f"hypotheses must be an integer in 1 .. {MAX_GLOBAL_HYPOTHESES}, got {hypotheses}")
+    if not 0.0 < float(edge_similarity) <= 1.0:
+        raise ValueError(f"edge_similarity must lie in (0, 1], got {edge_similarity}")
+    if not (float(min_edge) >= 0.0 and math.isfinite(float(min_edge))):
+        raise ValueError(f"min_edge must be finite and not negative, got {min_edge}")
+    if int(min_inliers) != min_inliers or int(min_inliers) < 0:
+        raise ValueError(f"min_inliers must be a non-negative integer, got {min_inliers}")
+    if int(refit_steps) != refit_steps or int(refit_steps) < 0:
+        raise ValueError(f"refit_steps must be a non-negative integer, got {refit_steps}")
+    return dict(keys=mesh_io._keys(keys, B), voxel=voxel, k=_check_normal_k(feature_k), H=int(hypotheses), tau=tau, e=float(edge_similarity),
+                min_edge=float(min_edge), min_inliers=int(min_inliers), mutual=bool(mutual), refit_steps=int(refit_steps))
+
+
+def _global_views(viewpoint, B, dev):
+    if viewpoint is None or len(viewpoint) != 2:
+        raise ValueError("viewpoint must be (source's, target's) sensor positions: the descriptors need oriented normals")
+    vs, vt = _viewpoint(viewpoint[0], B, dev), _viewpoint(viewpoint[1], B, dev)
+    if vs is None or vt is None:
+        raise ValueError("viewpoint must give a sensor position for the source and for the target")
+    return vs, vt
+
+
+def _global_match(torch, ops, src, fs, hs, tgt, ft, ht, mutual):
+    match, _ = ops.cloud_feature_match(fs, hs, src.offsets, ft, ht, tgt.offsets)
+    if mutual and match.numel() and ft.shape[0]:
+        back, _ = ops.cloud_feature_match(ft, ht, tgt.offsets, fs, hs, src.offsets)
+        rows = torch.arange(match.numel(), device=match.device)
+        B = src.offsets.numel() - 1
+        cloud = torch.bucketize(rows, src.offsets[1:].long().contiguous(), right=True).clamp_(max=B - 1)
+        j = (tgt.offsets.long()[cloud] + match.long()).clamp_(0, ft.shape[0] - 1)
+        agree = (match >= 0) & (back[j].long() == rows - src.offsets.long()[cloud])
+        match = torch.where(agree, match, torch.full_like(match, -1))
+    return match
+
+
+def _global_pose(torch, ops, src, tgt, match, a):
+    """Hypotheses, scores, selection and the refit for given matches.  -> R (B,3,3), t (B,3), found (B) int32, inliers (B) int32,
+    correspondences (B) int32, on the device."""
+    dev = src.points.device
+    cs, ct, crow, coff, _ = ops.cloud_correspondences(src.points, src.offsets, tgt.points, tgt.offsets, match)
+    key = torch.from_numpy(a["keys"]).to(dev)
+    transforms, valid, _ = ops.cloud_global_hypotheses(cs, ct, crow, coff, key, a["H"], a["e"], a["min_edge"])
+    counts = ops.cloud_global_score(cs, ct, coff, transforms, a["tau"], valid=valid)
+    R, t, best, _, found = ops.cloud_global_select(transforms, valid, counts, a["min_inliers"])
+    for _ in range(a["refit_steps"]):
+        pair = ops.cloud_global_inliers(src.points, src.offsets, tgt.points, tgt.offsets, match, R, t, a["tau"])
+        Rn, tn = ops.cloud_align_step(src.points, src.offsets, tgt.points, tgt.offsets, pair, R=R, t=t)[5:7]
+        again = ops.cloud_global_score(cs, ct, coff, torch.cat([Rn.reshape(-1, 1, 9), tn.reshape(-1, 1, 3)], 2).contiguous(), a["tau"])[:, 0]
+        keep = (found != 0) & (again >= best)                                   # the last pose whose count did not fall
+        R, t, best = torch.where(keep[:, None, None], Rn, R), torch.where(keep[:, None], tn, t), torch.where(keep, again, best)
+    return R, t, found, best, coff[1:] - coff[:-1]
+
+
+def _global_side(ops, cloud, a, view, words):
+    """One side of global_align: the voxel grid (where asked for) and the descriptors.  Status words go to `words` for the one readback."""
+    if a["voxel"] is not None:
+        cloud, _, status = _voxel(ops, cloud, a["voxel"])
+        words.append(status)
+    feature, has, _, _, _, status = _features(ops, cloud, a["k"], view, None)
+    words.append(status)
+    return cloud, feature, has
+
+
+def _global_result(torch, words, B, R, t, found, best, ncorr, what):
+    host = torch.cat(words + [found, best, ncorr]).cpu().numpy()                 # the one readback
+    n = len(words)
+    for i in range(n):
+        _raise_status(what, host[i * B:(i + 1) * B])
+    return GlobalAlignment(R, t, host[n * B:(n + 1) * B].astype(bool), host[(n + 1) * B:(n + 2) * B].astype(np.int32), host[(n + 2) * B:].astype(np.int32))
+
+
+def global_align(source, target, keys, voxel=0.02, feature_k=32, viewpoint=None, hypotheses=65536, tau=None, edge_similarity=0.9, min_edge=0.05,
+                 min_inliers=6, mutual=False, refit_steps=2):
+    """A rough pose of every source cloud on its target from nothing: FPFH descriptors (features()) on voxel_downsample of both
+    sides (voxel=None: the clouds as given), the nearest target descriptor of every source row (mutual=True: kept only where the reverse search
+    agrees), `hypotheses` rigid poses from three correspondences drawn under the pair's key (one integer per pair, or one for all) -- a triple is
+    dropped where its edges differ in length by more than edge_similarity or are shorter than min_edge --, each scored by the correspondences it
+    brings within tau (None: 1.5 voxel); the best (a tie: the lowest hypothesis) is refitted refit_steps times to its inliers.  viewpoint = (the
+    source's, the target's) sensor position, each (3,) or (B,3), each in its own cloud's frame: the descriptors need oriented normals.
+    -> GlobalAlignment; found False where fewer than min_inliers correspondences agree.  The result is a start for align(), which converges from
+    about 20 degrees and 10 cm.  ValueError for bad arguments before any launch; one readback."""
+    so, _ = _check_pairs(source, target)
+    B = len(so) - 1
+    a = _check_global(B, keys, voxel, feature_k, hypotheses, tau, edge_similarity, min_edge, min_inliers, mutual, refit_steps)
+    vs, vt = _global_views(viewpoint, B, source.points.device)
+    torch, ops, ctx = _ops(source)
+    with ctx:
+        words = []
+        src, fs, hs = _global_side(ops, source, a, vs, words)
+        tgt, ft, ht = _global_side(ops, target, a, vt, words)
+        match = _global_match(torch, ops, src, fs, hs, tgt, ft, ht, a["mutual"])
+        R, t, found, best, ncorr = _global_pose(torch, ops, src, tgt, match, a)
+        return _global_result(torch, words, B, R, t, found, best, ncorr, "global_align")
+
+
 # ---------------------------------------------------------------------------------------------------------------- the command
 def add_align_flags(p):
     """The flags that register further views onto --cloud_path's frame; without --more_views nothing changes."""
@@ -709,6 +956,13 @@ def add_align_flags(p):
     p.add_argument("--align_normal_k", type=int, default=16, help="registration with --align_metric plane: neighbours per normal (3 .. 32)")
     p.add_argument("--view_init", type=str, default=None, help="an .npz whose array `poses` (V,4,4) holds a start pose for every view of --more_views")
     p.add_argument("--fuse_voxel", type=float, default=0.0, help="fuse the registered views on a voxel grid of V metres; 0 = concatenate")
+    p.add_argument("--align_global", action="store_true", help="registration without start poses: FPFH descriptors, feature matches and RANSAC find a rough "
+                   "pose for every view, which the registration then refines (instead of --view_init)")
+    p.add_argument("--align_global_voxel", type=float, default=0.02, help="--align_global: the voxel size the descriptors are computed on, in metres")
+    p.add_argument("--align_feature_k", type=int, default=32, help="--align_global: neighbours per descriptor (3 .. 32)")
+    p.add_argument("--align_hypotheses", type=int, default=65536, help=f"--align_global: RANSAC hypotheses (1 .. {MAX_GLOBAL_HYPOTHESES})")
+    p.add_argument("--view_origin", type=float, nargs=3, metavar=("X", "Y", "Z"), default=(0.0, 0.0, 0.0), help="--align_global: the camera position in each "
+                   "view's own frame")
 
 
 def check_align_flags(p, a):
@@ -721,6 +975,17 @@ def check_align_flags(p, a):
         p.error("--fuse_voxel must be positive and finite")
     if a.more_views is None and a.view_init is not None:
         p.error("--view_init needs --more_views")
+    if a.align_global:
+        if a.more_views is None:
+            p.error("--align_global needs --more_views")
+        if a.view_init is not None:
+            p.error("--view_init and --align_global exclude each other")
+        try:
+            _check_global(1, [0], voxel=a.align_global_voxel, feature_k=a.align_feature_k, hypotheses=a.align_hypotheses)
+        except ValueError as e:
+            p.error(f"--align_global: {e}")
+        if not all(math.isfinite(x) for x in a.view_origin):
+            p.error("--view_origin must be three finite numbers")
 
 
 def register_files(first, args):
@@ -734,14 +999,25 @@ def register_files(first, args):
             raise ValueError(f"--view_init: poses must be ({len(more)},4,4), got {poses.shape}")
         init = [None] + [poses[k:k + 1] for k in range(len(more))]
     views = [pack([v], args.device) for v in [first] + more]
+    extra = {}
+    if getattr(args, "align_global", False):
+        init = "global"
+        extra = dict(keys=[args.seed], viewpoints=[tuple(args.view_origin)] * len(views),
+                     global_kw=dict(voxel=args.align_global_voxel, feature_k=args.align_feature_k, hypotheses=args.align_hypotheses))
     res = register_views(views, init=init, gate=args.align_gate, gate_min=args.align_gate_min, decay=args.align_decay, iters=args.align_iters,
-                         metric=args.align_metric, normal_k=args.align_normal_k)
+                         metric=args.align_metric, normal_k=args.align_normal_k, **extra)
     fused = fuse(views, res, voxel=args.fuse_voxel if args.fuse_voxel > 0.0 else None)
     pose = np.tile(np.eye(4), (len(views), 1, 1))
     for k, r in enumerate(res):
         pose[k, :3, :3], pose[k, :3, 3] = r.R[0].cpu().numpy(), r.t[0].cpu().numpy()
     report = {"view_pose": pose, "view_matched": np.array([int(r.matched[0]) for r in res]), "view_rms": np.array([float(r.rms[0]) for r in res]),
               "view_steps": np.array([int(r.steps[0]) for r in res]), "view_status": np.array([int(r.status[0]) for r in res]), "view_metric": np.array(args.align_metric)}
+    if extra:                                                        # view 0 fixes the frame: found, no inliers, the identity
+        start = np.tile(np.eye(4), (len(views), 1, 1))
+        for k, r in enumerate(res[1:], 1):
+            start[k, :3, :3], start[k, :3, 3] = r.start.R[0].cpu().numpy(), r.start.t[0].cpu().numpy()
+        report.update(view_global_found=np.array([True] + [bool(r.start.found[0]) for r in res[1:]]),
+                      view_global_inliers=np.array([0] + [int(r.start.inliers[0]) for r in res[1:]]), view_global_pose=start)
     return fused.points.cpu().numpy(), report
 
 

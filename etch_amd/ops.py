@@ -2173,9 +2173,10 @@ def cloud_knn_mean(points, offsets, k, cell=None, brute=False):
     return mean, status
 
 
-def cloud_normals(points, offsets, k, viewpoint=None, cell=None, brute=False, return_cov=False):
+def cloud_normals(points, offsets, k, viewpoint=None, cell=None, brute=False, return_cov=False, grid=None):
     """etch_cloud_normals: the normal of every row from its min(k, n - 1) nearest other rows of its cloud, 3 <= k <= 32, on the
     cell grid of cloud_knn_mean (the same rule for the cell size; `cell` overrides it and changes no bit).  viewpoint (B,3) fp64 or None.
+    grid: what cloud_cell_grid(points, offsets, 0, k, ..) returned for these points, to share one grid between calls (None: built here).
     -> normal (M,3) fp64, variation (M) fp64, flag (M) int32 (zeros for a cloud with a status bit), status (B) int32, and with return_cov the
     covariance (M,6) fp64, all still on the device."""
     B, M = _cloud_args(points, offsets, "cloud_normals")
@@ -2188,7 +2189,7 @@ def cloud_normals(points, offsets, k, viewpoint=None, cell=None, brute=False, re
         if tuple(viewpoint.shape) != (B, 3):
             raise _lib.EtchHipError(f"cloud_normals: viewpoint must be ({B},3), got {tuple(viewpoint.shape)}")
     dev = points.device
-    grid, status, sp, sk, order = cloud_cell_grid(points, offsets, 0, k, 0.0 if cell is None else float(cell), sort=not brute)
+    grid, status, sp, sk, order = cloud_cell_grid(points, offsets, 0, k, 0.0 if cell is None else float(cell), sort=not brute) if grid is None else grid
     normal = torch.zeros((M, 3), dtype=torch.float64, device=dev)
     variation = torch.zeros((M,), dtype=torch.float64, device=dev)
     flag = torch.zeros((M,), dtype=torch.int32, device=dev)
@@ -2540,3 +2541,150 @@ def cloud_transform(points, offsets, R, t):
     out = torch.zeros((M, 3), dtype=torch.float64, device=points.device)
     _lib.call("etch_cloud_transform", int(B), int(M), _some(points), offsets, R, t, _some(out))
     return out
+
+
+# ------------------------------------------------------------------ global registration (csrc/cloud_global.hip)
+GLOBAL_FEATURES = 33
+GLOBAL_MAX_HYPOTHESES = 262144
+
+
+def cloud_fpfh(points, offsets, normal, normal_flag, k, cell=None, brute=False, grid=None):
+    """etch_cloud_fpfh: the FPFH descriptor of every row from its min(k, n - 1) nearest other rows, 3 <= k <= 32, on the cell grid of cloud_normals
+    (`cell` overrides the cell size and changes no bit; brute=True scans every cloud whole).  normal (M,3) fp64: unit normals oriented consistently,
+    normal_flag (M) int32, both by row.  -> feature (M,33) fp64, has_feature (M) int32, spfh (M,33) int32, count (M) int32, neighbours (M,k) int32
+    (rows local to the cloud, -1 behind the last), status (B) int32, all still on the device.  grid: what cloud_cell_grid(points, offsets, 0, k, ..)
+    returned for these points (None: built here); cloud_normals takes the same, so that normals and descriptors share one grid and one sort."""
+    B, M = _cloud_args(points, offsets, "cloud_fpfh")
+    if not 3 <= int(k) <= CLOUD_MAX_K:
+        raise _lib.EtchHipError(f"cloud_fpfh: k must lie in 3 .. {CLOUD_MAX_K}, got {k}")
+    if cell is not None and not (float(cell) > 0.0 and math.isfinite(float(cell))):
+        raise _lib.EtchHipError(f"cloud_fpfh: cell must be positive and finite, got {cell}")
+    _need(normal, torch.float64, "normal"), _need(normal_flag, torch.int32, "normal_flag")
+    if tuple(normal.shape) != (M, 3) or tuple(normal_flag.shape) != (M,):
+        raise _lib.EtchHipError(f"cloud_fpfh: normal must be ({M},3) and normal_flag ({M},), got {tuple(normal.shape)} and {tuple(normal_flag.shape)}")
+    dev = points.device
+    grid, status, sp, sk, order = cloud_cell_grid(points, offsets, 0, k, 0.0 if cell is None else float(cell), sort=not brute) if grid is None else grid
+    feature = torch.zeros((M, GLOBAL_FEATURES), dtype=torch.float64, device=dev)
+    has = torch.zeros((M,), dtype=torch.int32, device=dev)
+    spfh = torch.zeros((M, GLOBAL_FEATURES), dtype=torch.int32, device=dev)
+    count = torch.zeros((M,), dtype=torch.int32, device=dev)
+    nbr = torch.full((M, int(k)), -1, dtype=torch.int32, device=dev)
+    _lib.call("etch_cloud_fpfh", int(B), int(M), int(k), int(bool(brute)), _some(points if brute else sp), sk, order, _some(points), offsets, grid, status,
+              _some(normal), _some(normal_flag), _some(spfh), _some(count), _some(nbr), _some(feature), _some(has))
+    return feature, has, spfh, count, nbr, status
+
+
+def _feature_args(feature, has, offsets, what):
+    _need(feature, torch.float64, "feature"), _need(has, torch.int32, "has_feature"), _need(offsets, torch.int32, "offsets")
+    if feature.dim() != 2 or feature.shape[1] != GLOBAL_FEATURES or tuple(has.shape) != (feature.shape[0],) or offsets.dim() != 1 or offsets.numel() < 2:
+        raise _lib.EtchHipError(f"{what}: feature must be (M,{GLOBAL_FEATURES}), has_feature (M,) and offsets (B+1), got {tuple(feature.shape)}, "
+                                f"{tuple(has.shape)} and {tuple(offsets.shape)}")
+    return offsets.numel() - 1, feature.shape[0]
+
+
+def cloud_feature_match(src_feature, src_has, src_offsets, tgt_feature, tgt_has, tgt_offsets):
+    """etch_cloud_feature_match: for every source row with a feature the row of target cloud b with a feature and the least (D, row).
+    -> match (Ms) int32 (local to the cloud, -1 without one), dist (Ms) fp64 (+inf without one), on the device."""
+    B, Ms = _feature_args(src_feature, src_has, src_offsets, "cloud_feature_match")
+    Bt, _ = _feature_args(tgt_feature, tgt_has, tgt_offsets, "cloud_feature_match")
+    if Bt != B:
+        raise _lib.EtchHipError(f"cloud_feature_match: {B} source clouds but {Bt} target clouds")
+    match = torch.full((Ms,), -1, dtype=torch.int32, device=src_feature.device)
+    dist = torch.full((Ms,), math.inf, dtype=torch.float64, device=src_feature.device)
+    _lib.call("etch_cloud_feature_match", int(B), int(Ms), _some(src_feature), _some(src_has), src_offsets, _some(tgt_feature), _some(tgt_has), tgt_offsets,
+              _some(match), _some(dist))
+    return match, dist
+
+
+def cloud_correspondences(src_points, src_offsets, tgt_points, tgt_offsets, match):
+    """The matched source rows of every pair in ascending row order, compacted on the device (etch_cloud_compact on match >= 0).  -> corr_src (Ms,3)
+    fp64, corr_tgt (Ms,3) fp64, corr_row (Ms) int32 = the matched target row, corr_offsets (B+1) int32, corr_index (Ms) int32 = the source row (both
+    rows local to their cloud); only the first corr_offsets[B] rows mean anything."""
+    B, Ms, Mt = _align_pairs(src_points, src_offsets, tgt_points, tgt_offsets, "cloud_correspondences")
+    _need(match, torch.int32, "match")
+    if tuple(match.shape) != (Ms,):
+        raise _lib.EtchHipError(f"cloud_correspondences: match must be ({Ms},)")
+    dev = src_points.device
+    if Ms == 0 or Mt == 0:
+        z = torch.zeros((Ms, 3), dtype=torch.float64, device=dev)
+        return z, z.clone(), torch.zeros((Ms,), dtype=torch.int32, device=dev), torch.zeros((B + 1,), dtype=torch.int32, device=dev), torch.zeros((Ms,), dtype=torch.int32, device=dev)
+    rows = torch.arange(Ms, dtype=torch.int32, device=dev)
+    _, coff, packed, corr_src = cloud_compact(src_points, rows, src_offsets, (match >= 0).to(torch.int32))
+    g = packed.long().clamp_(0, Ms - 1)                              # behind corr_offsets[B] the compaction wrote nothing: any row in range does
+    cloud = torch.bucketize(g, src_offsets[1:].long().contiguous(), right=True).clamp_(max=B - 1)
+    corr_row = match[g]
+    corr_tgt = tgt_points[(tgt_offsets.long()[cloud] + corr_row.long()).clamp_(0, Mt - 1)].contiguous()
+    return corr_src, corr_tgt, corr_row.contiguous(), coff, (g - src_offsets.long()[cloud]).to(torch.int32)
+
+
+def _corr_args(corr_src, corr_tgt, corr_offsets, what):
+    _need(corr_src, torch.float64, "corr_src"), _need(corr_tgt, torch.float64, "corr_tgt"), _need(corr_offsets, torch.int32, "corr_offsets")
+    if corr_src.dim() != 2 or corr_src.shape[1] != 3 or corr_tgt.shape != corr_src.shape or corr_offsets.dim() != 1 or corr_offsets.numel() < 2:
+        raise _lib.EtchHipError(f"{what}: corr_src and corr_tgt must be (N,3) and corr_offsets (B+1), got {tuple(corr_src.shape)}, {tuple(corr_tgt.shape)} and "
+                                f"{tuple(corr_offsets.shape)}")
+    return corr_offsets.numel() - 1, corr_src.shape[0]
+
+
+def _transform_args(transforms, B, what):
+    _need(transforms, torch.float64, "transforms")
+    if transforms.dim() != 3 or transforms.shape[0] != B or transforms.shape[2] != 12 or not 1 <= transforms.shape[1] <= GLOBAL_MAX_HYPOTHESES:
+        raise _lib.EtchHipError(f"{what}: transforms must be ({B},H,12) with 1 <= H <= {GLOBAL_MAX_HYPOTHESES}, got {tuple(transforms.shape)}")
+    return transforms.shape[1]
+
+
+def cloud_global_hypotheses(corr_src, corr_tgt, corr_row, corr_offsets, keys, hypotheses, edge_similarity=0.9, min_edge=0.05):
+    """etch_cloud_global_hypotheses: keys (B) int64 holding the uint64 bits.  -> transforms (B,H,12) fp64 = R row-major and t, valid (B,H) int32,
+    triples (B,H,3) int32 = the three correspondences drawn, all still on the device."""
+    B, N = _corr_args(corr_src, corr_tgt, corr_offsets, "cloud_global_hypotheses")
+    _need(corr_row, torch.int32, "corr_row"), _need(keys, torch.int64, "keys")
+    H = int(hypotheses)
+    if tuple(corr_row.shape) != (N,) or tuple(keys.shape) != (B,) or not 1 <= H <= GLOBAL_MAX_HYPOTHESES:
+        raise _lib.EtchHipError(f"cloud_global_hypotheses: corr_row must be ({N},), keys ({B},) and 1 <= hypotheses <= {GLOBAL_MAX_HYPOTHESES}")
+    if not 0.0 < float(edge_similarity) <= 1.0 or not (float(min_edge) >= 0.0 and math.isfinite(float(min_edge))):
+        raise _lib.EtchHipError("cloud_global_hypotheses: edge_similarity must lie in (0, 1] and min_edge be finite and not negative")
+    dev = corr_src.device
+    transforms = torch.empty((B, H, 12), dtype=torch.float64, device=dev)
+    valid = torch.empty((B, H), dtype=torch.int32, device=dev)
+    triples = torch.empty((B, H, 3), dtype=torch.int32, device=dev)
+    _lib.call("etch_cloud_global_hypotheses", int(B), H, _some(corr_src), _some(corr_tgt), _some(corr_row), corr_offsets, keys, float(edge_similarity),
+              float(min_edge), transforms, valid, triples)
+    return transforms, valid, triples
+
+
+def cloud_global_score(corr_src, corr_tgt, corr_offsets, transforms, tau, valid=None):
+    """etch_cloud_global_score for ANY transforms (B,H,12): -> inliers (B,H) int32; valid (B,H) int32 or None."""
+    B, N = _corr_args(corr_src, corr_tgt, corr_offsets, "cloud_global_score")
+    H, tau = _transform_args(transforms, B, "cloud_global_score"), _check_tau(tau, "cloud_global_score")
+    if valid is not None and tuple(_need(valid, torch.int32, "valid").shape) != (B, H):
+        raise _lib.EtchHipError(f"cloud_global_score: valid must be ({B},{H})")
+    inliers = torch.empty((B, H), dtype=torch.int32, device=corr_src.device)
+    _lib.call("etch_cloud_global_score", int(B), int(N), int(H), tau, _some(corr_src), _some(corr_tgt), corr_offsets, transforms, valid, inliers)
+    return inliers
+
+
+def cloud_global_select(transforms, valid, inliers, min_inliers=6):
+    """etch_cloud_global_select: -> R (B,3,3), t (B,3) fp64, best (B) int32 = the winner's inliers, best_h (B) int32, found (B) int32."""
+    _need(valid, torch.int32, "valid"), _need(inliers, torch.int32, "inliers")
+    B = transforms.shape[0] if transforms.dim() == 3 else 0
+    H = _transform_args(transforms, B, "cloud_global_select")
+    if B < 1 or tuple(valid.shape) != (B, H) or tuple(inliers.shape) != (B, H):
+        raise _lib.EtchHipError(f"cloud_global_select: valid and inliers must be ({B},{H}) with B >= 1")
+    dev = transforms.device
+    R = torch.empty((B, 3, 3), dtype=torch.float64, device=dev)
+    t = torch.empty((B, 3), dtype=torch.float64, device=dev)
+    best, best_h, found = (torch.empty((B,), dtype=torch.int32, device=dev) for _ in range(3))
+    _lib.call("etch_cloud_global_select", int(B), int(H), int(min_inliers), transforms, valid, inliers, R, t, best, best_h, found)
+    return R, t, best, best_h, found
+
+
+def cloud_global_inliers(src_points, src_offsets, tgt_points, tgt_offsets, match, R, t, tau):
+    """etch_cloud_global_inliers: pair (Ms) int32 = match where the moved source row lies within tau of its matched target row, else -1."""
+    B, Ms, Mt = _align_pairs(src_points, src_offsets, tgt_points, tgt_offsets, "cloud_global_inliers")
+    _need(match, torch.int32, "match")
+    if tuple(match.shape) != (Ms,):
+        raise _lib.EtchHipError(f"cloud_global_inliers: match must be ({Ms},)")
+    R, t = _align_transform(R, t, B, src_points.device, "cloud_global_inliers")
+    pair = torch.full((Ms,), -1, dtype=torch.int32, device=src_points.device)
+    _lib.call("etch_cloud_global_inliers", int(B), int(Ms), _check_tau(tau, "cloud_global_inliers"), _some(src_points), src_offsets, _some(tgt_points), tgt_offsets,
+              _some(match), R, t, _some(pair))
+    return pair

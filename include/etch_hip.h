@@ -1185,6 +1185,61 @@ int etch_cloud_align_plane(int B, int Ms, int iters, int brute, const double* sr
                            double* R, double* t, double* sums, int* matched, double* rms, double* dR, double* dt, int* status, int* done, int* steps,
                            int* pair, double* d2, void* stream);
 
+/* ---- raw point clouds: global registration -- FPFH descriptors, feature matches, RANSAC over triples (csrc/cloud_global.hip,
+ * csrc/cloud_global_solve.h) ---------------------------------------------------------------------------------------------- */
+
+#define ETCH_GLOBAL_BINS 11              /* bins per feature */
+#define ETCH_GLOBAL_FEATURES 33          /* a descriptor: the blocks theta, alpha, phi of ETCH_GLOBAL_BINS bins each */
+#define ETCH_GLOBAL_MAX_H 262144         /* the most hypotheses per pair */
+/* Descriptors.  Inputs as etch_cloud_normals takes them (the mode 0 keys, sorted; exact for any cell size; brute != 0: every query scans its whole
+ * cloud, sorted_points is then the unsorted points and sorted_keys, order, grid may be NULL), and points (M,3) UNSORTED, normal (M,3) fp64 unit
+ * normals ORIENTED consistently (etch_cloud_normals with a viewpoint) and normal_flag (M) int32, both by original row.  3 <= k <= ETCH_CLOUD_MAX_K.
+ * The neighbourhood of row i is etch_cloud_normals': the ke = min(k, n - 1) least (d2, row) pairs among the other rows of its cloud.
+ * neighbours (M,k) int32 = those rows in ascending (d2, row) order, local to the cloud, -1 behind the ke-th.
+ * Pass 1.  A pair (i, j), j in the list of i, is counted when both normal flags are 0, d2 > 0 and, with d = (q_j - p_i) / sqrt(d2) per component,
+ * a_i = ((n_ix d_x + n_iy d_y) + n_iz d_z) and a_j likewise: the source s is i where |a_i| >= |a_j|, else j with d negated; u = n_s, t = the other
+ * normal; c = d x u (each component a difference of two rounded products); cl2 = (c_x c_x + c_y c_y) + c_z c_z > 0 (else the pair is not counted);
+ * v = c / sqrt(cl2); w = u x v; theta = atan2(w.t, u.t), alpha = v.t, phi = u.d, every dot ((x + y) + z).  Bins: floor((11 (theta + pi)) / (2 pi)),
+ * floor((11 (alpha + 1)) / 2), floor((11 (phi + 1)) / 2), pi = the nearest double, each clamped to 0 .. 10.  spfh (M,33) int32 = the counts per
+ * bin in the order theta, alpha, phi; count (M) int32 = c_i, the pairs counted.  All of it is one rounding per operation except atan2, whose last
+ * bit belongs to the math library: a theta within rounding of a bin edge may fall on either side.
+ * Pass 2.  F_i[f] = sum_j (1 / d2_ij) ((100 spfh_j[f]) / c_j) over the list of i in its order, sequentially from 0, skipping c_j = 0 and d2 = 0;
+ * then per block s = the sequential sum of its 11 entries and F[f] <- (100 F[f]) / s where s > 0, else 0.  feature (M,33) fp64; has_feature (M)
+ * int32 = 0 where the row's normal is flagged, c_i = 0 or a block sum is not positive.  Rows of a cloud with ETCH_CLOUD_STATUS_NONFINITE are not
+ * written. */
+int etch_cloud_fpfh(int B, int M, int k, int brute, const double* sorted_points, const long long* sorted_keys, const int* order, const double* points,
+                    const int* offsets, const double* grid, const int* status, const double* normal, const int* normal_flag, int* spfh, int* count,
+                    int* neighbours, double* feature, int* has_feature, void* stream);
+/* For source row i of pair b with src_has != 0: among the rows j of target cloud b with tgt_has != 0 the one with the least (D, row),
+ * D = sum_f (a_f - b_f)^2 summed sequentially over f = 0 .. 32 from 0 (the product rounded once): match (Ms) int32 = that row local to its cloud,
+ * dist (Ms) fp64 = D; -1 and +inf where the row has no feature or the target none. */
+int etch_cloud_feature_match(int B, int Ms, const double* src_feature, const int* src_has, const int* src_offsets, const double* tgt_feature,
+                             const int* tgt_has, const int* tgt_offsets, int* match, double* dist, void* stream);
+/* The correspondences of pair b are its matched source rows in ascending row order: corr_offsets (B+1) int32, corr_src (N,3) fp64 the source
+ * points, corr_tgt (N,3) the matched target points, corr_row (N) int32 the matched target rows.  Hypothesis h of a pair with n_c correspondences and
+ * key K, 1 <= H <= ETCH_GLOBAL_MAX_H: Philox4x32-10 with counter (h, 2, 0, 0) and key (low32 K, high32 K) -> r0..r3, i_a = (r_a n_c) >> 32 (a = 0,
+ * 1, 2), written to triples (B,H,3) int32.  Invalid (valid 0, the identity written): n_c < 3; two equal i_a; two equal target rows; an edge (0,1),
+ * (1,2) or (2,0) that fails ls2 >= e2 lt2 and lt2 >= e2 ls2 and ls2 >= m2, with ls2, lt2 = ((dx dx + dy dy) + dz dz) on the source and the target
+ * side, e2 = edge_similarity edge_similarity, m2 = min_edge min_edge; or a degenerate solve.  The solve is etch_cloud_align_step's on the three pairs:
+ * c = 0.5 (min + max) of the target triple per component, the 16 sums of x' = a - c, q' = b - c taken in the order a = 0, 1, 2, Horn's quaternion.
+ * transforms (B,H,12) fp64 = R row-major, then t. */
+int etch_cloud_global_hypotheses(int B, int H, const double* corr_src, const double* corr_tgt, const int* corr_row, const int* corr_offsets,
+                                 const unsigned long long* keys, double edge_similarity, double min_edge, double* transforms, int* valid, int* triples,
+                                 void* stream);
+/* inliers (B,H) int32 = the correspondences c of pair b with ((dx dx + dy dy) + dz dz) <= tau tau (the product rounded once), d = R a_c + t - b_c and
+ * the transform applied as etch_cloud_align_grid states it, for ANY transforms (B,H,12); a hypothesis whose valid flag is 0 scores 0 (valid may be
+ * NULL: every one counts).  inliers is zeroed by the call and filled with integer atomics. */
+int etch_cloud_global_score(int B, int N, int H, double tau, const double* corr_src, const double* corr_tgt, const int* corr_offsets,
+                            const double* transforms, const int* valid, int* inliers, void* stream);
+/* The valid hypothesis with the most inliers per pair, a tie to the lowest h: R (B,9), t (B,3), best (B) int32 its inliers, best_h (B) int32 = h,
+ * found (B) int32.  found = 0, the identity, best = 0 and best_h = -1 where no hypothesis is valid or inliers < min_inliers. */
+int etch_cloud_global_select(int B, int H, int min_inliers, const double* transforms, const int* valid, const int* inliers, double* R, double* t, int* best,
+                             int* best_h, int* found, void* stream);
+/* pair (Ms) int32 = match[i] where match[i] >= 0 and source row i, moved by its pair's R, t, lies within tau of its matched target row (the test of
+ * etch_cloud_global_score), else -1: the pairs etch_cloud_align_step refits on. */
+int etch_cloud_global_inliers(int B, int Ms, double tau, const double* src_points, const int* src_offsets, const double* tgt_points, const int* tgt_offsets,
+                              const int* match, const double* R, const double* t, int* pair, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
