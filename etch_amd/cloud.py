@@ -25,7 +25,15 @@ handing it to the pipeline.
     features(cloud, k=32, viewpoint=), global_align(source, target, keys, viewpoint=(vs, vt), ...)   FPFH descriptors; a rough pose from nothing by
                                                                feature matches and RANSAC, the start of align(init="global") (section 25)
 
-Neighbours are rows of the same cloud only.  The kernels (csrc/cloud_filter.hip, csrc/cloud_isolate.hip, csrc/cloud_align.hip, csrc/cloud_normals.hip, csrc/cloud_global.hip) are exact and defined in fp64; there is no CPU path."""
+    areas(cloud, k=8), orient_normals(cloud, normals, sensors), surface(cloud, sensors=, normals=) -> OrientedCloud   a cloud with an inside (section 26):
+                                                               what etch_amd.containment and fit_surface(scan=) take in place of a mesh
+    fuse(views, transforms, voxel=, return_view=True)          also the view every fused row came from
+
+    python -m etch_amd.cloud ... --surface_refine [--surface_iters I ..] [--surface_contain --contain_w W --contain_every K --contain_normal_k K --contain_area_k K]
+                             the dense surface refinement (section 17) on the cleaned cloud's fit, with --surface_contain kept inside the cleaned cloud:
+                             several views (their sensors: --view_origin through the registration) or one file that carries normals
+
+Neighbours are rows of the same cloud only.  The kernels (csrc/cloud_filter.hip, csrc/cloud_isolate.hip, csrc/cloud_align.hip, csrc/cloud_normals.hip, csrc/cloud_global.hip) are exact and defined in fp64, the sweep of csrc/cloud_winding.hip in fp32 to the bit; there is no CPU path."""
 import argparse
 import math
 import os
@@ -761,9 +769,10 @@ def register_views(views, init=None, metric="point", normal_k=16, keys=None, vie
     return out
 
 
-def fuse(views, transforms, voxel=None):
+def fuse(views, transforms, voxel=None, return_view=False):
     """The views, each moved by its transform (an Alignment or (R, t)), concatenated into one cloud per subject; with voxel, voxel_downsample of
-    that, so that a surface several views saw is present once.  -> Cloud."""
+    that, so that a surface several views saw is present once.  -> Cloud; with return_view also view (M) int32 on the device = the view every
+    output row came from -- under voxel the view of the cell's lowest row, the row Cloud.index names."""
     views, offsets = _check_views(views)
     transforms = list(transforms)
     if len(transforms) != len(views):
@@ -774,7 +783,151 @@ def fuse(views, transforms, voxel=None):
     moved = [transform(v, *((T.R, T.t) if isinstance(T, Alignment) else T)) for v, T in zip(views, transforms)]
     with ctx:
         union = _union(torch, moved, offsets)
-    return voxel_downsample(union, voxel)[0] if voxel is not None else union
+        ids = _view_ids(torch, offsets, union.points.device) if return_view else None
+    if voxel is None:
+        return (union, ids) if return_view else union
+    out = voxel_downsample(union, voxel)[0]
+    if not return_view:
+        return out
+    with ctx:
+        return out, _lowest_view(torch, ids, union.offsets, out.index, out.offsets)
+
+
+def _view_ids(torch, offsets, dev):
+    """The view of every row of _union(views, offsets) (host offsets, one array per view): (M) int32 on dev."""
+    return _union_rows(torch, [torch.full((int(o[-1]),), k, dtype=torch.int32, device=dev) for k, o in enumerate(offsets)], offsets)
+
+
+def _lowest_view(torch, ids, union_offsets, index, out_offsets):
+    """Under a voxel grid: ids at the cell's lowest row.  index (rows) = that row, local to its cloud of the union; both offsets on the device."""
+    rows = torch.arange(index.shape[0], device=index.device)
+    b = (torch.searchsorted(out_offsets.long(), rows, right=True) - 1).clamp_(0, out_offsets.numel() - 2)
+    return ids[index.long() + union_offsets.long()[b]]
+
+
+# ---------------------------------------------------------------------------------------------------------------- oriented clouds: inside and outside
+AREA_MIN_K = 3
+
+
+class OrientedCloud:
+    """A cloud that knows its inside: per row pos (M,3) = the position, moment (M,3) = area x oriented unit normal and cap (M)
+    = area / pi, all fp32 on the device, with offsets (B+1) int32 and max_rows = the largest cloud's rows on the host.  What surface() returns and
+    etch_amd.containment takes in place of a mesh."""
+
+    def __init__(self, pos, moment, cap, offsets, max_rows):
+        self.pos, self.moment, self.cap, self.offsets, self.max_rows = pos, moment, cap, offsets, int(max_rows)
+
+
+def _check_area_k(k):
+    if int(k) != k or not AREA_MIN_K <= int(k) <= MAX_K:
+        raise ValueError(f"k must be an integer in {AREA_MIN_K} .. {MAX_K}, got {k}")
+    return int(k)
+
+
+def _ke(torch, o, k, dev):
+    """min(k, n - 1) of every row's cloud as (M) fp64 on the device, from the host offsets."""
+    n = np.diff(o)
+    ke = np.repeat(np.minimum(k, n - 1), n).astype(np.float64)
+    return torch.from_numpy(ke).to(dev)
+
+
+def areas(cloud, k=8, cell=None, brute=False):
+    """The area every row stands for: a_i = (pi d2k_i) / ke with d2k_i the squared distance to the ke-th nearest other row of its
+    cloud, ke = min(k, n - 1), 3 <= k <= 32 -- the disc to the k-th neighbour holds k rows, so a row of a surface sampled at density rho gets 1 / rho,
+    and half of it where two views overlap.  -> (M) fp64 on the device; 0 for a cloud of one row.  cell= and brute=True change no bit.  ValueError
+    for bad arguments before any launch; EtchHipError naming the cloud that holds a non-finite coordinate."""
+    k = _check_area_k(k)
+    if cell is not None:
+        _check_positive(cell, "cell")
+    o = _offsets(cloud)
+    torch, ops, ctx = _ops(cloud)
+    total = int(o[-1])
+    with ctx:
+        d2k, status = ops.cloud_knn_kth(cloud.points, cloud.offsets, k, cell=cell, brute=brute)
+        ke = _ke(torch, o, k, cloud.points.device)
+        a = torch.where(ke > 0, (math.pi * d2k[:total]) / ke.clamp(min=1.0), torch.zeros_like(ke))
+    _raise_status("areas", status.cpu().numpy())
+    return a
+
+
+def _sensors(sensors, o, dev):
+    """sensors: one position (3,), one per cloud (B,3) or one per row (M,3) -> (M,3) fp64 on the device; ValueError for any other shape."""
+    import torch
+    B, M = len(o) - 1, int(o[-1])
+    if isinstance(sensors, torch.Tensor) and sensors.is_cuda and tuple(sensors.shape) == (M, 3) and sensors.dtype.is_floating_point:
+        return sensors.to(device=dev, dtype=torch.float64).contiguous()       # per-row device tensors stay there: no look at their values
+    s = sensors.detach().cpu().numpy() if isinstance(sensors, torch.Tensor) else np.asarray(sensors)
+    if s.dtype.kind not in "fiu" or s.shape not in ((3,), (B, 3), (M, 3)):
+        raise ValueError(f"sensors must be (3,), ({B},3) or ({M},3) numbers, got {s.dtype} {s.shape}")
+    s = s.astype(np.float64)
+    if not np.isfinite(s).all():
+        raise ValueError("sensors must be finite")
+    if s.shape == (3,):
+        s = np.broadcast_to(s, (B, 3))
+    if s.shape != (M, 3):
+        s = np.repeat(s, np.diff(o), axis=0)
+    return torch.from_numpy(np.ascontiguousarray(s)).to(dev)
+
+
+def orient_normals(cloud, normals, sensors):
+    """Normals turned towards the sensor that saw their row: n is flipped where ((n_x w_x + n_y w_y) + n_z w_z) < 0 with w = sensor - p, section
+    24's rule.  sensors: (3,), one position per cloud (B,3), or one per row (M,3) -- a fused cloud, whose rows several sensors saw.  A row without
+    a normal, (0, 0, 0), stays so.  Nothing is propagated from row to row.  -> (M,3) fp64 on the device."""
+    o = _offsets(cloud)
+    M = int(o[-1])
+    dev = cloud.points.device
+    n = _given_normals(normals, M, dev)
+    s = _sensors(sensors, o, dev)
+    import torch
+    w = s - cloud.points[:M]                                         # plain torch: runs wherever the cloud is
+    dot = (n[:, 0] * w[:, 0] + n[:, 1] * w[:, 1]) + n[:, 2] * w[:, 2]
+    return torch.where((dot < 0.0)[:, None], -n, n)                  # a flagged row's (0, 0, 0) has dot 0 and stays
+
+
+def surface(cloud, sensors=None, normals=None, normal_k=16, area_k=8, center=None):
+    """A cloud with an inside -> OrientedCloud, what etch_amd.containment and fit_surface(scan=) take in place of a mesh.
+    The normals are normals(cloud, normal_k) turned towards `sensors` (orient_normals: one position, one per cloud, or one per row for a fused
+    cloud), or are given, already oriented, as normals= (M,3) -- a file's own (mesh_io.read_cloud(path, return_normals=True)) for example; a row
+    whose normal is (0, 0, 0) or not finite counts as flagged.  Exactly one of the two is needed, ValueError otherwise: there is NO orientation
+    propagation, so a cloud with neither sensor positions nor normals is out of scope.  Each row stands for the area areas(cloud, area_k); a
+    flagged row gets none and adds nothing to a winding number.  center (B,3) is subtracted from the positions in fp64 before the rounding to
+    fp32: give the centre of the frame the queries are in.  ValueError for every argument out of range, before any launch; EtchHipError naming the
+    cloud that holds a non-finite coordinate."""
+    if (sensors is None) == (normals is None):
+        raise ValueError("surface needs sensors= (the sensor positions, to orient computed normals) or normals= (already oriented), and not both")
+    area_k = _check_area_k(area_k)
+    if sensors is not None:
+        normal_k = _check_normal_k(normal_k)
+    o = _offsets(cloud)
+    B, M = len(o) - 1, int(o[-1])
+    dev = cloud.points.device
+    import torch
+    if sensors is not None:
+        sensors = _sensors(sensors, o, dev)
+    else:
+        normals = _given_normals(normals, M, dev)
+    c = None
+    if center is not None:
+        cc = center.detach().cpu().numpy() if isinstance(center, torch.Tensor) else np.asarray(center)
+        if cc.dtype.kind not in "fiu" or cc.shape not in ((3,), (B, 3)) or not np.isfinite(cc.astype(np.float64)).all():
+            raise ValueError(f"center must be (3,) or ({B},3) finite numbers, got {cc.dtype} {cc.shape}")
+        c = torch.from_numpy(np.array(np.broadcast_to(cc.astype(np.float64), (B, 3)), order="C")).to(dev)
+    torch, ops, ctx = _ops(cloud)
+    pts = cloud.points[:M].contiguous()
+    with ctx:
+        if normals is None:
+            n, _, flag, status = ops.cloud_normals(pts, cloud.offsets, normal_k)
+            w = sensors - pts
+            dot = (n[:, 0] * w[:, 0] + n[:, 1] * w[:, 1]) + n[:, 2] * w[:, 2]
+            n = torch.where((dot < 0.0)[:, None], -n, n)
+        else:
+            n = normals
+            flag = ((n == 0.0).all(1) | ~torch.isfinite(n).all(1)).to(torch.int32) * NORMAL_FLAG_AMBIGUOUS
+            n = torch.where((flag != 0)[:, None], torch.zeros_like(n), n)
+        d2k, status = ops.cloud_knn_kth(pts, cloud.offsets, area_k)
+        pos, moment, cap = ops.cloud_surface_pack(pts, cloud.offsets, n.contiguous(), flag.contiguous(), d2k, area_k, center=c)
+    _raise_status("surface", status.cpu().numpy())
+    return OrientedCloud(pos, moment, cap, cloud.offsets, int(np.diff(o).max()))
 
 
 # ---------------------------------------------------------------------------------------------------------------- global registration
@@ -988,8 +1141,9 @@ def check_align_flags(p, a):
             p.error("--view_origin must be three finite numbers")
 
 
-def register_files(first, args):
-    """The command's registration stage: --more_views read, registered onto `first` ((n,3) numpy) and fused.  -> the fused (n,3) numpy, the report."""
+def register_files(first, args, return_view=False):
+    """The command's registration stage: --more_views read, registered onto `first` ((n,3) numpy) and fused.  -> the fused (n,3) numpy, the report,
+    and with return_view the view (n) int32 numpy of every fused row (fuse(return_view=True))."""
     from . import mesh_io
     more = [mesh_io.read_cloud(f) for f in args.more_views]
     init = None
@@ -1006,7 +1160,8 @@ def register_files(first, args):
                      global_kw=dict(voxel=args.align_global_voxel, feature_k=args.align_feature_k, hypotheses=args.align_hypotheses))
     res = register_views(views, init=init, gate=args.align_gate, gate_min=args.align_gate_min, decay=args.align_decay, iters=args.align_iters,
                          metric=args.align_metric, normal_k=args.align_normal_k, **extra)
-    fused = fuse(views, res, voxel=args.fuse_voxel if args.fuse_voxel > 0.0 else None)
+    fused, view = fuse(views, res, voxel=args.fuse_voxel if args.fuse_voxel > 0.0 else None, return_view=True) if return_view else \
+        (fuse(views, res, voxel=args.fuse_voxel if args.fuse_voxel > 0.0 else None), None)
     pose = np.tile(np.eye(4), (len(views), 1, 1))
     for k, r in enumerate(res):
         pose[k, :3, :3], pose[k, :3, 3] = r.R[0].cpu().numpy(), r.t[0].cpu().numpy()
@@ -1018,7 +1173,31 @@ def register_files(first, args):
             start[k, :3, :3], start[k, :3, 3] = r.start.R[0].cpu().numpy(), r.start.t[0].cpu().numpy()
         report.update(view_global_found=np.array([True] + [bool(r.start.found[0]) for r in res[1:]]),
                       view_global_inliers=np.array([0] + [int(r.start.inliers[0]) for r in res[1:]]), view_global_pose=start)
+    if return_view:
+        return fused.points.cpu().numpy(), report, view.cpu().numpy()
     return fused.points.cpu().numpy(), report
+
+
+def source_rows(clean, voxel):
+    """The row of prepare()'s INPUT behind every row of its cleaned cloud, (rows) int64 on the device: the kept rows in order, and under a voxel grid
+    the kept row that is its cell's lowest (Cloud.index).  One cloud."""
+    import torch
+    kept = torch.nonzero(clean.keep, as_tuple=False)[:, 0]
+    return kept[clean.index.long()] if voxel else kept
+
+
+def contain_cloud(args, clean, center, raw_normals, view, poses):
+    """--surface_contain: the cleaned cloud as an OrientedCloud in the centred frame.  Several views: the normals are computed and turned towards the
+    sensor of the view each row came from, R_k o + t_k with o = --view_origin.  One view: the file's own normals, row by row."""
+    import torch
+    src = source_rows(clean, args.voxel > 0.0)
+    if view is not None:
+        o = np.asarray(args.view_origin, np.float64)
+        sensor = np.einsum("kij,j->ki", poses[:, :3, :3], o) + poses[:, :3, 3]
+        per_row = torch.from_numpy(sensor).to(clean.points.device)[torch.from_numpy(view).to(clean.points.device).long()[src]]
+        return surface(clean, sensors=per_row, normal_k=args.contain_normal_k, area_k=args.contain_area_k, center=center)
+    normals = torch.from_numpy(np.ascontiguousarray(raw_normals, np.float64)).to(clean.points.device)[src]
+    return surface(clean, normals=normals, area_k=args.contain_area_k, center=center)
 
 
 def add_filter_flags(p):
@@ -1085,7 +1264,7 @@ def isolate_report(clean):
 
 
 def build_parser():
-    from .inference_demo import add_flags
+    from .inference_demo import add_flags, add_surface_refine_flags
     p = argparse.ArgumentParser(prog="python -m etch_amd.cloud", description="Fit SMPL to a raw point cloud", conflict_handler="resolve")
     p.add_argument("--cloud_path", type=str, required=True, help="the cloud: .ply, .obj (vertices), .npy / .npz ((M,3)), .xyz / .txt (three columns)")
     p.add_argument("--voxel", type=float, default=0.0, help="voxel-grid down-sampling before the pick: the cell size in metres; 0 = off")
@@ -1095,6 +1274,9 @@ def build_parser():
     add_flags(p)
     p.add_argument("--chamfer_refine", type=str, nargs="?", const="partial", default="none", choices=["none", "both", "partial", "clutter"],
                    help="refine the body against the whole cleaned cloud after the marker fit; without a value: partial")
+    add_surface_refine_flags(p)
+    p.add_argument("--contain_normal_k", type=int, default=16, help="--surface_contain: neighbours per normal of the cleaned cloud (3 .. 32)")
+    p.add_argument("--contain_area_k", type=int, default=8, help="--surface_contain: neighbours per area of the cleaned cloud (3 .. 32)")
     return p
 
 
@@ -1108,6 +1290,12 @@ def parse_args(argv=None):
         p.error("--voxel must be positive and finite")
     if a.num_point < 1:
         p.error("--num_point must be at least 1")
+    from .inference_demo import surface_contain_settings, surface_refine_settings
+    surface_refine_settings(a, p)
+    if surface_contain_settings(a, p) is not None:
+        for k in (a.contain_normal_k, a.contain_area_k):
+            if not AREA_MIN_K <= k <= MAX_K:
+                p.error(f"--contain_normal_k and --contain_area_k must lie in {AREA_MIN_K} .. {MAX_K}")
     return a
 
 
@@ -1116,23 +1304,39 @@ def main(argv=None):
     from . import mesh_io
     from .models.fit_SMPL import Mesh
     args = parse_args(argv)
-    raw = mesh_io.read_cloud(args.cloud_path)                         # a malformed file raises before the model is loaded
+    raw, raw_normals = mesh_io.read_cloud(args.cloud_path, return_normals=True)     # a malformed file raises before the model is loaded
+    contain = getattr(args, "surface_contain", False)
+    if contain and not args.more_views and raw_normals is None:
+        build_parser().error("--surface_contain: a single view is half a shell and has no inside; give --more_views, or a file that carries normals")
     model = demo.prepare_common(args)
     export = Mesh.export
     if getattr(args, "ingest", "host") == "device":
         export = mesh_io.write_obj
     stat, radius = filter_args(args)
     floor, cluster = isolate_args(args)
-    views = {}
+    views, view = {}, None
     if args.more_views:                                               # the views enter as one cloud, ahead of every cleaning stage
-        raw, views = register_files(raw, args)
+        if contain:
+            raw, views, view = register_files(raw, args, return_view=True)
+        else:
+            raw, views = register_files(raw, args)
     p32, c, clean = prepare(pack([raw], args.device), args.num_point, [args.seed], voxel=args.voxel if args.voxel > 0.0 else None, stat=stat, radius=radius,
                             floor=floor, cluster=cluster)
     points, center, cleaned = p32[0].cpu().numpy(), c[0].cpu().numpy(), clean.points.cpu().numpy()
     name = os.path.splitext(os.path.basename(args.cloud_path))[0]
     stages = {f"rows_{k}": v for k, v in clean.stages.items()}
-    np.savez(os.path.join(args.output_folder, f"{name}_cloud.npz"), keep=clean.keep.cpu().numpy(), center=center, points=points,
-             removed=np.int64(len(raw) - int(clean.keep.sum())), rows_output=np.array([len(cleaned)]), **stages, **isolate_report(clean), **views)
+    report = dict(keep=clean.keep.cpu().numpy(), center=center, points=points, removed=np.int64(len(raw) - int(clean.keep.sum())),
+                  rows_output=np.array([len(cleaned)]), **stages, **isolate_report(clean), **views)
+    if getattr(args, "surface_refine", False):                        # the fit comes first: the report holds the containment figures
+        scan = contain_cloud(args, clean, center, raw_normals, view, views.get("view_pose")) if contain else Mesh(cleaned - center, np.zeros((0, 3), np.int64))
+        found = {}
+        demo._refine_and_save(args, model, points, scan, center, name, export, report=found)
+        for when in ("before", "after"):
+            report.update({f"contain_{when}_{k}": np.float64(v) for k, v in found.get("contain_" + when, {}).items()})
+        np.savez(os.path.join(args.output_folder, f"{name}_cloud.npz"), **report)
+        print(f"Predicted SMPL mesh, smpl info and the cleaning report saved under {args.output_folder}")
+        return
+    np.savez(os.path.join(args.output_folder, f"{name}_cloud.npz"), **report)
     if args.chamfer_refine != "none":
         demo._refine_and_save(args, model, points, Mesh(cleaned - center, np.zeros((0, 3), np.int64)), center, name, export)
     else:

@@ -7,7 +7,12 @@ scan whose faces are wound inward (w = -1 inside) read the same as one wound out
 it everywhere): it has no inside, and the commands refuse the combination.
 
 Every function takes the scans as a list of Mesh (vertices, faces; packed and sent to the device here) or as the tuple pack_scans returns,
-already on the device, and the queries in the frame of the scans' vertices."""
+already on the device, and the queries in the frame of the scans' vertices.
+
+A scan that is a CLOUD comes as the cloud.OrientedCloud that cloud.surface builds -- positions, oriented normals and areas --
+wherever a mesh is accepted.  Its winding number is the dipole sum of Barill et al. (2018) over the rows, the same |w| >= 0.5 convention
+holds, and "the surface" is the nearest ROW: a distance to it overestimates the distance to the sampled surface by up to the sampling
+distance, and a body pulled to it ends within one sampling distance of the surface."""
 import numpy as np
 import torch
 
@@ -32,6 +37,10 @@ def _scans(meshes, device):
     return pack_scans(list(meshes), device)
 
 
+def _is_cloud(scans):
+    return all(hasattr(scans, a) for a in ("pos", "moment", "cap", "offsets", "max_rows"))
+
+
 def _points(queries, device=None):
     q = torch.as_tensor(queries)
     q = q.to(device=device if device is not None else (q.device if q.is_cuda else "cuda"), dtype=torch.float32).contiguous()
@@ -43,15 +52,21 @@ def _points(queries, device=None):
 
 
 def winding_number(meshes, queries, lengths=None):
-    """w (B,Q) fp32 of scan b at queries (B,Q,3); lengths (B,) for ragged query sets (padding gets 0)."""
-    q = _points(queries)
+    """w (B,Q) fp32 of scan b at queries (B,Q,3); lengths (B,) for ragged query sets (padding gets 0).  meshes: meshes, or an OrientedCloud."""
+    q = _points(queries, meshes.pos.device if _is_cloud(meshes) else None)
+    if _is_cloud(meshes):
+        return ops.cloud_winding_number(meshes, q, lengths, want_nearest=False)[0]
     return ops.mesh_winding_number(_scans(meshes, q.device), q, lengths)
 
 
 def signed_distance(meshes, queries, lengths=None):
     """sign(|w| - 0.5) sqrt(d2): the distance to the scan's surface, NEGATIVE outside the scan (positive inside: how deep under the garment),
-    (B,Q) fp32; padding gets 0.  d2 is the exact closest point's (ops.ragged_mesh_closest); a NaN w counts as inside."""
-    q = _points(queries)
+    (B,Q) fp32; padding gets 0.  d2 is the exact closest point's (ops.ragged_mesh_closest); a NaN w counts as inside.  With an OrientedCloud
+    d2 is the nearest row's, from the same pass as w: the distance then overestimates by up to the sampling distance."""
+    q = _points(queries, meshes.pos.device if _is_cloud(meshes) else None)
+    if _is_cloud(meshes):
+        w, _, d2 = ops.cloud_winding_number(meshes, q, lengths)
+        return torch.where(w.abs() < 0.5, -d2.sqrt(), d2.sqrt())
     scans = _scans(meshes, q.device)
     w = ops.mesh_winding_number(scans, q, lengths)
     _, _, d2 = ops.ragged_mesh_closest(scans, q, lengths)
@@ -60,11 +75,15 @@ def signed_distance(meshes, queries, lengths=None):
 
 def containment_metrics(meshes, body_verts):
     """Per scan: how much of the body (B,V,3, in the scans' frame) lies outside its scan -> a list of dicts {outside_share: the share of the
-    vertices with |w| < 0.5, protrusion_rms_mm, protrusion_max_mm: the distance to the scan's surface over those vertices (0 with none)}."""
-    v = _points(body_verts)
-    scans = _scans(meshes, v.device)
-    w = ops.mesh_winding_number(scans, v)
-    face, _, d2 = ops.ragged_mesh_closest(scans, v)
+    vertices with |w| < 0.5, protrusion_rms_mm, protrusion_max_mm: the distance to the scan's surface over those vertices (0 with none)}.
+    With an OrientedCloud the distance is to the nearest row (an overestimate by up to the sampling distance)."""
+    v = _points(body_verts, meshes.pos.device if _is_cloud(meshes) else None)
+    if _is_cloud(meshes):
+        w, face, d2 = ops.cloud_winding_number(meshes, v)
+    else:
+        scans = _scans(meshes, v.device)
+        w = ops.mesh_winding_number(scans, v)
+        face, _, d2 = ops.ragged_mesh_closest(scans, v)
     out = (w.abs() < 0.5) & (face >= 0)
     n = out.sum(1).double()
     d2o = torch.where(out, d2.double(), torch.zeros((), dtype=torch.float64, device=v.device))

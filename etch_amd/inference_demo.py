@@ -184,10 +184,12 @@ def parse_args(argv=None):
     return args
 
 
-def fit_and_refine(args, model, points, centered_mesh):
+def fit_and_refine(args, model, points, centered_mesh, report=None):
     """The marker fit of points (N,3), then with --chamfer_refine fit_cham against the centred scan's vertices (the script's `vertices_scan`).
     -> the fit's meshes, the body model, the refined vertices (None without --chamfer_refine) and the parameters as fit_cham's dict (without
-    --chamfer_refine its `init`, the marker fit's).  With --surface_refine the refinement is fit_surface on stage 1's inner points instead."""
+    --chamfer_refine its `init`, the marker fit's).  With --surface_refine the refinement is fit_surface on stage 1's inner points instead.
+    With --surface_contain, centered_mesh may be a cloud.OrientedCloud in the frame of the points (etch_amd.cloud); report: a dict that then
+    receives contain_before and contain_after, the metrics that are printed."""
     from .models.chamfer_refine import fit_cham, init_from_fit
     from .models.fit_SMPL import _resolve_body_model
 
@@ -205,24 +207,27 @@ def fit_and_refine(args, model, points, centered_mesh):
         contain = surface_contain_settings(args)
         if contain is not None:
             # the centred mesh the command ingested (either --ingest mode) is the frame of the points and so of the fit
-            from .containment import containment_metrics, pack_scans
-            scans = pack_scans([centered_mesh], args.device)
+            from .containment import _is_cloud, containment_metrics, pack_scans
+            scans = centered_mesh if _is_cloud(centered_mesh) else pack_scans([centered_mesh], args.device)
             before = containment_metrics(scans, np.asarray(meshes[0].vertices, np.float32)[None])[0]
             surface = dict(surface, scan=scans, **contain)
         verts, prm = fit_surface(bm, inner["inner"], prm, markers=dev["markers"], valid=dev["valid"], marker_vids=list(args.markerset.values()), **surface)
         if contain is not None:
+            after = containment_metrics(scans, verts)[0]
             print("containment before the refinement: " + format_containment(before))
-            print("containment after the refinement:  " + format_containment(containment_metrics(scans, verts)[0]))
+            print("containment after the refinement:  " + format_containment(after))
+            if report is not None:
+                report.update(contain_before=before, contain_after=after)
     elif args.chamfer_refine != "none":
         scan = torch.from_numpy(np.asarray(centered_mesh.vertices, np.float32)).unsqueeze(0).to(args.device)
         verts, prm = fit_cham(bm, scan, prm, prior=None, bidir=args.chamfer_refine, iterations=args.refine_iters)
     return meshes, bm, verts, prm
 
 
-def _refine_and_save(args, model, points, centered_mesh, original_center, scan_name, export=Mesh.export):
+def _refine_and_save(args, model, points, centered_mesh, original_center, scan_name, export=Mesh.export, report=None):
     """--chamfer_refine / --surface_refine: the OBJ is the refined mesh moved back by the scan centre; the .npz holds the refined parameters, `scale`, and the
     joints in the centred scan's frame ((joints + trans) * scale, the frame the LM joints of an unrefined run are written in)."""
-    meshes, _, verts, prm = fit_and_refine(args, model, points, centered_mesh)
+    meshes, _, verts, prm = fit_and_refine(args, model, points, centered_mesh, report=report)
     final = Mesh(verts[0] + original_center, meshes[0].faces)
     export(final, os.path.join(args.output_folder, f"{scan_name}_pred_smpl.obj"))
     pose = prm["pose"][0].cpu().numpy()

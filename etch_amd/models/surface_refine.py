@@ -78,7 +78,8 @@ def fit_surface(body_model, inner_points, init, markers=None, valid=None, marker
     scan: the scans the bodies lie under, in the frame of the inner points -- a list of B Mesh or containment.pack_scans' tuple.
     The loss gains w_contain (sum_v o_v |v - c_v|^2) / V over the body's vertices, o_v = the vertex is outside its scan (|winding number| <
     0.5), c_v its closest point on the scan, both recomputed every contain_every iterations and held in between.  w_contain = 1e2 is w_dense's
-    value (both terms are mean squared metres): a default, not a tuned optimum.  params gains "outside_share" (B,) float64, the share of the
+    value (both terms are mean squared metres): a default, not a tuned optimum.  scan may also be a cloud.OrientedCloud: c_v is then
+    the nearest ROW of the cloud, so the pull ends within one sampling distance of the surface.  params gains "outside_share" (B,) float64, the share of the
     final vertices outside, and the trace a fifth column.  scan=None is the refinement without the term, through the entry point it always used."""
     if iterations < 1:
         raise ValueError("iterations must be >= 1")
@@ -112,10 +113,15 @@ def fit_surface(body_model, inner_points, init, markers=None, valid=None, marker
     if scan is None:
         verts, joints, loss, tr = ops.smpl_surface_refine(db.lbs_consts, faces[str(dev)], pts, params, nl, weights, mk, pr, iterations, lr, **kw)
     else:
-        from ..containment import _scans, containment_metrics
-        scans = _scans(scan, dev)
-        verts, joints, loss, tr = ops.smpl_surface_refine_contain(db.lbs_consts, faces[str(dev)], pts, params, scans, nl, weights, mk, pr, iterations, lr,
-                                                                  w_contain=w_contain, contain_every=contain_every, **kw)
+        from ..containment import _is_cloud, _scans, containment_metrics
+        if _is_cloud(scan):                                 # a cloud.OrientedCloud: the row target, one pass per refresh
+            scans = scan
+            verts, joints, loss, tr = ops.smpl_surface_refine_contain_cloud(db.lbs_consts, faces[str(dev)], pts, params, scans, nl, weights, mk, pr,
+                                                                            iterations, lr, w_contain=w_contain, contain_every=contain_every, **kw)
+        else:
+            scans = _scans(scan, dev)
+            verts, joints, loss, tr = ops.smpl_surface_refine_contain(db.lbs_consts, faces[str(dev)], pts, params, scans, nl, weights, mk, pr, iterations, lr,
+                                                                      w_contain=w_contain, contain_every=contain_every, **kw)
     out = dict(loss=loss.sum(), loss_per_scan=loss, pose=params[:, :3 * nj], beta=params[:, 3 * nj:3 * nj + nb],
                trans=params[:, 3 * nj + nb:3 * nj + nb + 3], scale=params[:, 3 * nj + nb + 3:], joints=joints, verts=verts)
     if want_trace:

@@ -2688,3 +2688,145 @@ def cloud_global_inliers(src_points, src_offsets, tgt_points, tgt_offsets, match
     _lib.call("etch_cloud_global_inliers", int(B), int(Ms), _check_tau(tau, "cloud_global_inliers"), _some(src_points), src_offsets, _some(tgt_points), tgt_offsets,
               _some(match), R, t, _some(pair))
     return pair
+
+
+# ------------------------------------------------------------------ point winding numbers (csrc/cloud_winding.hip)
+def cloud_knn_kth(points, offsets, k, cell=None, brute=False, grid=None):
+    """etch_cloud_knn_kth: d2 of every row to its min(k, n - 1)-th nearest other row of its cloud (0 for a cloud of one row), 3 <= k <= 32, on the
+    cell grid of cloud_knn_mean; `cell` and brute change no bit.  grid: what cloud_cell_grid(points, offsets, 0, k, ..) returned, to share one.
+    -> d2k (M) fp64 by original row (zeros for a cloud with a status bit), status (B) int32, both still on the device."""
+    B, M = _cloud_args(points, offsets, "cloud_knn_kth")
+    if not 3 <= int(k) <= CLOUD_MAX_K:
+        raise _lib.EtchHipError(f"cloud_knn_kth: k must lie in 3 .. {CLOUD_MAX_K}, got {k}")
+    if cell is not None and not (float(cell) > 0.0 and math.isfinite(float(cell))):
+        raise _lib.EtchHipError(f"cloud_knn_kth: cell must be positive and finite, got {cell}")
+    grid, status, sp, sk, order = cloud_cell_grid(points, offsets, 0, k, 0.0 if cell is None else float(cell), sort=not brute) if grid is None else grid
+    d2k = torch.zeros((M,), dtype=torch.float64, device=points.device)
+    _lib.call("etch_cloud_knn_kth", int(B), int(M), int(k), int(bool(brute)), points if brute else sp, sk, order, offsets, grid, status, d2k)
+    return d2k, status
+
+
+def cloud_surface_pack(points, offsets, normal, flag, d2k, k, center=None):
+    """etch_cloud_surface_pack: points (M,3), normal (M,3) oriented unit normals, d2k (M) fp64 and flag (M) int32 by original row, k the k of d2k,
+    center (B,3) fp64 or None -> pos (M,3), moment (M,3), cap (M) fp32: the rows cloud_winding_number reads (zeros behind the last cloud)."""
+    B, M = _cloud_args(points, offsets, "cloud_surface_pack")
+    if not 3 <= int(k) <= CLOUD_MAX_K:
+        raise _lib.EtchHipError(f"cloud_surface_pack: k must lie in 3 .. {CLOUD_MAX_K}, got {k}")
+    _need(normal, torch.float64, "normal"), _need(flag, torch.int32, "flag"), _need(d2k, torch.float64, "d2k")
+    if tuple(normal.shape) != (M, 3) or tuple(flag.shape) != (M,) or tuple(d2k.shape) != (M,):
+        raise _lib.EtchHipError(f"cloud_surface_pack: normal ({M},3), flag ({M},), d2k ({M},), got {tuple(normal.shape)}, {tuple(flag.shape)}, {tuple(d2k.shape)}")
+    if center is not None:
+        _need(center, torch.float64, "center")
+        if tuple(center.shape) != (B, 3):
+            raise _lib.EtchHipError(f"cloud_surface_pack: center must be ({B},3), got {tuple(center.shape)}")
+    dev = points.device
+    pos = torch.zeros((M, 3), dtype=torch.float32, device=dev)
+    moment = torch.zeros((M, 3), dtype=torch.float32, device=dev)
+    cap = torch.zeros((M,), dtype=torch.float32, device=dev)
+    _lib.call("etch_cloud_surface_pack", int(B), int(M), int(k), points, normal, flag, d2k, offsets, center, pos, moment, cap)
+    return pos, moment, cap
+
+
+def _oriented_cloud_args(cloud, B, what):
+    """cloud = (pos (M,3), moment (M,3), cap (M) fp32, offsets (B+1) int32, max_rows), or an object with these attributes (cloud.OrientedCloud):
+    the packed batch of cloud_surface_pack -> the four tensors and max_rows, shapes and dtypes checked.  The offsets stay on the device: max_rows
+    is the caller's (a host integer known when the batch was packed)."""
+    if isinstance(cloud, (tuple, list)):
+        if len(cloud) != 5:
+            raise _lib.EtchHipError(f"{what}: the oriented cloud is (pos, moment, cap, offsets, max_rows)")
+        pos, moment, cap, offsets, max_rows = cloud
+    else:
+        pos, moment, cap, offsets, max_rows = cloud.pos, cloud.moment, cloud.cap, cloud.offsets, cloud.max_rows
+    _need(pos, torch.float32, "pos"), _need(moment, torch.float32, "moment"), _need(cap, torch.float32, "cap"), _need(offsets, torch.int32, "offsets")
+    M = pos.shape[0]
+    if pos.dim() != 2 or pos.shape[1] != 3 or tuple(moment.shape) != (M, 3) or tuple(cap.shape) != (M,) or tuple(offsets.shape) != (B + 1,):
+        raise _lib.EtchHipError(f"{what}: pos (M,3), moment (M,3), cap (M,), offsets ({B + 1},), got {tuple(pos.shape)}, {tuple(moment.shape)}, "
+                                f"{tuple(cap.shape)}, {tuple(offsets.shape)}")
+    if int(max_rows) < 0 or int(max_rows) > M:
+        raise _lib.EtchHipError(f"{what}: max_rows must lie in [0, {M}], got {max_rows}")
+    return pos, moment, cap, offsets, int(max_rows)
+
+
+def cloud_winding_number(cloud, queries, lengths=None, want_nearest=True):
+    """etch_cloud_winding_number: the winding number of the oriented cloud b (_oriented_cloud_args) at queries (B,Q,3) fp32 (lengths (B,) for ragged
+    query sets) and, from the same pass, the nearest row.  -> w (B,Q) fp32, nearest (B,Q) int32 local to the cloud (-1: none), nearest_d2 (B,Q)
+    fp32 (the last two None without want_nearest).  Padding gets 0, -1, 0.  Bitwise reproducible; cloud b alone = cloud b in a batch."""
+    B, Q = _queries(queries, "queries")
+    pos, moment, cap, offsets, mr = _oriented_cloud_args(cloud, B, "cloud_winding_number")
+    ql = _lengths(lengths, B, Q, queries.device, "lengths")
+    ws = _byte_workspace("etch_cloud_winding_number_workspace", queries.device, B, Q, mr)
+    dev = queries.device
+    w = torch.empty((B, Q), dtype=torch.float32, device=dev)
+    nearest = torch.empty((B, Q), dtype=torch.int32, device=dev) if want_nearest else None
+    d2 = torch.empty((B, Q), dtype=torch.float32, device=dev) if want_nearest else None
+    _lib.call("etch_cloud_winding_number", B, Q, mr, pos, moment, cap, offsets, queries, ql, ws, w, nearest, d2)
+    return w, nearest, d2
+
+
+def cloud_containment_energy_grad(body_verts, cloud, w, nearest, nearest_d2, coef=None, w_contain=1.0, g=None):
+    """containment_energy_grad against an oriented cloud: o_v = [|w_v| < 0.5] with a nearest row, c_v = that row's position (a sample of the
+    surface) -> terms (B,2) fp64 = {sum_v o_v nearest_d2_v, sum_v o_v} and g (B,V,3) (given: updated IN PLACE; None: zeros first) with
+    coef_b w_contain (2 / V) o_v (v - c_v) added.  -> (terms, g)."""
+    B, V = _queries(body_verts, "body_verts")
+    pos, _, _, offsets, _ = _oriented_cloud_args(cloud, B, "cloud_containment_energy_grad")
+    if tuple(w.shape) != (B, V) or tuple(nearest.shape) != (B, V) or tuple(nearest_d2.shape) != (B, V):
+        raise _lib.EtchHipError(f"cloud_containment_energy_grad: w, nearest and nearest_d2 must be ({B},{V})")
+    _need(w, torch.float32, "w"), _need(nearest, torch.int32, "nearest"), _need(nearest_d2, torch.float32, "nearest_d2")
+    if coef is not None:
+        coef = _need(coef.to(torch.float32).contiguous(), torch.float32, "coef")
+        if tuple(coef.shape) != (B,):
+            raise _lib.EtchHipError(f"coef must be ({B},)")
+    if g is None:
+        g = torch.zeros_like(body_verts)
+    elif tuple(g.shape) != (B, V, 3):
+        raise _lib.EtchHipError(f"g must be ({B},{V},3)")
+    _need(g, torch.float32, "g")
+    ws = _byte_workspace("etch_cloud_containment_energy_grad_workspace", body_verts.device, B, V)
+    terms = torch.zeros((B, 2), dtype=torch.float64, device=body_verts.device)
+    _lib.call("etch_cloud_containment_energy_grad", B, V, body_verts, pos, offsets, w, nearest, nearest_d2, coef, float(w_contain), ws, terms, g)
+    _lib.wrote(g)
+    return terms, g
+
+
+def smpl_surface_refine_contain_cloud(consts, faces, points, params, scan, lengths=None, weights=None, markers=None, prior=None, iters=200, lr=2e-2,
+                                      beta1=0.9, beta2=0.999, eps=1e-8, w_dense=1e2, w_marker=1.0, w_beta=1e-2, w_prior=1e-7, trunc=0.05,
+                                      optimize_scale=False, w_contain=1e2, contain_every=10, nj=24, nb=10, n_extra=21, want_trace=False):
+    """smpl_surface_refine_contain with scan = an oriented cloud in the body's frame (_oriented_cloud_args): at iterations 0, K, 2K, ... one pass
+    of cloud_winding_number over the current vertices gives o_v and the row c_v each outside vertex is pulled to; held in between.
+    params is updated IN PLACE.  -> verts, joints, loss of the last forward (B,), loss trace (B, iters, 5) or None."""
+    _need(points, torch.float32, "points"), _need(params, torch.float32, "params"), _need(faces, torch.int32, "faces")
+    _check_body(consts, nj, nb, n_extra)
+    V = int(consts[0].shape[0])
+    if points.dim() != 3 or points.shape[2] != 3 or tuple(params.shape) != (points.shape[0], 3 * nj + nb + 4) or faces.dim() != 2 or faces.shape[1] != 3:
+        raise _lib.EtchHipError(f"points must be (B,N,3), params (B, {3 * nj + nb + 4}), faces (F,3)")
+    B, N, _ = points.shape
+    F = int(faces.shape[0])
+    if F and (int(faces.min()) < 0 or int(faces.max()) >= V):
+        raise _lib.EtchHipError(f"face vertex ids must lie in [0, {V})")
+    if int(contain_every) < 1:
+        raise _lib.EtchHipError("contain_every must be at least 1")
+    pos, moment, cap, offsets, mr = _oriented_cloud_args(scan, B, "smpl_surface_refine_contain_cloud")
+    nl = _lengths(lengths, B, N, points.device, "lengths")
+    if weights is not None:
+        weights = _need(weights.to(torch.float32).contiguous(), torch.float32, "weights")
+        if tuple(weights.shape) != (B, N):
+            raise _lib.EtchHipError(f"weights must be ({B},{N})")
+    M, vids, mpos, valid = _marker_args(markers, B, V, points.device)
+    arr = (ctypes.c_void_p * 8)(*[t.data_ptr() for t in consts])
+    G, parr = 0, None
+    if prior is not None:
+        means, prec, w = (_need(t, torch.float32, n) for t, n in zip(prior, ("means", "precisions", "nll_weights")))
+        G = int(w.shape[0])
+        if tuple(w.shape) != (G,) or tuple(means.shape) != (G, 69) or tuple(prec.shape) != (G, 69, 69):
+            raise _lib.EtchHipError("prior: means (G,69), precisions (G,69,69), nll_weights (G,)")
+        parr = (ctypes.c_void_p * 3)(means.data_ptr(), prec.data_ptr(), w.data_ptr())
+    ws = _byte_workspace("etch_smpl_surface_refine_contain_cloud_workspace", points.device, B, N, V, int(nj), int(nb), int(n_extra), mr)
+    verts = torch.empty((B, V, 3), dtype=torch.float32, device=points.device)
+    joints = torch.empty((B, nj + n_extra, 3), dtype=torch.float32, device=points.device)
+    loss = torch.empty((B,), dtype=torch.float32, device=points.device)
+    tr = torch.empty((B, iters, 5), dtype=torch.float32, device=points.device) if want_trace else None
+    _lib.call("etch_smpl_surface_refine_contain_cloud", B, N, V, F, int(nj), int(nb), int(n_extra), arr, faces, points, nl, weights, M, vids, mpos, valid, parr,
+              G, int(iters), float(lr), float(beta1), float(beta2), float(eps), float(w_dense), float(w_marker), float(w_beta), float(w_prior), float(trunc),
+              int(bool(optimize_scale)), mr, pos, moment, cap, offsets, float(w_contain), int(contain_every), params, verts, joints, tr, loss, ws)
+    _lib.wrote(params)
+    return verts, joints, loss, tr

@@ -1240,6 +1240,56 @@ int etch_cloud_global_select(int B, int H, int min_inliers, const double* transf
 int etch_cloud_global_inliers(int B, int Ms, double tau, const double* src_points, const int* src_offsets, const double* tgt_points, const int* tgt_offsets,
                               const int* match, const double* R, const double* t, int* pair, void* stream);
 
+/* ---- raw point clouds: point winding numbers and containment against a cloud (csrc/cloud_winding.hip, csrc/cloud_winding_solve.h; DESIGN
+ * section 26) -------------------------------------------------------------------------------------------------------------------------------- */
+
+/* d2k (M) fp64 by original row = the ke-th least d2 among the other rows of the row's cloud, ke = min(k, n - 1), 3 <= k <= ETCH_CLOUD_MAX_K: the d2
+ * of the last row of etch_cloud_normals' neighbourhood; 0 for a cloud of one row.  Inputs as etch_cloud_knn_mean takes them (the mode 0 keys, sorted;
+ * exact for any cell size; brute != 0: every query scans its whole cloud, sorted_points is then the unsorted points and sorted_keys, order, grid may
+ * be NULL), and the same bits in every form.  Rows of a cloud with ETCH_CLOUD_STATUS_NONFINITE are not written. */
+int etch_cloud_knn_kth(int B, int M, int k, int brute, const double* sorted_points, const long long* sorted_keys, const int* order, const int* offsets,
+                       const double* grid, const int* status, double* d2k, void* stream);
+/* The rows the winding sweep reads, from points (M,3), normal (M,3) ORIENTED unit normals, flag (M) int32 and d2k (M) of etch_cloud_knn_kth at the
+ * same k, all fp64 by original row; center (B,3) fp64 or NULL = 0.  a_i = (pi d2k_i) / ke in fp64 in that order, 0 where ke = 0, flag_i != 0 or a
+ * coordinate of the row is not finite.  pos (M,3) = fp32(p - center), moment (M,3) = fp32(a n), cap (M) = fp32(a / pi): each difference, product and
+ * quotient in fp64, rounded once. */
+int etch_cloud_surface_pack(int B, int M, int k, const double* points, const double* normal, const int* flag, const double* d2k, const int* offsets,
+                            const double* center, float* pos, float* moment, float* cap, void* stream);
+/* Workspace bytes of etch_cloud_winding_number. */
+int etch_cloud_winding_number_workspace(int B, int Q, int max_rows, long long* bytes);
+/* The winding number of the oriented cloud b (rows offsets[b] .. offsets[b + 1] of pos, moment, cap; offsets (B+1) int32 in device memory; max_rows
+ * >= every cloud's row count sizes the launch, rows of a cloud past it are not visited) at queries (B,Q,3) fp32; q_len (B) int32 or NULL: queries at
+ * or past it are padding and get w 0, nearest -1, nearest_d2 0.  Per (query q, row i), every operation fp32 and rounded once: r = pos_i - q,
+ * d2 = (rx rx + ry ry) + rz rz, s = d2 where d2 > cap_i else cap_i, term = ((rx mx + ry my) + rz mz) / (s sqrtf(s)); a row with cap_i == 0 contributes
+ * exactly 0.  A thread adds the terms of one 1024-row chunk in ascending row order in fp32 from 0; the chunks are added in ascending order in fp64,
+ * multiplied by the double nearest 1 / (4 pi) and rounded once: w (B,Q) = 1 inside a closed surface sampled with outward normals, 0 outside, -1
+ * with inward normals.  nearest (B,Q) int32 or NULL = the row, local to its cloud, with the least (d2, row) among the rows with d2 < +inf (a NaN or
+ * infinite d2 never wins; -1 where there is none), nearest_d2 (B,Q) fp32 or NULL its d2 (0 with -1), from the same pass.  No atomics: cloud b in a
+ * batch is bitwise cloud b alone, and two runs are bitwise equal. */
+int etch_cloud_winding_number(int B, int Q, int max_rows, const float* pos, const float* moment, const float* cap, const int* offsets, const float* queries,
+                              const int* q_len, void* workspace, float* w, int* nearest, float* nearest_d2, void* stream);
+/* Workspace bytes of etch_cloud_containment_energy_grad. */
+int etch_cloud_containment_energy_grad_workspace(int B, int V, long long* bytes);
+/* etch_containment_energy_grad against a cloud: o_v = [ |w_v| < 0.5 ] and nearest_v in [0, n_b) (a NaN w is not outside), c_v = pos[nearest_v] as
+ * fp64 -- a SAMPLE of the surface.  terms (B,2) fp64 = {sum_v o_v nearest_d2_v, sum_v o_v}; g (B,V,3) or NULL, to which coef_b w_contain (2 / V)
+ * o_v (v - c_v) is ADDED under the rules stated there. */
+int etch_cloud_containment_energy_grad(int B, int V, const float* body_verts, const float* pos, const int* offsets, const float* w, const int* nearest,
+                                       const float* nearest_d2, const float* coef, float w_contain, void* workspace, double* terms, float* g,
+                                       void* stream);
+/* Workspace bytes of etch_smpl_surface_refine_contain_cloud. */
+int etch_smpl_surface_refine_contain_cloud_workspace(int B, int N, int V, int nj, int nb, int n_extra, int max_rows, long long* bytes);
+/* etch_smpl_surface_refine_contain with the scan given as an oriented cloud (max_rows, pos, moment, cap, offsets, in the frame of the body): at a
+ * refresh the one pass of etch_cloud_winding_number over the current vertices gives o_v and the row each outside vertex is pulled to; everything
+ * else -- the hold-fixed rule, the normalisation by V, the trace (B, iters, 5), the schedule on `stream` without a host wait -- is as stated
+ * there.  With w_contain = 0 the parameters and the first four trace columns are bitwise those of etch_smpl_surface_refine. */
+int etch_smpl_surface_refine_contain_cloud(int B, int N, int V, int F, int nj, int nb, int n_extra, const void* const* consts, const int* faces,
+                                           const float* points, const int* n_len, const float* weights, int M, const int* marker_vids, const float* markers,
+                                           const float* marker_valid, const void* const* prior, int n_gauss, int iters, float lr, float beta1, float beta2,
+                                           float eps, float w_dense, float w_marker, float w_beta, float w_prior, float trunc, int optimize_scale,
+                                           int max_rows, const float* pos, const float* moment, const float* cap, const int* offsets, float w_contain,
+                                           int contain_every, float* params, float* verts, float* joints, float* loss_trace, float* loss_last,
+                                           void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
