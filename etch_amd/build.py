@@ -23,7 +23,8 @@ EXTRA = {"index_ops.hip": ["-ffp-contract=off"], "chamfer_fit.hip": ["-ffp-contr
          "depth_render.hip": ["-ffp-contract=off"], "surface_fit.hip": ["-ffp-contract=off"], "containment.hip": ["-ffp-contract=off"],
          "cloud_filter.hip": ["-ffp-contract=off"], "cloud_isolate.hip": ["-ffp-contract=off"],
          "cloud_align.hip": ["-ffp-contract=off"], "cloud_normals.hip": ["-ffp-contract=off"],
-         "cloud_global.hip": ["-ffp-contract=off"], "cloud_winding.hip": ["-ffp-contract=off"]}
+         "cloud_global.hip": ["-ffp-contract=off"], "cloud_winding.hip": ["-ffp-contract=off"],
+         "cloud_mesh.hip": ["-ffp-contract=off"]}
 
 
 def hipcc():

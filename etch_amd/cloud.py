@@ -25,6 +25,8 @@ handing it to the pipeline.
     features(cloud, k=32, viewpoint=), global_align(source, target, keys, viewpoint=(vs, vt), ...)   FPFH descriptors; a rough pose from nothing by
                                                                feature matches and RANSAC, the start of align(init="global") (section 25)
 
+    reconstruct(surface, voxel) -> Reconstruction   the watertight mesh of an OrientedCloud (section 27): the level set |w| = 0.5 of its winding
+                                  number by marching tetrahedra on blocks that follow the surface
     areas(cloud, k=8), orient_normals(cloud, normals, sensors), surface(cloud, sensors=, normals=) -> OrientedCloud   a cloud with an inside (section 26):
                                                                what etch_amd.containment and fit_surface(scan=) take in place of a mesh
     fuse(views, transforms, voxel=, return_view=True)          also the view every fused row came from
@@ -930,6 +932,123 @@ def surface(cloud, sensors=None, normals=None, normal_k=16, area_k=8, center=Non
     return OrientedCloud(pos, moment, cap, cloud.offsets, int(np.diff(o).max()))
 
 
+# ---------------------------------------------------------------------------------------------------------------- a mesh from the winding field
+MESH_KEEP = ("largest", "all")
+MESH_MAX_PAD, MESH_MAX_DILATE, MESH_MAX_ROUNDS = 64, 2, 1 << 20
+
+
+class Reconstruction:
+    """What reconstruct() returns: meshes = one Mesh per cloud (float64 vertices, int32 faces; empty for an empty cloud), and per cloud closed (B)
+    bool, clipped (B) = mixed faces that pointed out of the lattice, blocks (B) = blocks evaluated, rounds (B) = growth rounds that added blocks,
+    components (B) = connected components before keep= chose, status (B) = STATUS_EMPTY or 0, all numpy."""
+
+    def __init__(self, meshes, closed, clipped, blocks, rounds, components, status):
+        self.meshes, self.closed, self.clipped, self.blocks, self.rounds, self.components, self.status = meshes, closed, clipped, blocks, rounds, components, status
+
+
+def _check_int(x, lo, hi, name):
+    if isinstance(x, bool) or int(x) != x or not lo <= int(x) <= hi:
+        raise ValueError(f"{name} must be an integer in {lo} .. {hi}, got {x}")
+    return int(x)
+
+
+def reconstruct(surface, voxel, level=0.5, keep="largest", seed_dilate=0, pad_blocks=2, max_rounds=32, center=None):
+    """The watertight surface of an oriented cloud: the level set |w| = level of section 26's winding number, by marching
+    tetrahedra on a lattice of `voxel`-sized cells in blocks of 8 x 8 x 8.  Only the blocks the surface runs through are evaluated: the blocks
+    that hold a row (dilated by seed_dilate blocks), then, round by round, the neighbours behind every block face the level set crosses, at most
+    max_rounds rounds.  closed[b] says that the followed surface left neither the evaluated blocks nor the lattice (pad_blocks blocks around the
+    rows): then the mesh has no boundary edge.  closed = False is a result, not an error.  keep="largest" keeps the connected component with the
+    most faces (a tie: the one with the lowest vertex), keep="all" everything.  Vertices are welded by the integer key of the lattice edge they
+    lie on, in ascending key order; center (B,3) or (3,) is added to them in fp64.  Bitwise reproducible; cloud b in a batch is bitwise cloud b
+    alone.  ValueError for every argument out of range before any launch; EtchHipError naming the cloud whose lattice is out of range (an axis
+    with more than 2^20 - 1 nodes or more than 2^24 blocks: the voxel is too small for the cloud's extent).  -> Reconstruction."""
+    if not isinstance(surface, OrientedCloud):
+        raise ValueError(f"surface must be an OrientedCloud (cloud.surface), got {type(surface).__name__}")
+    if isinstance(voxel, bool) or not isinstance(voxel, (int, float, np.floating, np.integer)) or not (float(voxel) > 0.0 and math.isfinite(float(voxel))):
+        raise ValueError(f"voxel must be positive and finite, got {voxel}")
+    if isinstance(level, bool) or not isinstance(level, (int, float, np.floating, np.integer)) or not 0.0 < float(level) < 1.0:
+        raise ValueError(f"level must lie in (0, 1), got {level}")
+    if keep not in MESH_KEEP:
+        raise ValueError(f"keep must be one of {MESH_KEEP}, got {keep!r}")
+    seed_dilate = _check_int(seed_dilate, 0, MESH_MAX_DILATE, "seed_dilate")
+    pad_blocks = _check_int(pad_blocks, 0, MESH_MAX_PAD, "pad_blocks")
+    max_rounds = _check_int(max_rounds, 0, MESH_MAX_ROUNDS, "max_rounds")
+    import torch
+
+    from . import ops
+    from .models.fit_SMPL import Mesh
+    B = int(surface.offsets.numel()) - 1
+    c = np.zeros((B, 3))
+    if center is not None:
+        cc = center.detach().cpu().numpy() if isinstance(center, torch.Tensor) else np.asarray(center)
+        if cc.dtype.kind not in "fiu" or cc.shape not in ((3,), (B, 3)) or not np.isfinite(cc.astype(np.float64)).all():
+            raise ValueError(f"center must be (3,) or ({B},3) finite numbers, got {cc.dtype} {cc.shape}")
+        c = np.array(np.broadcast_to(cc.astype(np.float64), (B, 3)))
+    voxel, level = float(voxel), float(level)
+    dev = surface.pos.device
+    with torch.cuda.device(dev):
+        lattice, status = ops.cloud_mesh_lattice(surface, voxel, pad_blocks)
+        lat, st = lattice.cpu().numpy().astype(np.int64), status.cpu().numpy()
+        if (st & STATUS_RANGE).any():
+            b = int(np.flatnonzero(st & STATUS_RANGE)[0])
+            raise _lib.EtchHipError(f"reconstruct: cloud {b}: the lattice has an axis with more than 2^20 - 1 nodes or more than 2^24 blocks: "
+                                    "the voxel is too small for the cloud's extent")
+        toff_host = np.concatenate([[0], np.cumsum((lat[:, 3:] - lat[:, :3]).prod(1))]).astype(np.int64)
+        toff = torch.from_numpy(toff_host).to(dev)
+        table = torch.full((int(toff_host[-1]),), ops.MESH_TABLE_INACTIVE, dtype=torch.int32, device=dev)
+        ops.cloud_mesh_seed(surface, voxel, seed_dilate, lattice, status, toff, table)
+        slots, fields = [], []
+        clipped = torch.zeros((B,), dtype=torch.int64, device=dev)
+        rounds = torch.zeros((B,), dtype=torch.int64, device=dev)
+        left_open = torch.zeros((B,), dtype=torch.bool, device=dev)
+        n_slots, r = 0, 0
+        while True:
+            new = torch.nonzero(table == ops.MESH_TABLE_MARK, as_tuple=False)[:, 0]      # ascending = (cloud, block key); the round's one readback
+            if new.numel() == 0:
+                break
+            of = torch.bucketize(new, toff[1:], right=True)
+            if r > max_rounds:                                                            # the surface goes on, the rounds are used up
+                table[new] = ops.MESH_TABLE_INACTIVE
+                left_open[of] = True
+                break
+            if r > 0:
+                rounds[torch.unique(of)] += 1
+            sl = torch.stack([of, new - toff[of]], 1).to(torch.int32).contiguous()
+            table[new] = torch.arange(n_slots, n_slots + new.numel(), dtype=torch.int32, device=dev)
+            n_slots += int(new.numel())
+            fld = ops.cloud_mesh_field(surface, voxel, level, lattice, sl)
+            flags = ops.cloud_mesh_grow(lattice, toff, sl, fld, table)
+            clipped.index_add_(0, of, (flags == 2).sum(1))
+            slots.append(sl), fields.append(fld)
+            r += 1
+        meshes = [Mesh(np.zeros((0, 3)) + c[b], np.zeros((0, 3), np.int32)) for b in range(B)]
+        components = np.zeros(B, np.int64)
+        blocks = np.zeros(B, np.int64)
+        if slots:
+            sl, fld = torch.cat(slots), torch.cat(fields)
+            order = torch.argsort(sl[:, 0].long() * (1 << 32) + sl[:, 1].long())
+            sl, fld = sl[order].contiguous(), fld[order].contiguous()
+            counts, keys, fpos = ops.cloud_mesh_extract(lattice, voxel, sl, fld)
+            per_cloud = torch.zeros((B,), dtype=torch.int64, device=dev).index_add_(0, sl[:, 0].long(), counts.sum(1, dtype=torch.int64))
+            f_end = np.cumsum(per_cloud.cpu().numpy())
+            blocks = torch.bincount(sl[:, 0].long(), minlength=B).cpu().numpy()
+            for b in range(B):
+                f0, f1 = int(f_end[b - 1]) if b else 0, int(f_end[b])
+                if f1 == f0:
+                    continue
+                _, verts, faces = ops.cloud_mesh_weld(keys[f0:f1], fpos[f0:f1])
+                labels = ops.mesh_components(verts.shape[0], faces)
+                components[b] = int((labels == torch.arange(verts.shape[0], dtype=torch.int32, device=dev)).sum())
+                if keep == "largest" and components[b] > 1:
+                    per_label = torch.bincount(labels[faces[:, 0].long()].long(), minlength=verts.shape[0])
+                    winner = int(torch.nonzero(per_label == per_label.max(), as_tuple=False)[0, 0])      # a tie: the lowest label
+                    verts, faces = ops.mesh_keep_component(verts, faces, labels, winner)
+                meshes[b] = Mesh(verts.cpu().numpy().astype(np.float64) + c[b], faces.cpu().numpy())
+        clipped = clipped.cpu().numpy()
+        closed = (st == 0) & ~left_open.cpu().numpy() & (clipped == 0)
+    return Reconstruction(meshes, closed, clipped, blocks, rounds.cpu().numpy(), components, st)
+
+
 # ---------------------------------------------------------------------------------------------------------------- global registration
 MAX_GLOBAL_HYPOTHESES = 262144
 STATUS_GLOBAL_NOT_FOUND = 16                                       # align(init="global"): no pose was found, the loop started from the identity
@@ -1277,6 +1396,11 @@ def build_parser():
     add_surface_refine_flags(p)
     p.add_argument("--contain_normal_k", type=int, default=16, help="--surface_contain: neighbours per normal of the cleaned cloud (3 .. 32)")
     p.add_argument("--contain_area_k", type=int, default=8, help="--surface_contain: neighbours per area of the cleaned cloud (3 .. 32)")
+    p.add_argument("--mesh_out", action="store_true", help="write the subject's surface, the level set of the cleaned cloud's winding number, as "
+                   "<name>_surface.obj in the input frame; needs --more_views or a file that carries normals; uses --contain_normal_k and --contain_area_k")
+    p.add_argument("--mesh_voxel", type=float, default=0.01, help="--mesh_out: the lattice's cell size in metres")
+    p.add_argument("--mesh_level", type=float, default=0.5, help="--mesh_out: the level of |w| the surface is, in (0, 1)")
+    p.add_argument("--mesh_keep", type=str, default="largest", choices=list(MESH_KEEP), help="--mesh_out: the largest connected component, or all")
     return p
 
 
@@ -1292,7 +1416,11 @@ def parse_args(argv=None):
         p.error("--num_point must be at least 1")
     from .inference_demo import surface_contain_settings, surface_refine_settings
     surface_refine_settings(a, p)
-    if surface_contain_settings(a, p) is not None:
+    if a.mesh_voxel <= 0.0 or not math.isfinite(a.mesh_voxel):
+        p.error("--mesh_voxel must be positive and finite")
+    if not 0.0 < a.mesh_level < 1.0:
+        p.error("--mesh_level must lie in (0, 1)")
+    if surface_contain_settings(a, p) is not None or a.mesh_out:
         for k in (a.contain_normal_k, a.contain_area_k):
             if not AREA_MIN_K <= k <= MAX_K:
                 p.error(f"--contain_normal_k and --contain_area_k must lie in {AREA_MIN_K} .. {MAX_K}")
@@ -1306,8 +1434,9 @@ def main(argv=None):
     args = parse_args(argv)
     raw, raw_normals = mesh_io.read_cloud(args.cloud_path, return_normals=True)     # a malformed file raises before the model is loaded
     contain = getattr(args, "surface_contain", False)
-    if contain and not args.more_views and raw_normals is None:
-        build_parser().error("--surface_contain: a single view is half a shell and has no inside; give --more_views, or a file that carries normals")
+    for flag, on in (("--surface_contain", contain), ("--mesh_out", args.mesh_out)):
+        if on and not args.more_views and raw_normals is None:
+            build_parser().error(f"{flag}: a single view is half a shell and has no inside; give --more_views, or a file that carries normals")
     model = demo.prepare_common(args)
     export = Mesh.export
     if getattr(args, "ingest", "host") == "device":
@@ -1316,7 +1445,7 @@ def main(argv=None):
     floor, cluster = isolate_args(args)
     views, view = {}, None
     if args.more_views:                                               # the views enter as one cloud, ahead of every cleaning stage
-        if contain:
+        if contain or args.mesh_out:
             raw, views, view = register_files(raw, args, return_view=True)
         else:
             raw, views = register_files(raw, args)
@@ -1327,6 +1456,12 @@ def main(argv=None):
     stages = {f"rows_{k}": v for k, v in clean.stages.items()}
     report = dict(keep=clean.keep.cpu().numpy(), center=center, points=points, removed=np.int64(len(raw) - int(clean.keep.sum())),
                   rows_output=np.array([len(cleaned)]), **stages, **isolate_report(clean), **views)
+    if args.mesh_out:                                                 # the subject's own surface, next to the body's
+        rec = reconstruct(contain_cloud(args, clean, center, raw_normals, view, views.get("view_pose")), args.mesh_voxel, level=args.mesh_level,
+                          keep=args.mesh_keep, center=center)
+        export(rec.meshes[0], os.path.join(args.output_folder, f"{name}_surface.obj"))
+        report.update(mesh_closed=rec.closed[0], mesh_blocks=rec.blocks[0], mesh_rounds=rec.rounds[0], mesh_components=rec.components[0],
+                      mesh_vertices=np.int64(len(rec.meshes[0].vertices)), mesh_faces=np.int64(len(rec.meshes[0].faces)))
     if getattr(args, "surface_refine", False):                        # the fit comes first: the report holds the containment figures
         scan = contain_cloud(args, clean, center, raw_normals, view, views.get("view_pose")) if contain else Mesh(cleaned - center, np.zeros((0, 3), np.int64))
         found = {}

@@ -2830,3 +2830,134 @@ def smpl_surface_refine_contain_cloud(consts, faces, points, params, scan, lengt
               int(bool(optimize_scale)), mr, pos, moment, cap, offsets, float(w_contain), int(contain_every), params, verts, joints, tr, loss, ws)
     _lib.wrote(params)
     return verts, joints, loss, tr
+
+
+# ------------------------------------------------------------------ a mesh from the winding field (csrc/cloud_mesh.hip)
+MESH_BLOCK_NODES = 729
+MESH_BLOCK_CELLS = 512
+MESH_TABLE_INACTIVE, MESH_TABLE_MARK = -1, -2
+
+
+def _mesh_cloud(cloud, what):
+    B = int(cloud[3].numel() if isinstance(cloud, (tuple, list)) else cloud.offsets.numel()) - 1
+    return (B,) + _oriented_cloud_args(cloud, B, what)
+
+
+def _mesh_voxel(voxel, what):
+    if not (float(voxel) > 0.0 and math.isfinite(float(voxel))):
+        raise _lib.EtchHipError(f"{what}: voxel must be positive and finite, got {voxel}")
+    return float(voxel)
+
+
+def _mesh_slots(lattice, slots, B, what):
+    _need(lattice, torch.int32, "lattice"), _need(slots, torch.int32, "slots")
+    if tuple(lattice.shape) != (B, 6) or slots.dim() != 2 or slots.shape[1] != 2:
+        raise _lib.EtchHipError(f"{what}: lattice must be ({B},6) and slots (S,2), got {tuple(lattice.shape)} and {tuple(slots.shape)}")
+    return int(slots.shape[0])
+
+
+def cloud_mesh_lattice(cloud, voxel, pad_blocks=2):
+    """etch_cloud_mesh_lattice: the block lattice of every oriented cloud -> lattice (B,6) int32 = lo, hi in blocks, status (B) int32
+    (CLOUD_STATUS_EMPTY, CLOUD_STATUS_RANGE), both still on the device."""
+    B, pos, _, cap, offsets, mr = _mesh_cloud(cloud, "cloud_mesh_lattice")
+    lattice = torch.zeros((B, 6), dtype=torch.int32, device=offsets.device)
+    status = torch.zeros((B,), dtype=torch.int32, device=offsets.device)
+    _lib.call("etch_cloud_mesh_lattice", B, mr, pos, cap, offsets, _mesh_voxel(voxel, "cloud_mesh_lattice"), int(pad_blocks), lattice, status)
+    return lattice, status
+
+
+def cloud_mesh_seed(cloud, voxel, seed_dilate, lattice, status, table_offsets, table):
+    """etch_cloud_mesh_seed: marks (MESH_TABLE_MARK) the blocks of round 0 in table (int32, cloud b's blocks from table_offsets[b] on, (B+1) int64 on
+    the device), IN PLACE."""
+    B, pos, _, cap, offsets, mr = _mesh_cloud(cloud, "cloud_mesh_seed")
+    _need(lattice, torch.int32, "lattice"), _need(status, torch.int32, "status"), _need(table_offsets, torch.int64, "table_offsets"), _need(table, torch.int32, "table")
+    if tuple(lattice.shape) != (B, 6) or tuple(status.shape) != (B,) or tuple(table_offsets.shape) != (B + 1,) or table.dim() != 1:
+        raise _lib.EtchHipError(f"cloud_mesh_seed: lattice ({B},6), status ({B},), table_offsets ({B + 1},), table (T,)")
+    _lib.call("etch_cloud_mesh_seed", B, mr, pos, cap, offsets, _mesh_voxel(voxel, "cloud_mesh_seed"), int(seed_dilate), lattice, status, table_offsets, table)
+    _lib.wrote(table)
+    return table
+
+
+def cloud_mesh_field(cloud, voxel, level, lattice, slots):
+    """etch_cloud_mesh_field: s = |w| - level at the 729 nodes of the blocks slots (S,2) int32 = (cloud, index in the cloud's table) -> (S,729) fp32;
+    w is cloud_winding_number's at the node's fp32 position, to the bit."""
+    B, pos, moment, cap, offsets, mr = _mesh_cloud(cloud, "cloud_mesh_field")
+    S = _mesh_slots(lattice, slots, B, "cloud_mesh_field")
+    field = torch.zeros((S, MESH_BLOCK_NODES), dtype=torch.float32, device=offsets.device)
+    _lib.call("etch_cloud_mesh_field", B, S, mr, pos, moment, cap, offsets, _mesh_voxel(voxel, "cloud_mesh_field"), float(level), lattice, slots, field)
+    return field
+
+
+def cloud_mesh_grow(lattice, table_offsets, slots, field, table):
+    """etch_cloud_mesh_grow: the face test of the blocks `slots` with their `field` (S,729); marks neighbours in table IN PLACE.
+    -> flags (S,6) int32: 1 = mixed towards a block without a slot, 2 = mixed and out of the lattice."""
+    B = int(lattice.shape[0])
+    S = _mesh_slots(lattice, slots, B, "cloud_mesh_grow")
+    _need(field, torch.float32, "field"), _need(table_offsets, torch.int64, "table_offsets"), _need(table, torch.int32, "table")
+    if tuple(field.shape) != (S, MESH_BLOCK_NODES) or tuple(table_offsets.shape) != (B + 1,):
+        raise _lib.EtchHipError(f"cloud_mesh_grow: field must be ({S},{MESH_BLOCK_NODES}) and table_offsets ({B + 1},)")
+    flags = torch.zeros((S, 6), dtype=torch.int32, device=field.device)
+    _lib.call("etch_cloud_mesh_grow", B, S, lattice, table_offsets, slots, field, table, flags)
+    _lib.wrote(table)
+    return flags
+
+
+def cloud_mesh_extract(lattice, voxel, slots, field):
+    """etch_cloud_mesh_extract, both launches: the counts, their prefix sum (torch.cumsum, one read of the total), the faces.  slots sorted by
+    (cloud, block) give the faces in DESIGN section 27's order.  -> counts (S,512) int32, face_keys (F,3) int64, face_pos (F,3,3) fp32."""
+    B = int(lattice.shape[0])
+    S = _mesh_slots(lattice, slots, B, "cloud_mesh_extract")
+    _need(field, torch.float32, "field")
+    if tuple(field.shape) != (S, MESH_BLOCK_NODES):
+        raise _lib.EtchHipError(f"cloud_mesh_extract: field must be ({S},{MESH_BLOCK_NODES}), got {tuple(field.shape)}")
+    h, dev = _mesh_voxel(voxel, "cloud_mesh_extract"), field.device
+    counts = torch.zeros((S, MESH_BLOCK_CELLS), dtype=torch.int32, device=dev)
+    _lib.call("etch_cloud_mesh_extract", B, S, 0, lattice, h, slots, field, counts, None, None, None)
+    inclusive = torch.cumsum(counts.reshape(-1), 0, dtype=torch.int64)
+    F = int(inclusive[-1]) if S else 0
+    keys = torch.zeros((F, 3), dtype=torch.int64, device=dev)
+    fpos = torch.zeros((F, 3, 3), dtype=torch.float32, device=dev)
+    if F:
+        cell_offsets = (inclusive - counts.reshape(-1)).contiguous()
+        _lib.call("etch_cloud_mesh_extract", B, S, F, lattice, h, slots, field, None, cell_offsets, keys, fpos)
+    return counts, keys, fpos
+
+
+def cloud_mesh_weld(face_keys, face_pos):
+    """Integer welding of ONE cloud's faces: the distinct keys in ascending order (torch.unique) are the vertices.  -> vertex keys (V) int64,
+    verts (V,3) fp32, faces (F,3) int32.  A key has the same position bits wherever it was produced, so any of its copies serves."""
+    keys, inverse = torch.unique(face_keys.reshape(-1), sorted=True, return_inverse=True)
+    verts = torch.zeros((keys.numel(), 3), dtype=torch.float32, device=face_keys.device)
+    verts[inverse] = face_pos.reshape(-1, 3)
+    return keys, verts, inverse.reshape(-1, 3).to(torch.int32).contiguous()
+
+
+def mesh_components(V, faces, passes=4):
+    """etch_mesh_components until no label changes (one int32 read per `passes` rounds) -> labels (V) int32: the lowest vertex of each component."""
+    _need(faces, torch.int32, "faces")
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise _lib.EtchHipError(f"mesh_components: faces must be (F,3), got {tuple(faces.shape)}")
+    labels = torch.zeros((int(V),), dtype=torch.int32, device=faces.device)
+    changed = torch.zeros((1,), dtype=torch.int32, device=faces.device)
+    init = 1
+    while True:
+        _lib.call("etch_mesh_components", int(V), int(faces.shape[0]), faces, init, int(passes), labels, changed)
+        init = 0
+        if not int(changed[0]):
+            return labels
+
+
+def mesh_keep_component(verts, faces, labels, label):
+    """etch_mesh_keep_component: the vertices and faces of the component `label`, order kept, re-indexed (the prefix sums are torch.cumsum)."""
+    _need(verts, torch.float32, "verts"), _need(faces, torch.int32, "faces"), _need(labels, torch.int32, "labels")
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    if tuple(verts.shape) != (V, 3) or tuple(faces.shape) != (F, 3) or tuple(labels.shape) != (V,):
+        raise _lib.EtchHipError("mesh_keep_component: verts (V,3), faces (F,3), labels (V,)")
+    kv = labels == int(label)
+    vp = torch.cumsum(kv, 0, dtype=torch.int64)
+    fp = torch.cumsum(kv[faces[:, 0].long()], 0, dtype=torch.int64) if F else torch.zeros((0,), dtype=torch.int64, device=verts.device)
+    nv, nf = (int(vp[-1]) if V else 0), (int(fp[-1]) if F else 0)
+    out_v = torch.zeros((nv, 3), dtype=torch.float32, device=verts.device)
+    out_f = torch.zeros((nf, 3), dtype=torch.int32, device=verts.device)
+    _lib.call("etch_mesh_keep_component", V, F, verts, faces, labels, int(label), vp, fp, nv, nf, out_v, out_f)
+    return out_v, out_f

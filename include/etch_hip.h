@@ -1290,6 +1290,51 @@ int etch_smpl_surface_refine_contain_cloud(int B, int N, int V, int F, int nj, i
                                            int contain_every, float* params, float* verts, float* joints, float* loss_trace, float* loss_last,
                                            void* workspace, void* stream);
 
+/* ---- raw point clouds: a watertight mesh from the winding field (csrc/cloud_mesh.hip, csrc/cloud_mesh_solve.h) ------------- */
+#define ETCH_MESH_BLOCK_NODES 729        /* 9^3 nodes of a block of 8 x 8 x 8 cells */
+#define ETCH_MESH_BLOCK_CELLS 512
+#define ETCH_MESH_TABLE_INACTIVE (-1)    /* block table: the block is not evaluated */
+#define ETCH_MESH_TABLE_MARK (-2)        /* block table: marked by etch_cloud_mesh_seed or etch_cloud_mesh_grow; the caller gives it a slot >= 0 */
+
+/* The lattice of the oriented cloud b (pos, cap, offsets as etch_cloud_winding_number takes them) for the voxel h = `voxel` > 0: node g of an axis
+ * lies at fp32((double) g h), a block covers the nodes 8 B .. 8 B + 8 of every axis.  lattice (B,6) int32 = lo[3], hi[3] in blocks with
+ * lo = floor(min / (8 h)) - pad_blocks, hi = floor(max / (8 h)) + 1 + pad_blocks over the rows with cap > 0 and a finite pos, in fp64.  status (B)
+ * int32 (written): ETCH_CLOUD_STATUS_EMPTY without such a row, ETCH_CLOUD_STATUS_RANGE where an axis has more than 2^20 - 1 nodes, the lattice more
+ * than 2^24 blocks or |lo|, |hi| reach 2^27; lo = hi = 0 then. */
+int etch_cloud_mesh_lattice(int B, int max_rows, const float* pos, const float* cap, const int* offsets, double voxel, int pad_blocks, int* lattice,
+                            int* status, void* stream);
+/* Round 0: the block of every row that counts, dilated by seed_dilate (0 .. 2) blocks in the 26-neighbourhood and clipped to the lattice, gets
+ * ETCH_MESH_TABLE_MARK in table.  table: one int32 per block of every cloud, cloud b's at table_offsets[b] (B+1 int64 in device memory), block
+ * (x, y, z) local to lo at (x ny + y) nz + z -- the order of the block keys.  A cloud with a status bit is skipped. */
+int etch_cloud_mesh_seed(int B, int max_rows, const float* pos, const float* cap, const int* offsets, double voxel, int seed_dilate, const int* lattice,
+                         const int* status, const long long* table_offsets, int* table, void* stream);
+/* field (S,729) fp32: s = fabsf(w) - level at the nodes of the blocks slots (S,2) int32 = (cloud, the block's index in the cloud's table), node
+ * (ox, oy, oz) of a block at (ox 9 + oy) 9 + oz.  w is etch_cloud_winding_number's at the node's fp32 position, to the bit; one workgroup per slot,
+ * no workspace, no atomics: a node shared by two blocks has the same bits in both.  A slot that names no block of its lattice is not written. */
+int etch_cloud_mesh_field(int B, int S, int max_rows, const float* pos, const float* moment, const float* cap, const int* offsets, double voxel, float level,
+                          const int* lattice, const int* slots, float* field, void* stream);
+/* The face test of the S blocks of the last round (slots, field as above): face f (-x, +x, -y, +y, -z, +z) is mixed when its 81 nodes are neither
+ * all inside nor all outside, inside = !(s < 0).  flags (S,6) int32 = 0, or 1: mixed towards a block that has no slot -- that block now holds
+ * ETCH_MESH_TABLE_MARK --, or 2: mixed and pointing out of the lattice (clipped). */
+int etch_cloud_mesh_grow(int B, int S, const int* lattice, const long long* table_offsets, const int* slots, const float* field, int* table, int* flags,
+                         void* stream);
+/* Marching tetrahedra on the Freudenthal split of every cell of the S blocks, for ANY field values.  counts (S,512) int32 or NULL = triangles per
+ * cell, cell (cx, cy, cz) at (cx 8 + cy) 8 + cz.  With cell_offsets (S,512) int64 = the exclusive prefix sum of the counts and F their total, cell c
+ * writes its triangles (tetrahedron 0..5, triangle 0..1) from face cell_offsets[c] on: face_keys (F,3) int64 = the 63-bit keys of the three
+ * crossings, (((ix 2^20 + iy) 2^20 + iz) 8 + kind) with i the edge's lower node local to the lattice and kind = 4 dx + 2 dy + dz the edge's offset;
+ * face_pos (F,3,3) fp32 = their positions, per axis t = s_n / (s_n - s_up), x = x_n + t (x_up - x_n) in fp32, one rounding per operation. */
+int etch_cloud_mesh_extract(int B, int S, long long F, const int* lattice, double voxel, const int* slots, const float* field, int* counts,
+                            const long long* cell_offsets, long long* face_keys, float* face_pos, void* stream);
+/* labels (V) int32: `passes` rounds of hooking and pointer jumping over faces (F,3) int32; init != 0 starts from label_v = v.  changed (1) int32 is
+ * set to 0 and then to 1 by a round that lowered a label: call again (init = 0) until it stays 0; then label_v = the lowest vertex index of v's
+ * connected component. */
+int etch_mesh_components(int V, int F, const int* faces, int init, int passes, int* labels, int* changed, void* stream);
+/* The vertices with labels == label and the faces whose first vertex has it, compacted with their order kept: vert_prefix (V), face_prefix (F)
+ * int64 = the INCLUSIVE prefix sums of those two conditions, kept_verts, kept_faces their totals.  out_verts (kept_verts,3) fp32, out_faces
+ * (kept_faces,3) int32 re-indexed. */
+int etch_mesh_keep_component(int V, int F, const float* verts, const int* faces, const int* labels, int label, const long long* vert_prefix,
+                             const long long* face_prefix, long long kept_verts, long long kept_faces, float* out_verts, int* out_faces, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
